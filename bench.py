@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the wavefront path-tracing hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: set-up, pre-warm, the W warm-up steps, the K timed steps, the result line.  --full adds every
+other leg listed below (per-stage breakdown, tile gather, roofline replay, whole-frame job, CPU baseline, config 5); the --no-* options
+leave legs out of a --full run.  --dump-outputs DIR writes the frame the K timed steps accumulated (see dump_outputs()).
 
 With N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES: it starts N fresh child processes (rank i on GPU i,
 rendezvous on 127.0.0.1) before anything here has touched a GPU, passes rank 0's output through and exits with the children's status.
@@ -22,7 +26,7 @@ once per K steps: it is timed on its own right after (`tile_gather_ms`) and is i
 rank 0's GPU: the metric excludes scene build / upload and the final host read-back).  What is scaled ("weak"): the per-GPU pool is fixed, so every rank does one wavefront
 iteration over 2^21 paths per step whatever N is; the frame it fills is 1/N of the image.
 
-Besides `value` the line carries
+Besides `value` the line of a --full run carries
   full_frame    the WHOLE job of the metric's definition (BASELINE.md section 2): W*H*spp paths fed, then the drain -- seconds, paths, Mpaths/s;
                 with N ranks each renders its band's share (a fixed total job: strong scaling), time = slowest rank
   roofline      for the dominant kernel (k_cast_f, both ray casts in one persistent launch), see roofline_object()
@@ -116,7 +120,37 @@ def parse_args():
     ap.add_argument("--config5-steps", type=int, default=40)
     ap.add_argument("--config5-prewarm", type=int, default=60)
     ap.add_argument("--cpu-iters", type=int, default=24, help="oracle iterations timed for cpu_baseline (~0.6 s each at pool 2^21 on 16 threads)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-stage breakdown, tile gather, roofline, full_frame, cpu_baseline, config5 (the --no-* options leave legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame accumulated by the last timed step to DIR/*.npy (rank 0)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, frame):
+    """Writes what the timed path computed, as of its last step: the accumulation target (H x W x 4 float32, the reference's render
+    texture; channel 3 holds the per-pixel sample count as uint32 bits).
+      framebuffer_rgb.npy      float32 (H, W, 3)  running mean radiance
+      framebuffer_samples.npy  float64 (H, W)     samples accumulated per pixel
+    When that exceeds DUMP_LIMIT_BYTES (frames larger than 4K), a fixed seeded sample of pixels is written instead, flattened, with
+    pixel_index.npy (float64, row-major pixel numbers) naming them."""
+    import numpy as np
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    H, W = frame.shape[:2]
+    rgb = frame[..., :3].reshape(H * W, 3)
+    samples = frame[..., 3].view(np.uint32).reshape(H * W).astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    per_pixel = 3 * 4 + 8
+    if H * W * per_pixel <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "framebuffer_rgb.npy"), rgb.reshape(H, W, 3))
+        np.save(os.path.join(directory, "framebuffer_samples.npy"), samples.reshape(H, W))
+        return
+    n = DUMP_LIMIT_BYTES // (per_pixel + 8)
+    idx = np.sort(np.random.default_rng(20261016).choice(H * W, size=n, replace=False))
+    np.save(os.path.join(directory, "framebuffer_rgb.npy"), rgb[idx])
+    np.save(os.path.join(directory, "framebuffer_samples.npy"), samples[idx])
+    np.save(os.path.join(directory, "pixel_index.npy"), idx.astype(np.float64))
 
 
 def visible_gpus():
@@ -354,7 +388,6 @@ def main_rank(args):
     r.synchronize()
     r.reset_stats()
     r.enable_timing(0 if args.no_stage_timing else 2)   # two HIP events per step, around the ray-cast launch only
-    tile_t = torch.empty((rows, W, 4), dtype=torch.float32, device="cuda")
 
     barrier()
     t_start = time.perf_counter()
@@ -363,33 +396,41 @@ def main_rank(args):
     barrier()
     elapsed = time.perf_counter() - t_start
     # the tile gather happens once per FRAME (thousands of steps), not once per K steps: it is timed on its own here and is part of the
-    # full_frame leg below, where it belongs
-    t_gather = time.perf_counter()
-    r.copy_framebuffer_to_device(tile_t.data_ptr(), tile_t.numel() * 4)  # synchronises the renderer's stream
-    frame = tiles.gather_tiles(tile_t if coll_dev == "cuda" else tile_t.cpu(), W, H, rank, world, dist if use_dist else None, force_collective=args.force_dist)
-    barrier()
-    gather_ms = (time.perf_counter() - t_gather) * 1e3
+    # full_frame leg below, where it belongs; --dump-outputs takes the gathered frame
+    gather_ms = None
+    if args.full or args.dump_outputs:
+        tile_t = torch.empty((rows, W, 4), dtype=torch.float32, device="cuda")
+        t_gather = time.perf_counter()
+        r.copy_framebuffer_to_device(tile_t.data_ptr(), tile_t.numel() * 4)  # synchronises the renderer's stream
+        frame = tiles.gather_tiles(tile_t if coll_dev == "cuda" else tile_t.cpu(), W, H, rank, world, dist if use_dist else None, force_collective=args.force_dist)
+        barrier()
+        gather_ms = (time.perf_counter() - t_gather) * 1e3
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, frame.cpu().numpy())
+        del frame
 
     st = r.stats()
     if st.flags & (capi.STAT_STACK_OVERFLOW | capi.STAT_CAST_ABORTED):
         raise SystemExit("bench.py: the ray cast reported an error (gmupt_stats.flags = %#x): the numbers would be invalid" % st.flags)
     r.enable_timing(0)
     cast_ms = st.ms_extend / max(st.timed_iterations, 1)
-    # per-stage breakdown: a short untimed continuation with events around every stage group
-    r.reset_stats(); r.enable_timing(1); step(r, cam, 50); stb = r.stats(); r.enable_timing(0)
+    stb = None
+    if args.full:
+        # per-stage breakdown: a short untimed continuation with events around every stage group
+        r.reset_stats(); r.enable_timing(1); step(r, cam, 50); stb = r.stats(); r.enable_timing(0)
     total_paths, total_segments = all_sum([float(st.paths_completed), float(st.segments)])
     elapsed = all_max(elapsed)
-    gather_ms = all_max(gather_ms)
+    if gather_ms is not None:
+        gather_ms = all_max(gather_ms)
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_baseline = run_cpu_baseline(r, cam, scene, W, H, rows, y0, args)
     r.close()
-    del frame
 
     # ------------------------------------------------------------------ roofline: deterministic replay with the counting kernels
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         r2, cam2 = make_renderer(True)
         step(r2, cam2, args.prewarm + args.warmup)
         r2.synchronize(); r2.reset_stats()
@@ -406,7 +447,7 @@ def main_rank(args):
 
     # ------------------------------------------------------------------ the whole job: W*H*spp paths, feed + drain (each rank its band)
     full_frame = None
-    if not args.no_full_frame:
+    if args.full and not args.no_full_frame:
         budget = W * rows * args.spp
         rf, camf = make_renderer(False, budget=budget)
         rf.synchronize()
@@ -428,14 +469,14 @@ def main_rank(args):
                       "note": "feed W*H*spp paths then drain; the drain ends 512 iterations after the budget ran out (the reference's NaN-throughput paths never end, DESIGN.md section 5)"}
 
     config5 = None
-    if rank == 0 and world == 1 and not args.no_config5:
+    if args.full and rank == 0 and world == 1 and not args.no_config5:
         config5 = config5_leg(capi, scenes, dev, args)
 
     if rank == 0:
         value = total_paths / elapsed / 1e6
         out = {
             "metric": "Mpaths/s @1920x1080x64spp, 260k-tri scene", "value": round(value, 3), "unit": "Mpaths/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "headline": "value = completed paths / wall time of the K timed steady-state steps (all ranks; barrier + device synchronisation on both sides); tile_gather_ms = one gather of the tiles to rank 0, which happens once per frame and is inside full_frame = the whole W*H*spp job incl. ramp-up, drain and gather",
             "config": {"workload": "config3: %d-tri seeded sphere room (%d nodes), %dx%d, %d spp steady state, UE4+glass+NEE, unbounded depth"
@@ -444,9 +485,9 @@ def main_rank(args):
                        "scaled": "per-GPU pool fixed; a step = one wavefront iteration of every rank's pool; the frame is split into %d row band(s)" % world,
                        "parallelism": "tile%d" % world},
             "msegments_per_s": round(total_segments / elapsed / 1e6, 1),
-            "stage_ms": {"logic": round(stb.ms_logic / max(stb.timed_iterations, 1), 4), "material": round(stb.ms_material / max(stb.timed_iterations, 1), 4),
-                         "raycast": round(cast_ms, 4), "shadow_separate": round(stb.ms_shadow / max(stb.timed_iterations, 1), 4)},
-            "tile_gather_ms": round(gather_ms, 3), "scene_build_s": round(build_s, 2), "collectives": (args.backend if use_dist else "none (one rank)"),
+            "stage_ms": {"logic": round(stb.ms_logic / max(stb.timed_iterations, 1), 4) if stb else None, "material": round(stb.ms_material / max(stb.timed_iterations, 1), 4) if stb else None,
+                         "raycast": round(cast_ms, 4), "shadow_separate": round(stb.ms_shadow / max(stb.timed_iterations, 1), 4) if stb else None},
+            "tile_gather_ms": round(gather_ms, 3) if gather_ms is not None else None, "scene_build_s": round(build_s, 2), "collectives": (args.backend if use_dist else "none (one rank)"),
             "full_frame": full_frame, "roofline": roofline, "cpu_baseline": cpu_baseline, "config5": config5,
         }
         print(json.dumps(out), flush=True)

@@ -92,7 +92,7 @@ def _bench_child(port, force_dist, out_path, q):
         spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
         bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
         argv = ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--prewarm", "30", "--pool", "65536", "--width", "320", "--height", "181", "--spheres", "12", "--subdiv", "2",
-                "--spp", "2", "--no-cpu-baseline", "--no-roofline", "--no-config5", "--backend", "nccl"] + (["--force-dist"] if force_dist else [])
+                "--spp", "2", "--full", "--no-cpu-baseline", "--no-roofline", "--no-config5", "--backend", "nccl"] + (["--force-dist"] if force_dist else [])
         sys.argv = argv
         with open(out_path, "w") as f:
             old = sys.stdout; sys.stdout = f

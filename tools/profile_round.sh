@@ -16,9 +16,9 @@ if [ "$MODE" = config5 ]; then
   timeout -k 10 500 python3 tools/config5.py --count --cache /tmp/config5_scene.npz --out $OUT/run.json > $OUT/run.log 2>&1 || { echo "plain run failed"; tail -5 $OUT/run.log; exit 1; }
   CMD="python3 tools/config5.py --cache /tmp/config5_scene.npz"; SHORT="--prewarm 40 --steps 10"; SKIP=40
 else
-  timeout -k 10 500 python3 bench.py > $OUT/run.log 2>&1 || { echo "plain run failed"; tail -5 $OUT/run.log; exit 1; }
+  timeout -k 10 500 python3 bench.py --full > $OUT/run.log 2>&1 || { echo "plain run failed"; tail -5 $OUT/run.log; exit 1; }
   tail -1 $OUT/run.log > $OUT/run.json
-  CMD="python3 bench.py --no-cpu-baseline --no-roofline --no-full-frame --no-config5"; SHORT="--prewarm 260 --steps 20 --warmup 5"; SKIP=265
+  CMD="python3 bench.py --full --no-cpu-baseline --no-roofline --no-full-frame --no-config5"; SHORT="--prewarm 260 --steps 20 --warmup 5"; SKIP=265
 fi
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace.log 2>&1 || { echo "trace pass failed"; tail -5 $OUT/trace.log; exit 1; }
 cp $OUT/trace/*/*kernel_stats.csv $OUT/kernel_stats.csv

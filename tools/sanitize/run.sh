@@ -4,8 +4,15 @@ set -e
 cd "$(dirname "$0")"
 SRC="builder_main.cpp ../../gmu-path-tracer_amd/host/sbvh_builder.cpp"
 export GMUPT_BUILD_THREADS=8 GMUPT_BUILD_FANOUT=512
-g++ -std=c++17 -O1 -g -fsanitize=thread -ffp-contract=off -o /tmp/gmupt_builder_tsan $SRC -lpthread
-TSAN_OPTIONS="halt_on_error=1" /tmp/gmupt_builder_tsan 20000
-g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off -o /tmp/gmupt_builder_asan $SRC -lpthread
-ASAN_OPTIONS="detect_leaks=1" /tmp/gmupt_builder_asan 20000
+# gcc's sanitizer runtimes expect the kernel's default 28 bits of mmap randomisation: where a kernel uses more, a PIE can land outside
+# ThreadSanitizer's application range ("FATAL: ThreadSanitizer: unexpected memory mapping").  The sanitized programs therefore run with
+# address randomisation off for their own process (a personality flag, as LLVM's runtime does itself), where the system allows it.
+NORAND=""
+setarch "$(uname -m)" -R true 2>/dev/null && NORAND="setarch $(uname -m) -R"
+BIN=$(mktemp -d)   # a private directory per run: fixed names would collide with another user's run
+trap 'rm -rf "$BIN"' EXIT
+g++ -std=c++17 -O1 -g -fsanitize=thread -ffp-contract=off -o "$BIN/gmupt_builder_tsan" $SRC -lpthread
+TSAN_OPTIONS="halt_on_error=1" $NORAND "$BIN/gmupt_builder_tsan" 20000
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_builder_asan" $SRC -lpthread
+ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_builder_asan" 20000
 echo "sanitizers: clean"
