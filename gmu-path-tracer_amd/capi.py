@@ -74,7 +74,29 @@ class SbvhParams(C.Structure):
                 ("min_leaf_size", C.c_int32), ("max_leaf_size", C.c_int32), ("node_cost", C.c_float), ("tri_cost", C.c_float)]
 
 
-ERR_CAST_FAULT = -7
+ERR_INVALID_ARGUMENT, ERR_HIP, ERR_OUT_OF_MEMORY, ERR_NOT_BOUND, ERR_UNSUPPORTED, ERR_IO, ERR_CAST_FAULT = -1, -2, -3, -4, -5, -6, -7
+MAX_TRACE_BATCH = 1 << 26   # rays per batch of gmupt_trace_rays
+
+
+class Ray(C.Structure):
+    """gmupt_ray: 32 bytes; a (N, 8) float32 tensor holds N of them (origin xyz, tmax, direction xyz, pad)."""
+    _fields_ = [("origin", C.c_float * 3), ("tmax", C.c_float), ("direction", C.c_float * 3), ("pad", C.c_uint32)]
+
+
+class Hit(C.Structure):
+    """gmupt_hit: 32 bytes (t, u, v, triangle, light, material, pad[2])."""
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("triangle", C.c_int32), ("light", C.c_uint32),
+                ("material", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+class TraceInfo(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("pad_", C.c_uint32), ("redo_rays", C.c_uint64), ("ms", C.c_double)]
+
+
+assert C.sizeof(Ray) == 32 and C.sizeof(Hit) == 32 and C.sizeof(TraceInfo) == 24
+ray_dtype = np.dtype([("origin", "<f4", 3), ("tmax", "<f4"), ("direction", "<f4", 3), ("pad", "<u4")])
+hit_dtype = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("triangle", "<i4"), ("light", "<u4"), ("material", "<u4"), ("pad", "<u4", 2)])
+assert ray_dtype.itemsize == 32 and hit_dtype.itemsize == 32
 
 
 class GmuptError(RuntimeError):
@@ -114,6 +136,9 @@ SYMBOLS = {
     "gmupt_reset_stats": (C.c_int, [_P]),
     "gmupt_enable_timing": (C.c_int, [_P, C.c_int]),
     "gmupt_render_budget": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "gmupt_trace_rays": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(TraceInfo)]),
+    "gmupt_camera_pick_ray": (C.c_int, [C.POINTER(CameraBuffer), C.c_float, C.c_float, C.POINTER(Ray)]),
+    "gmupt_pick": (C.c_int, [_P, C.c_float, C.c_float, C.c_uint32, C.POINTER(Ray), C.POINTER(Hit)]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -209,6 +234,7 @@ class Device:
         self.h = _P()
         _check(lib().gmupt_device_create(index, C.byref(self.h)))
         _devices_created += 1
+        self.index = index
 
     def close(self):
         if self.h:
@@ -420,6 +446,44 @@ class Renderer:
         _check(lib().gmupt_render_budget(self.h, camera.h, max_iterations, C.byref(it)))
         return it.value
 
+    # ray queries (gmupt_trace_rays / gmupt_pick)
+    def trace(self, closest=None, any=None, light_count=0, info=None):
+        """Closest-hit and any-hit queries on caller rays in one launch (include/gmupt.h states the semantics).
+
+        closest / any: (N, 8) float32 rays (origin xyz, tmax, direction xyz, pad) as torch tensors on this renderer's GPU, or numpy
+        arrays (staged through a torch tensor on the GPU); None for an empty batch.  Returns (hits, occluded) of the kind given:
+        hits (N, 8) float32 gmupt_hit records (hit_fields() splits them; words 3-7 are integers, compare them as bits), occluded (M,) int32 for torch / uint32 for numpy.  torch's
+        current stream is synchronised first; the call itself synchronises the renderer's stream.  info: optional TraceInfo to fill."""
+        import torch
+        dev = torch.device("cuda", getattr(self.dev, "index", 0))
+        as_numpy = isinstance(closest, np.ndarray) or isinstance(any, np.ndarray)
+
+        def stage(a):
+            if a is None:
+                return torch.empty((0, 8), dtype=torch.float32, device=dev)
+            t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)).to(dev) if isinstance(a, np.ndarray) else a
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 8 or not t.is_cuda:
+                raise GmuptError("trace: rays must be (N, 8) float32 on the GPU (or numpy)", ERR_INVALID_ARGUMENT)
+            return t.contiguous()
+
+        c, a = stage(closest), stage(any)
+        hits = torch.empty((c.shape[0], 8), dtype=torch.float32, device=dev)
+        occ = torch.empty((a.shape[0],), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        ti = info if info is not None else TraceInfo()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        _check(lib().gmupt_trace_rays(self.h, ptr(c), c.shape[0], ptr(hits), ptr(a), a.shape[0], ptr(occ), int(light_count), C.byref(ti)))
+        self.last_trace = ti
+        if as_numpy:
+            return hits.cpu().numpy(), occ.cpu().numpy().view(np.uint32)
+        return hits, occ
+
+    def pick(self, px, py, light_count=0):
+        """gmupt_pick: (Ray, Hit) of the un-jittered primary ray through whole-frame pixel (px, py) of the current camera."""
+        ray, hit = Ray(), Hit()
+        _check(lib().gmupt_pick(self.h, float(px), float(py), int(light_count), C.byref(ray), C.byref(hit)))
+        return ray, hit
+
     # reference-layout debug access
     def read_path_state(self):
         out = np.empty(self.pool * STATE_BYTES, dtype=np.uint8)
@@ -451,6 +515,21 @@ class Renderer:
         if self.h:
             lib().gmupt_renderer_destroy(self.h)
             self.h = _P()
+
+
+def camera_pick_ray(cam_buffer, px, py):
+    """gmupt_camera_pick_ray (host only): the un-jittered primary ray of newPath.hlsl:36-39 through whole-frame pixel (px, py)."""
+    ray = Ray()
+    _check(lib().gmupt_camera_pick_ray(C.byref(cam_buffer), float(px), float(py), C.byref(ray)))
+    return ray
+
+
+def hit_fields(hits):
+    """Splits (N, 8) gmupt_hit records (numpy or torch) into a dict of numpy arrays: t, u, v (float32), triangle (int32), light,
+    material (uint32)."""
+    h = hits.cpu().numpy() if hasattr(hits, "cpu") else np.asarray(hits)
+    rec = np.ascontiguousarray(h, dtype=np.float32).reshape(-1, 8).view(hit_dtype)[:, 0]
+    return {k: rec[k].copy() for k in ("t", "u", "v", "triangle", "light", "material")}
 
 
 def sbvh_build(verts, indices, vertex_material=None, params=None):

@@ -1,6 +1,7 @@
 // C-ABI of libgmupt.so (see include/gmupt.h for the contract and the reference call sites each entry replaces).
 // Host code only; the kernels live in pt_kernels.hip.
 #include "pt_device.hpp"
+#include "detmath.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
 #include "../host/TextureLoader.hpp"
@@ -47,6 +48,8 @@ uint32_t deferred_block_threads();
 uint32_t traversal_overflow_entries();
 uint32_t traversal_top_capacity(uint32_t maxDepth);
 uint32_t traversal_wide_top_capacity();
+void launch_trace_wide(const RenderParams& p, const gmupt_ray* closest, uint32_t nClosest, gmupt_hit* hits, const gmupt_ray* any, uint32_t nAny,
+                       uint32_t* occluded, uint32_t lightCount, hipStream_t s);
 }
 using namespace gmupt;
 
@@ -216,6 +219,9 @@ struct gmupt_renderer {
     void* travNodes = nullptr; void* travTris = nullptr; void* travRecs = nullptr; void* travWide = nullptr; void* travPairs = nullptr; void* travPairRef = nullptr;
     int travMode = 70; // GMUPT_TRAVERSAL: "wide" (default) both ray casts in one launch over the 4-wide collapse | "cast0" the same over the binary tree | "def0" separate launches; the other rungs of the ladder exist in -DGMUPT_VARIANTS builds only
     uint32_t castFlags = 0; // GMUPT_STAT_* bits of the ray-cast kernels launched since the last reset
+    // ray queries (gmupt_trace_rays): work counters + statistics of their own, allocated on first use; one ray + one hit for gmupt_pick
+    uint32_t* queryCounters = nullptr; DevStats* queryStats = nullptr; void* pickBuf = nullptr;
+    hipEvent_t queryEv[2] = { nullptr, nullptr };
 };
 
 static int dev_alloc(gmupt_renderer* r, void** ptr, size_t bytes, int fill)
@@ -245,6 +251,7 @@ extern "C" void gmupt_renderer_destroy(gmupt_renderer* r)
     (void)hipSetDevice(r->dev->id);
     if (r->stream) (void)hipStreamSynchronize(r->stream);
     for (auto& se : r->evPool) for (auto& e : se.e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : r->queryEv) if (e) (void)hipEventDestroy(e);
     for (void* a : r->allocs) (void)hipFree(a);
     if (r->p.fb) (void)hipFree(r->p.fb);
     if (r->p.listHead) (void)hipFree(r->p.listHead);
@@ -909,6 +916,97 @@ extern "C" int gmupt_reset_stats(gmupt_renderer* r)
     HIP_TRY(hipStreamSynchronize(r->stream));
     for (double& m : r->msStage) m = 0.0;
     r->timedIters = 0; r->iterations = 0; r->castFlags = 0;
+    return GMUPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ ray queries
+static_assert(sizeof(gmupt_ray) == 32 && offsetof(gmupt_ray, tmax) == 12 && offsetof(gmupt_ray, direction) == 16, "gmupt_ray layout");
+static_assert(sizeof(gmupt_hit) == 32 && offsetof(gmupt_hit, triangle) == 12 && offsetof(gmupt_hit, light) == 16 && offsetof(gmupt_hit, material) == 20, "gmupt_hit layout");
+static_assert(sizeof(gmupt_trace_info) == 24 && offsetof(gmupt_trace_info, redo_rays) == 8 && offsetof(gmupt_trace_info, ms) == 16, "gmupt_trace_info layout");
+
+extern "C" int gmupt_trace_rays(gmupt_renderer* r, const gmupt_ray* closest, uint32_t n_closest, gmupt_hit* hits,
+                                const gmupt_ray* any, uint32_t n_any, uint32_t* occluded, uint32_t light_count, gmupt_trace_info* info)
+{
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_trace_rays: null renderer");
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_trace_rays: no scene bound");
+    constexpr uint32_t kMaxBatch = 1u << 26;
+    if (n_closest > kMaxBatch || n_any > kMaxBatch) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_trace_rays: %u closest-hit / %u any-hit rays (at most 2^26 per batch)", n_closest, n_any);
+    if (n_closest && (!closest || !hits)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_trace_rays: null closest-hit rays or hits");
+    if (n_any && (!any || !occluded)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_trace_rays: null any-hit rays or occluded flags");
+    if ((n_closest && (((uintptr_t)closest | (uintptr_t)hits) & 15u)) || (n_any && (((uintptr_t)any & 15u) || ((uintptr_t)occluded & 3u))))
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_trace_rays: misaligned pointer (rays and hits need 16 bytes, occluded flags 4)");
+    // the wide collapse and the limits of launch_cast_wide's 32-bit buffer offsets, here including the TriPair table
+    const RenderParams& p = r->p;
+    if (!p.trav.wnodes || p.extendPrune || p.shadowPrune)
+        return fail(GMUPT_ERR_UNSUPPORTED, "gmupt_trace_rays: the bound scene has no wide collapse (it needs GMUPT_TRAVERSAL=wide, no GMUPT_EXTEND_PRUNE / GMUPT_SHADOW_PRUNE, "
+                    "and child boxes inside their parents)");
+    if ((uint64_t)p.trav.wideCount * 128ull >= (1ull << 31) || ((uint64_t)p.scene.numTris + 1ull) * 48ull >= (1ull << 31) || (uint64_t)p.trav.numPairs * 80ull >= (1ull << 31))
+        return fail(GMUPT_ERR_UNSUPPORTED, "gmupt_trace_rays: the wide tables of the bound scene exceed 2 GiB (%u nodes, %u references, %u pairs)", p.trav.wideCount, p.scene.numTris, p.trav.numPairs);
+    HIP_TRY(hipSetDevice(r->dev->id));
+    if (!r->queryStats) {
+        int rc = dev_alloc(r, (void**)&r->queryCounters, 128, 0);
+        if (rc == GMUPT_OK) rc = dev_alloc(r, (void**)&r->queryStats, sizeof(DevStats), 0);
+        if (rc != GMUPT_OK) { r->queryStats = nullptr; return rc; }
+        for (hipEvent_t& e : r->queryEv) HIP_TRY(hipEventCreate(&e));
+    }
+    const uint32_t launchFlags = GMUPT_STAT_FUSED_CAST | GMUPT_STAT_CAST_WIDE;
+    if (n_closest == 0 && n_any == 0) { HIP_TRY(hipStreamSynchronize(r->stream)); if (info) info->flags = launchFlags; return GMUPT_OK; }
+    // behind whatever the renderer has queued; the renderer's counters and statistics are left alone
+    HIP_TRY(hipMemsetAsync(r->queryCounters, 0, 128, r->stream));
+    HIP_TRY(hipMemsetAsync(r->queryStats, 0, sizeof(DevStats), r->stream));
+    RenderParams q = p;
+    q.travCounters = r->queryCounters; q.stats = r->queryStats;
+    HIP_TRY(hipEventRecord(r->queryEv[0], r->stream));
+    launch_trace_wide(q, closest, n_closest, hits, any, n_any, occluded, light_count, r->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(r->queryEv[1], r->stream));
+    DevStats ds;
+    HIP_TRY(hipMemcpyAsync(&ds, r->queryStats, sizeof(ds), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, r->queryEv[0], r->queryEv[1]));
+    const uint32_t flags = launchFlags | ((ds.stackOverflow & 1u) ? GMUPT_STAT_STACK_OVERFLOW : 0u) | ((ds.stackOverflow & 2u) ? GMUPT_STAT_CAST_ABORTED : 0u);
+    if (info) { info->flags = flags; info->redo_rays = ds.castRedoRays; info->ms = ms; }
+    if (ds.stackOverflow & 2u) return fail(GMUPT_ERR_CAST_FAULT, "gmupt_trace_rays: a wave of the ray cast left its loop at the iteration limit (GMUPT_STAT_CAST_ABORTED): the results are invalid");
+    if (ds.stackOverflow & 1u) return fail(GMUPT_ERR_CAST_FAULT, "gmupt_trace_rays: a traversal stack overflowed (GMUPT_STAT_STACK_OVERFLOW): the results are invalid");
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_camera_pick_ray(const gmupt_camera_buffer* cam, float px, float py, gmupt_ray* out)
+{
+    if (!cam || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_camera_pick_ray: null argument");
+    // newPath.hlsl:36-39 with the jitter at 0: (x + 0) * pixelSize is x * pixelSize for every float x
+    const float u = px * cam->pixelSize[0], v = py * cam->pixelSize[1];
+    const f3 ulc = mk3(cam->upperLeftCorner[0], cam->upperLeftCorner[1], cam->upperLeftCorner[2]);
+    const f3 hor = mk3(cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]);
+    const f3 ver = mk3(cam->vertical[0], cam->vertical[1], cam->vertical[2]);
+    const f3 dir = normalize3((ulc + hor * u) - ver * v);
+    std::memset(out, 0, sizeof(*out));
+    for (int k = 0; k < 3; k++) out->origin[k] = cam->position[k];
+    out->direction[0] = dir.x; out->direction[1] = dir.y; out->direction[2] = dir.z;
+    out->tmax = std::numeric_limits<float>::max();   // FLT_MAX: the reference's starting distance (structs.h:9)
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_pick(gmupt_renderer* r, float px, float py, uint32_t light_count, gmupt_ray* ray_out, gmupt_hit* hit_out)
+{
+    if (!r || !hit_out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pick: null argument");
+    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_pick: no camera set");
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_pick: no scene bound");
+    gmupt_ray ray;
+    int rc = gmupt_camera_pick_ray(&r->p.cam, px, py, &ray);
+    if (rc != GMUPT_OK) return rc;
+    HIP_TRY(hipSetDevice(r->dev->id));
+    if (!r->pickBuf) { rc = dev_alloc(r, &r->pickBuf, 64, 0); if (rc != GMUPT_OK) { r->pickBuf = nullptr; return rc; } }
+    gmupt_ray* dRay = (gmupt_ray*)r->pickBuf;
+    gmupt_hit* dHit = (gmupt_hit*)((char*)r->pickBuf + 32);
+    HIP_TRY(hipMemcpyAsync(dRay, &ray, sizeof(ray), hipMemcpyHostToDevice, r->stream));
+    rc = gmupt_trace_rays(r, dRay, 1, dHit, nullptr, 0, nullptr, light_count, nullptr);
+    if (rc != GMUPT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(hit_out, dHit, sizeof(*hit_out), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (ray_out) *ray_out = ray;
     return GMUPT_OK;
 }
 

@@ -205,6 +205,25 @@ __device__ __forceinline__ int inner_step_pruned(const TravScene& ts, const floa
         __syncthreads(); \
     }
 
+// the light spheres after the triangles (extensionRayCast.hlsl:168-194): a sphere nearer than DIST takes it; INDEX = 0 or 1 + its index.
+// (A macro, not a function: finish_extension_ray keeps the instruction stream it had before gmupt_trace_rays shared the test.)
+#define GMUPT_LIGHT_SPHERES(LIGHTS, COUNT, O, D, DIST, INDEX) \
+    uint32_t INDEX = 0; \
+    { const uint32_t lc = (COUNT) < GMUPT_MAX_LIGHTS ? (COUNT) : GMUPT_MAX_LIGHTS; \
+      for (uint32_t li = 0; li < lc; li++) { \
+          const gmupt_light L = (LIGHTS)[li]; \
+          const f3 position = mk3(L.position[0], L.position[1], L.position[2]) - (O); \
+          const float radius2 = L.radius * L.radius; \
+          const float tca = dot3(position, (D)); \
+          const float d2 = dot3(position, position) - tca * tca; \
+          if (d2 > radius2) continue; \
+          const float thc = dsqrt(radius2 - d2); \
+          float t0 = tca - thc; \
+          const float t1 = tca + thc; \
+          if (t0 < 0.0f) t0 = t1; \
+          if (t0 > 0.0f && t0 < (DIST)) { (DIST) = t0; INDEX = li + 1; } \
+      } }
+
 // the end of an extension ray: hit record of the closest triangle, then the light spheres (extensionRayCast.hlsl:168-194,218-232)
 __device__ __forceinline__ void finish_extension_ray(const RenderParams& p, uint32_t index, f3 o, f3 d, float distance, float hu, float hv, int hitRef)
 {
@@ -215,21 +234,7 @@ __device__ __forceinline__ void finish_extension_ray(const RenderParams& p, uint
         stu(p, F_TRI_0, index, (uint32_t)T.x); stu(p, F_TRI_1, index, (uint32_t)T.y);
         stu(p, F_TRI_2, index, (uint32_t)T.z); stu(p, F_TRI_MAT, index, (uint32_t)T.w);
     }
-    uint32_t lightIndex = 0;
-    const uint32_t lc = p.cam.lightCount < GMUPT_MAX_LIGHTS ? p.cam.lightCount : GMUPT_MAX_LIGHTS;
-    for (uint32_t li = 0; li < lc; li++) {
-        const gmupt_light L = p.scene.lights[li];
-        const f3 position = mk3(L.position[0], L.position[1], L.position[2]) - o;
-        const float radius2 = L.radius * L.radius;
-        const float tca = dot3(position, d);
-        const float d2 = dot3(position, position) - tca * tca;
-        if (d2 > radius2) continue;
-        const float thc = dsqrt(radius2 - d2);
-        float t0 = tca - thc;
-        const float t1 = tca + thc;
-        if (t0 < 0.0f) t0 = t1;
-        if (t0 > 0.0f && t0 < distance) { distance = t0; lightIndex = li + 1; }
-    }
+    GMUPT_LIGHT_SPHERES(p.scene.lights, p.cam.lightCount, o, d, distance, lightIndex)
     stu(p, F_IS_EMITTER, index, lightIndex);
     stf(p, F_HIT_DIST, index, distance);
 }

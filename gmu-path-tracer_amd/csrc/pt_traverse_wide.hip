@@ -316,8 +316,68 @@ __device__ __forceinline__ PairHit tri_pair_compute(const vec4f a0, const vec4f 
 #undef GMUPT_LO
 #undef GMUPT_HI
 
-template <bool STATS, int REPS>
-__global__ __launch_bounds__(kDefBlock) void k_cast_w(RenderParams p)
+// ---- where the rays come from and where the results go: a compile-time policy of k_cast_w.
+// StateIO is the path tracer's own ray cast (queues and path state of the renderer, extensionRayCast.hlsl / shadowRayCast.hlsl); QueryIO
+// serves gmupt_trace_rays: caller arrays of gmupt_ray in, gmupt_hit records and occluded flags out.  Everything else -- the walk, the
+// parking, the exact walk, the watchdog -- is the same code; the work counters and the statistics are whatever p.travCounters and p.stats
+// point to (the query launcher gives it buffers of its own).  The ray is read by path-state field (ray3 / rayf): the StateIO instantiations
+// then compile to the instruction stream of the kernel before the policy existed (tools/isa_compare.py).
+struct StateIO {
+    using Params = RenderParams;
+    __device__ static __forceinline__ void prologue(const Params& p) { shadow_counter_epilogue(p); }
+    __device__ static __forceinline__ uint32_t count(const Params& p, int phase) { return phase == 0 ? p.qc[QC_EXT_COUNT] : p.qc[QC_SHADOWRAY]; }  // extensionRayCast.hlsl:205, shadowRayCast.hlsl:151
+    __device__ static __forceinline__ const uint32_t* queue(const Params& p, int phase) { return p.queues + (size_t)(phase == 0 ? Q_EXT_RAY : Q_SHADOW_RAY) * p.P; }
+    __device__ static __forceinline__ uint32_t entry(const uint32_t* q, uint32_t i) { return q[i]; }
+    __device__ static __forceinline__ f3 ray3(const Params& p, uint32_t f, uint32_t i) { return ld3(p, f, i); }
+    __device__ static __forceinline__ float rayf(const Params& p, uint32_t f, uint32_t i) { return ldf(p, f, i); }
+    __device__ static __forceinline__ float closest_limit(const Params&, uint32_t) { return kFltMax; }          // an extension ray has no limit
+    __device__ static __forceinline__ void finish_closest(const Params& p, uint32_t index, f3 o, f3 d, float distance, float hu, float hv, int ref)
+    {
+        finish_extension_ray(p, index, o, d, distance, hu, hv, ref);                                            // extensionRayCast.hlsl:218-232
+    }
+    __device__ static __forceinline__ void finish_any(const Params& p, uint32_t index, uint32_t occluded) { stu(p, F_IN_SHADOW, index, occluded); }   // shadowRayCast.hlsl:167
+};
+
+struct QueryParams : RenderParams {
+    const gmupt_ray* rays[2];   // phase 0: closest-hit rays, phase 1: any-hit rays
+    uint32_t count[2];
+    gmupt_hit* hits;            // one per closest-hit ray
+    uint32_t* occluded;         // one per any-hit ray
+    uint32_t lightCount;        // light spheres tested after the triangles (clamped to GMUPT_MAX_LIGHTS)
+};
+
+struct QueryIO {
+    using Params = QueryParams;
+    __device__ static __forceinline__ void prologue(const Params&) {}                                            // the renderer's counters stay as they are
+    __device__ static __forceinline__ uint32_t count(const Params& p, int phase) { return p.count[phase]; }
+    __device__ static __forceinline__ const uint32_t* queue(const Params&, int) { return nullptr; }
+    __device__ static __forceinline__ uint32_t entry(const uint32_t*, uint32_t i) { return i; }                // identity queues, no holes
+    // the path-state fields of the two ray kinds on the caller's 32-byte records (f is a constant after inlining): origin, direction, and
+    // tmax as the limit of BOTH kinds (the light distance of an any-hit ray, the starting distance of a closest-hit ray)
+    __device__ static __forceinline__ f3 ray3(const Params& p, uint32_t f, uint32_t i)
+    {
+        const float4 a = reinterpret_cast<const float4*>(p.rays[(f == F_SH_OX || f == F_SH_DX) ? 1 : 0] + i)[(f == F_RAY_DX || f == F_SH_DX) ? 1 : 0];
+        return mk3(a.x, a.y, a.z);
+    }
+    __device__ static __forceinline__ float rayf(const Params& p, uint32_t, uint32_t i) { return p.rays[1][i].tmax; }   // F_LIGHT_DIST
+    __device__ static __forceinline__ float closest_limit(const Params& p, uint32_t i) { return p.rays[0][i].tmax; }
+    __device__ static __forceinline__ void finish_closest(const Params& p, uint32_t index, f3 o, f3 d, float distance, float hu, float hv, int ref)
+    {
+        const bool hit = ref >= 0;
+        const uint32_t material = hit ? p.scene.tris[ref].materialID : 0u;
+        GMUPT_LIGHT_SPHERES(p.scene.lights, p.lightCount, o, d, distance, light)                // extensionRayCast.hlsl:168-194
+        float4* h = reinterpret_cast<float4*>(p.hits + index);
+        // the triangle as its first reference with the same record (word 10 of Tri48): duplicated references of one triangle tie, and which
+        // of them a walk meets first depends on the lanes; the lowest index is the same answer every time
+        const int tri = hit ? (int)__builtin_bit_cast(uint32_t, p.trav.tris[ref].r2[2]) : -1;
+        h[0] = make_float4(distance, hit ? hu : 0.0f, hit ? hv : 0.0f, __builtin_bit_cast(float, tri));
+        h[1] = make_float4(__builtin_bit_cast(float, light), __builtin_bit_cast(float, material), 0.0f, 0.0f);
+    }
+    __device__ static __forceinline__ void finish_any(const Params& p, uint32_t index, uint32_t occluded) { p.occluded[index] = occluded; }
+};
+
+template <bool STATS, int REPS, class IO>
+__global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
 {
     constexpr int S = kWideStack;
     // one LDS object, the tree top first: a top node's LDS address is then its byte offset in the node table (cur * 128), and the plane
@@ -330,13 +390,13 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(RenderParams p)
         for (uint32_t k = threadIdx.x; k < p.trav.wideTopCount * 8u; k += kDefBlock) s_top[k] = src[k];
         __syncthreads();
     }
-    shadow_counter_epilogue(p);
+    IO::prologue(p);
     int* sl = s_stack + threadIdx.x;     // entry i of this lane: sl[i * kDefBlock]
     TravCount tcE = { 0, 0, 0 }, tcS = { 0, 0, 0 }; uint32_t raysE = 0, raysS = 0, wInE = 0, wTrE = 0, wInS = 0, wTrS = 0;
     const TravScene& ts = p.trav;
-    const uint32_t countExt = p.qc[QC_EXT_COUNT], countSh = p.qc[QC_SHADOWRAY];  // extensionRayCast.hlsl:205, shadowRayCast.hlsl:151
-    const uint32_t* qExt = p.queues + (size_t)Q_EXT_RAY * p.P;
-    const uint32_t* qSh = p.queues + (size_t)Q_SHADOW_RAY * p.P;
+    const uint32_t countExt = IO::count(p, 0), countSh = IO::count(p, 1);
+    const uint32_t* qExt = IO::queue(p, 0);
+    const uint32_t* qSh = IO::queue(p, 1);
     const __amdgpu_buffer_rsrc_t rNodes = make_rsrc(ts.wnodes, ts.wideCount * 128u);
     const __amdgpu_buffer_rsrc_t rTris = make_rsrc(ts.tris, (p.scene.numTris + 1u) * 48u);    // + the sentinel record (the exact walk; the source-triangle numbers)
     const __amdgpu_buffer_rsrc_t rPairs = make_rsrc(ts.pairs, ts.numPairs * 80u);
@@ -374,8 +434,8 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(RenderParams p)
          tT = kFltMax; refT = -1; redoT = false; } while (0)
     // the end of a decided ray in its lane
 #define GMUPT_WIDE_FINISH() \
-    do { if (kind == 0) finish_extension_ray(p, index, ray_o(ray), ray_d(ray), distance, hu, hv, hitRef >= 0 ? (int)ts.pairRef[hitRef] : -1);   /* extensionRayCast.hlsl:218-232; hitRef is a pair SLOT */ \
-         else stu(p, F_IN_SHADOW, index, hitRef >= 0 ? 1u : 0u);                                    /* shadowRayCast.hlsl:167 */ \
+    do { if (kind == 0) IO::finish_closest(p, index, ray_o(ray), ray_d(ray), distance, hu, hv, hitRef >= 0 ? (int)ts.pairRef[hitRef] : -1);   /* hitRef is a pair SLOT */ \
+         else IO::finish_any(p, index, hitRef >= 0 ? 1u : 0u); \
          haveRay = false; redo = false; } while (0)
 
     // Watchdog: a persistent kernel must end whatever happens (see k_cast_f)
@@ -468,8 +528,8 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(RenderParams p)
                 if (lane == 0u) atomicAdd(&p.stats->castRedoRays, (unsigned long long)nParked);
                 if (parked) {
                     const bool shadowRay = kind == 3;
-                    ray_set(ray, shadowRay ? ld3(p, F_SH_OX, index) : ld3(p, F_RAY_OX, index), shadowRay ? ld3(p, F_SH_DX, index) : ld3(p, F_RAY_DX, index));
-                    distance = shadowRay ? ldf(p, F_LIGHT_DIST, index) : kFltMax;
+                    ray_set(ray, shadowRay ? IO::ray3(p, F_SH_OX, index) : IO::ray3(p, F_RAY_OX, index), shadowRay ? IO::ray3(p, F_SH_DX, index) : IO::ray3(p, F_RAY_DX, index));
+                    distance = shadowRay ? IO::rayf(p, F_LIGHT_DIST, index) : IO::closest_limit(p, index);
                     const f3 o = ray_o(ray), invdir = ray_inv(ray), d = ray_d(ray);
                     hitRef = -1; hu = 0.0f; hv = 0.0f;
                     int* ovf = p.ovfStack + gtid;
@@ -507,8 +567,8 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(RenderParams p)
                     }
 #undef GMUPT_EXACT_PUSH
 #undef GMUPT_EXACT_POP
-                    if (shadowRay) stu(p, F_IN_SHADOW, index, hitRef >= 0 ? 1u : 0u);            // shadowRayCast.hlsl:167
-                    else finish_extension_ray(p, index, o, d, distance, hu, hv, hitRef);         // extensionRayCast.hlsl:218-232
+                    if (shadowRay) IO::finish_any(p, index, hitRef >= 0 ? 1u : 0u);
+                    else IO::finish_closest(p, index, o, d, distance, hu, hv, hitRef);
                     haveRay = false; kind = 0; redo = false; cur = kDone; pa = 0; bottom = 0; pb = S - 1; ti = -1;
                     tT = kFltMax; refT = -1; redoT = false; hitRef = -1;
                 }
@@ -534,8 +594,8 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(RenderParams p)
                         const uint32_t gb = sgm * segLen + base, ge = (base + p.raysPerWave < segLen ? gb + p.raysPerWave : (sgm + 1u) * segLen);
                         next = gb; end = ge; chunkBase = gb;
                         const uint32_t* q = phase == 0 ? qExt : qSh;
-                        qe0 = (gb + lane < ge) ? q[gb + lane] : kQueueHole;
-                        qe1 = (gb + 64u + lane < ge) ? q[gb + 64u + lane] : kQueueHole;
+                        qe0 = (gb + lane < ge) ? IO::entry(q, gb + lane) : kQueueHole;
+                        qe1 = (gb + 64u + lane < ge) ? IO::entry(q, gb + 64u + lane) : kQueueHole;
                     }
                 }
                 if (!got) { phase++; next = end = 0; }
@@ -555,8 +615,8 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(RenderParams p)
                     next = base; end = (base + req < count) ? base + req : count;
                     chunkBase = base;
                     const uint32_t* q = phase == 0 ? qExt : qSh;
-                    qe0 = (base + lane < end) ? q[base + lane] : kQueueHole;
-                    qe1 = (base + 64u + lane < end) ? q[base + 64u + lane] : kQueueHole;
+                    qe0 = (base + lane < end) ? IO::entry(q, base + lane) : kQueueHole;
+                    qe1 = (base + 64u + lane < end) ? IO::entry(q, base + 64u + lane) : kQueueHole;
                 }
                 else { phase++; next = end = 0; lastBase = 0; }
             }
@@ -570,8 +630,8 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(RenderParams p)
                 const bool newRay = take && ((phase != 0 && !GMUPT_WIDE_XCD_EXPERIMENT) || newIndex != kQueueHole); // holes only exist in the extension queue (and in the experiment's padded bins)
                 f3 newO = mk3(0, 0, 0), newD = mk3(0, 0, 1); float newDist = kFltMax;
                 if (newRay) {
-                    if (phase == 0) { newO = ld3(p, F_RAY_OX, newIndex); newD = ld3(p, F_RAY_DX, newIndex); }                 // :213-214
-                    else { newO = ld3(p, F_SH_OX, newIndex); newD = ld3(p, F_SH_DX, newIndex); newDist = ldf(p, F_LIGHT_DIST, newIndex); } // :162-164
+                    if (phase == 0) { newO = IO::ray3(p, F_RAY_OX, newIndex); newD = IO::ray3(p, F_RAY_DX, newIndex); newDist = IO::closest_limit(p, newIndex); }  // :213-214
+                    else { newO = IO::ray3(p, F_SH_OX, newIndex); newD = IO::ray3(p, F_SH_DX, newIndex); newDist = IO::rayf(p, F_LIGHT_DIST, newIndex); }         // :162-164
                 }
                 if (haveRay) GMUPT_WIDE_FINISH();   // (decided: a ray that needs the exact walk was parked at the top of the loop and its lane is not idle)
                 if (newRay) {
@@ -720,9 +780,26 @@ uint32_t launch_cast_wide(const RenderParams& p, bool stats, hipStream_t s)
     const uint64_t recordBytes = (uint64_t)p.trav.wideCount * 128ull + (uint64_t)p.trav.numPairs * 80ull;
     const bool eight = p.tuneWideSteps ? p.tuneWideSteps >= 8u : recordBytes > (256ull << 20);
     RenderParams q = p; q.wideQuarterTail = eight ? 1u : 0u;   // (measured with it: config 5 4.87-4.95 vs 4.95-4.99 ms, config 3 0.926-0.928 vs 0.920-0.923)
-    if (stats) { if (eight) hipLaunchKernelGGL((k_cast_w<true, GMUPT_WIDE_REPS + 2>), dim3(pb), dim3(kDefBlock), 0, s, q); else hipLaunchKernelGGL((k_cast_w<true, GMUPT_WIDE_REPS>), dim3(pb), dim3(kDefBlock), 0, s, q); }
-    else { if (eight) hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS + 2>), dim3(pb), dim3(kDefBlock), 0, s, q); else hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS>), dim3(pb), dim3(kDefBlock), 0, s, q); }
+    if (stats) { if (eight) hipLaunchKernelGGL((k_cast_w<true, GMUPT_WIDE_REPS + 2, StateIO>), dim3(pb), dim3(kDefBlock), 0, s, q); else hipLaunchKernelGGL((k_cast_w<true, GMUPT_WIDE_REPS, StateIO>), dim3(pb), dim3(kDefBlock), 0, s, q); }
+    else { if (eight) hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS + 2, StateIO>), dim3(pb), dim3(kDefBlock), 0, s, q); else hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS, StateIO>), dim3(pb), dim3(kDefBlock), 0, s, q); }
     return GMUPT_STAT_FUSED_CAST | GMUPT_STAT_CAST_WIDE;
+}
+
+// gmupt_trace_rays: the same walk over caller rays (QueryIO).  p is the renderer's parameter block with p.stats and p.travCounters
+// already pointing at the query's own zeroed buffers (gmupt_capi.hip checks that the scene has a wide collapse within the 2 GiB limits).
+// The rest of the launch is launch_cast_wide's: grid, overflow stacks, steps per iteration, tail rule.
+void launch_trace_wide(const RenderParams& p, const gmupt_ray* closest, uint32_t nClosest, gmupt_hit* hits, const gmupt_ray* any, uint32_t nAny,
+                       uint32_t* occluded, uint32_t lightCount, hipStream_t s)
+{
+    QueryParams q;
+    static_cast<RenderParams&>(q) = p;
+    q.rays[0] = closest; q.rays[1] = any; q.count[0] = nClosest; q.count[1] = nAny;
+    q.hits = hits; q.occluded = occluded; q.lightCount = lightCount;
+    const uint64_t recordBytes = (uint64_t)p.trav.wideCount * 128ull + (uint64_t)p.trav.numPairs * 80ull;
+    const bool eight = p.tuneWideSteps ? p.tuneWideSteps >= 8u : recordBytes > (256ull << 20);
+    q.wideQuarterTail = eight ? 1u : 0u;
+    if (eight) hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS + 2, QueryIO>), dim3(p.travGridBlocks), dim3(kDefBlock), 0, s, q);
+    else hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS, QueryIO>), dim3(p.travGridBlocks), dim3(kDefBlock), 0, s, q);
 }
 
 } // namespace gmupt

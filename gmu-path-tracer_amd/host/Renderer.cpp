@@ -62,9 +62,35 @@ void Renderer::update(float dt)
 
 	mScene.update(dt);
 	check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); // UpdateSubresource(mCameraBuffer), Renderer.cpp:161
+	mCameraSet = true;
 }
 
 void Renderer::draw()
+{
+	bindScene();
+	check(gmupt_iterate(mRenderer.get())); // logic, newPath, materialUE4, materialGlass, extensionRay, shadowRay (Renderer.cpp:195-211)
+	mIterations++;
+}
+
+gmupt_trace_info Renderer::traceRays(const gmupt_ray* closest, uint32_t nClosest, gmupt_hit* hits, const gmupt_ray* any, uint32_t nAny, uint32_t* occluded,
+                                     uint32_t lightCount)
+{
+	bindScene();
+	gmupt_trace_info info{};
+	check(gmupt_trace_rays(mRenderer.get(), closest, nClosest, hits, any, nAny, occluded, lightCount, &info));
+	return info;
+}
+
+Renderer::Pick Renderer::pick(float x, float y)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	Pick p{};
+	check(gmupt_pick(mRenderer.get(), x, y, mScene.mCamera.getBuffer()->lightCount, &p.ray, &p.hit));
+	return p;
+}
+
+void Renderer::bindScene()
 {
 	if (!mSceneBound)
 	{
@@ -74,8 +100,6 @@ void Renderer::draw()
 		check(gmupt_renderer_bind_textures(mRenderer.get(), mScene.mDiffuse.get(), mScene.mMetallicRoughness.get(), mScene.mNormal.get()));
 		mSceneBound = true;
 	}
-	check(gmupt_iterate(mRenderer.get())); // logic, newPath, materialUE4, materialGlass, extensionRay, shadowRay (Renderer.cpp:195-211)
-	mIterations++;
 }
 
 std::vector<float> Renderer::readFramebuffer()

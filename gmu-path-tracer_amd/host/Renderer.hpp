@@ -38,11 +38,20 @@ public:
 	Scene& scene() { return mScene; }
 	unsigned long long iterations() const { return mIterations; }
 
+	// ray queries on the bound scene (gmupt_trace_rays): rays and outputs are caller-owned device memory; synchronous, the frame is untouched
+	gmupt_trace_info traceRays(const gmupt_ray* closest, uint32_t nClosest, gmupt_hit* hits, const gmupt_ray* any, uint32_t nAny, uint32_t* occluded,
+	                           uint32_t lightCount);
+	// picking for the GUI's editors (Source/GUI.cpp:110-221): the un-jittered primary ray through whole-frame pixel (x, y) of the current camera
+	// and what it hits first, light spheres up to the camera's lightCount included
+	struct Pick { gmupt_ray ray; gmupt_hit hit; };
+	Pick pick(float x, float y);
+
 private:
 	void createDevice(int hipDevice);
 	void createBuffers(Resolution res);
 	void captureScreen();
 	void resize(const Resolution& resolution);
+	void bindScene();
 
 	struct DeviceDeleter { void operator()(gmupt_device* d) const { gmupt_device_destroy(d); } };
 	struct RendererDeleter { void operator()(gmupt_renderer* r) const { gmupt_renderer_destroy(r); } };
@@ -54,7 +63,7 @@ private:
 	Resolution mResolution;
 	RowBand mBand;
 	unsigned mPoolPaths, mLivePaths;
-	bool mSceneBound = false;
+	bool mSceneBound = false, mCameraSet = false;
 	bool mHasResize = false, mCaptureRequested = false;
 	Resolution mPendingResize{};
 	std::string mLastCapture;

@@ -7,6 +7,8 @@
 //                                                         device D (default R) and the bands are gathered on rank 0 over RCCL (TileGather.hpp);
 //                                                         rank 0 writes --dump / --pfm of the whole frame; --no-gather: every rank dumps its band
 //                [--print-bands H N]                      the row split, as JSON
+//                [--pick X,Y]                             after the frames: what lies under whole-frame pixel (X, Y), as one JSON line
+//                [--help]                                 this list
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +53,7 @@ int main(int argc, char** argv)
 	bool capture = false, buildOnly = false, noGather = false;
 	unsigned ranks = 1, rank = 0; int device = -1;
 	std::string paramsOnly, rendezvous;
+	bool doPick = false; float pickX = 0.f, pickY = 0.f;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
 		auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -72,6 +75,14 @@ int main(int argc, char** argv)
 		else if (a == "--rendezvous") rendezvous = next();
 		else if (a == "--device") device = std::atoi(next());
 		else if (a == "--no-gather") noGather = true;
+		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
+		else if (a == "--help" || a == "-h") {
+			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
+			            "             [--build-only] [--dump-mesh out.gmesh] [--models-root DIR] [--list-scenes] [--params FILE]\n"
+			            "             [--ranks N --rank R --rendezvous FILE [--device D] [--no-gather]] [--print-bands H N]\n"
+			            "             [--pick X,Y]   after the frames: triangle / material / light sphere under whole-frame pixel (X, Y), one JSON line\n");
+			return 0;
+		}
 		else if (a == "--print-bands") { // H N: the row bands of an H-row frame over N ranks, as JSON (the CPU tests compare them with tiles.py)
 			const unsigned H = std::strtoul(next(), nullptr, 10), N = std::strtoul(next(), nullptr, 10);
 			std::printf("[");
@@ -164,6 +175,16 @@ int main(int argc, char** argv)
 		Renderer renderer(nullptr, { w, h }, scene, 0, pool, live);
 		for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
 		if (capture) { renderer.requestCapture(); renderer.update(0.f); std::printf("capture %s\n", renderer.lastCapturePath().c_str()); }
+		if (doPick) {
+			const Renderer::Pick pk = renderer.pick(pickX, pickY);
+			const bool found = pk.hit.triangle >= 0 || pk.hit.light > 0;
+			float pt[3] = { 0.f, 0.f, 0.f };
+			for (int k = 0; k < 3; k++) pt[k] = pk.ray.origin[k] + pk.ray.direction[k] * pk.hit.t;
+			std::printf("{\"pick\": [%.9g, %.9g], \"triangle\": %d, \"material\": %u, \"light\": %u, \"t\": %.9g, \"u\": %.9g, \"v\": %.9g, \"origin\": [%.9g, %.9g, %.9g], \"direction\": [%.9g, %.9g, %.9g]",
+			            pickX, pickY, pk.hit.triangle, pk.hit.material, pk.hit.light, pk.hit.t, pk.hit.u, pk.hit.v, pk.ray.origin[0], pk.ray.origin[1], pk.ray.origin[2],
+			            pk.ray.direction[0], pk.ray.direction[1], pk.ray.direction[2]);
+			if (found) std::printf(", \"point\": [%.9g, %.9g, %.9g]}\n", pt[0], pt[1], pt[2]); else std::printf(", \"point\": null}\n");
+		}
 		if (!pfm.empty()) renderer.writePfm(pfm);
 		if (!dump.empty()) {
 			const auto fb = renderer.readFramebuffer();

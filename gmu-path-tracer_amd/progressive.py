@@ -45,6 +45,17 @@ class ProgressiveSession:
         self.renderer.resize(width, rows if rows is not None else height)
         self.camera.update_resolution(width, height)
 
+    def pick(self, px, py):
+        """What lies under whole-frame pixel (px, py) for the GUI's light / material editor: the un-jittered primary ray of the current
+        camera through the renderer's closest-hit query, light spheres up to the session's lightCount included.  Returns a dict:
+        triangle (reference index, -1: none), material (of that triangle), light (0, or 1 + the light sphere in front of every
+        triangle), t and the world-space point origin + direction * t (None when nothing was hit)."""
+        ray, hit = self.renderer.pick(px, py, int(self.camera.buffer.lightCount))
+        o = np.array(ray.origin[:], np.float32); d = np.array(ray.direction[:], np.float32)
+        found = hit.triangle >= 0 or hit.light > 0
+        return {"triangle": int(hit.triangle), "material": int(hit.material), "light": int(hit.light), "t": float(hit.t),
+                "point": (o + d * np.float32(hit.t)) if found else None}
+
     # ---- frames
     def frame(self, dt=0.0):
         self.camera.update(dt)                       # Renderer::update: camera vectors, iterationCounter, randomSeed

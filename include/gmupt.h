@@ -212,6 +212,51 @@ int gmupt_enable_timing(gmupt_renderer* r, int mode); /* hipEvent timing on the 
 typedef struct gmupt_camera gmupt_camera;
 int gmupt_render_budget(gmupt_renderer* r, gmupt_camera* camera, uint32_t max_iterations, uint32_t* iters);
 
+/* ---- ray queries: the wide ray cast (k_cast_w) on rays the caller supplies ----
+ * One launch serves a batch of closest-hit rays and a batch of any-hit rays (either may be empty), with the traversal, the tie handling
+ * and the arithmetic of the renderer's own ray cast: the answers are bit for bit what extensionRayCast.hlsl / shadowRayCast.hlsl give.
+ *
+ * Closest hit (extensionRayCast.hlsl:64-74,168-194): `distance` starts at tmax; a triangle counts if t >= 0 && t < distance (strict: among
+ *   hits with bitwise equal t the reference's binary near-first order decides).  t is in units of |direction| (it need not be normalised).
+ *   After the triangles the first light_count light spheres are tested; a sphere with 0 < t < distance sets `light` and `t`, while
+ *   triangle / u / v / material still describe the nearest triangle.  On a miss of everything: t = tmax, triangle = -1, u = v = 0,
+ *   light = material = 0.  With tmax = FLT_MAX the record is the reference's (hitDistance, baryCoord.yz, triangle, isEmitter).
+ * Any hit (shadowRayCast.hlsl:41-45,89): occluded = 1 if some triangle has 1e-8 < t < 1e8 (EPSILON = 1e-8, structs.h:10) and
+ *   |direction * t| < tmax -- tmax plays the reference's lightDistance; the light spheres are not tested.
+ * Calling: rays and outputs are caller-owned DEVICE memory (hipMalloc, torch tensors), 16-byte aligned (occluded: 4); at most 2^26 rays per
+ *   batch.  The call is enqueued on the renderer's stream behind any pending gmupt_iterate work, then synchronises and reads back its own
+ *   fault flags: GMUPT_ERR_CAST_FAULT on a traversal stack overflow or an aborted wave (the outputs are then invalid).  The renderer's path
+ *   state, queues, counters, framebuffer and gmupt_get_stats are not touched (the query has its own work counters and statistics).
+ * Errors: GMUPT_ERR_NOT_BOUND without a scene; GMUPT_ERR_INVALID_ARGUMENT for a NULL or misaligned pointer of a non-empty batch or more
+ *   than 2^26 rays; GMUPT_ERR_UNSUPPORTED when the bound scene has no usable wide collapse (GMUPT_TRAVERSAL other than wide, the opt-in
+ *   GMUPT_EXTEND_PRUNE / GMUPT_SHADOW_PRUNE, a tree whose child boxes stick out of their parents, or tables beyond the 2 GiB limits of
+ *   32-bit buffer offsets). */
+typedef struct { float origin[3]; float tmax; float direction[3]; uint32_t pad; } gmupt_ray;   /* 32 bytes; pad is ignored */
+typedef struct {
+    float t, u, v;
+    int32_t triangle;   /* reference index into the GMUPT_BUFFER_TRIANGLES array, -1: no triangle below tmax.  Of the references with the same
+                           record (a triangle that spatial splits put into several leaves) always the lowest index: they tie, and the order in
+                           which the parallel walk meets them would otherwise decide */
+    uint32_t light;     /* 0, or 1 + index of a light sphere nearer than every triangle (the reference's isEmitter) */
+    uint32_t material;  /* materialID of that triangle record (0 without a triangle) */
+    uint32_t pad[2];
+} gmupt_hit;            /* 32 bytes */
+typedef struct {
+    uint32_t flags;     /* GMUPT_STAT_* of the launch: GMUPT_STAT_FUSED_CAST | GMUPT_STAT_CAST_WIDE, plus the fault bits */
+    uint32_t pad_;
+    uint64_t redo_rays; /* rays walked again in the reference's binary order (exact ties in t, or a full stack) */
+    double ms;          /* device time of the launch (hipEvents on the renderer's stream) */
+} gmupt_trace_info;     /* 24 bytes */
+int gmupt_trace_rays(gmupt_renderer* r, const gmupt_ray* closest, uint32_t n_closest, gmupt_hit* hits,
+                     const gmupt_ray* any, uint32_t n_any, uint32_t* occluded, uint32_t light_count, gmupt_trace_info* info /* may be NULL */);
+/* host only: the un-jittered primary ray of newPath.hlsl:36-39 (jitter 0) through whole-frame pixel coordinates (px, py) of the camera --
+ * origin = position, direction = normalize(upperLeftCorner + horizontal * (px * pixelSize.x) - vertical * (py * pixelSize.y)),
+ * tmax = FLT_MAX.  Tile renderers share the whole frame's camera, so the same coordinates hold in tile mode. */
+int gmupt_camera_pick_ray(const gmupt_camera_buffer* cam, float px, float py, gmupt_ray* out);
+/* picking: gmupt_camera_pick_ray on the renderer's current camera, then a one-ray closest-hit gmupt_trace_rays (synchronous).
+ * GMUPT_ERR_NOT_BOUND also when no camera was set.  ray_out may be NULL. */
+int gmupt_pick(gmupt_renderer* r, float px, float py, uint32_t light_count, gmupt_ray* ray_out, gmupt_hit* hit_out);
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);
