@@ -93,10 +93,21 @@ class TraceInfo(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("pad_", C.c_uint32), ("redo_rays", C.c_uint64), ("ms", C.c_double)]
 
 
-assert C.sizeof(Ray) == 32 and C.sizeof(Hit) == 32 and C.sizeof(TraceInfo) == 24
+class Aov(C.Structure):
+    """gmupt_aov: 64 bytes per pixel (albedo, depth, normal, roughness, position, metallic, triangle, material, light, coverage)."""
+    _fields_ = [("albedo", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("roughness", C.c_float),
+                ("position", C.c_float * 3), ("metallic", C.c_float), ("triangle", C.c_int32), ("material", C.c_uint32),
+                ("light", C.c_uint32), ("coverage", C.c_uint32)]
+
+
+AOV_MAX_SAMPLES = 8
+AOV_CHUNK_RAYS = 1 << 21   # rays per chunk of gmupt_render_aovs
+assert C.sizeof(Ray) == 32 and C.sizeof(Hit) == 32 and C.sizeof(TraceInfo) == 24 and C.sizeof(Aov) == 64
 ray_dtype = np.dtype([("origin", "<f4", 3), ("tmax", "<f4"), ("direction", "<f4", 3), ("pad", "<u4")])
 hit_dtype = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("triangle", "<i4"), ("light", "<u4"), ("material", "<u4"), ("pad", "<u4", 2)])
-assert ray_dtype.itemsize == 32 and hit_dtype.itemsize == 32
+aov_dtype = np.dtype([("albedo", "<f4", 3), ("depth", "<f4"), ("normal", "<f4", 3), ("roughness", "<f4"), ("position", "<f4", 3),
+                      ("metallic", "<f4"), ("triangle", "<i4"), ("material", "<u4"), ("light", "<u4"), ("coverage", "<u4")])
+assert ray_dtype.itemsize == 32 and hit_dtype.itemsize == 32 and aov_dtype.itemsize == 64
 
 
 class GmuptError(RuntimeError):
@@ -139,6 +150,8 @@ SYMBOLS = {
     "gmupt_trace_rays": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(TraceInfo)]),
     "gmupt_camera_pick_ray": (C.c_int, [C.POINTER(CameraBuffer), C.c_float, C.c_float, C.POINTER(Ray)]),
     "gmupt_pick": (C.c_int, [_P, C.c_float, C.c_float, C.c_uint32, C.POINTER(Ray), C.POINTER(Hit)]),
+    "gmupt_render_aovs": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(TraceInfo)]),
+    "gmupt_aov_ray": (C.c_int, [C.POINTER(CameraBuffer), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Ray)]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -484,6 +497,22 @@ class Renderer:
         _check(lib().gmupt_pick(self.h, float(px), float(py), int(light_count), C.byref(ray), C.byref(hit)))
         return ray, hit
 
+    # AOV buffers (gmupt_render_aovs)
+    def aovs(self, samples=1, info=None):
+        """The per-pixel G-buffer of the current camera's rays over this renderer's framebuffer rectangle (the tile in tile mode):
+        a (H, W, 16) float32 torch tensor on this renderer's GPU, one 64-byte gmupt_aov record per pixel (include/gmupt.h states the
+        semantics; aov_fields() splits it -- words 12-15 are integers, compare them as bits).  samples: 1..8 (s*s stratified rays per pixel
+        for the filtered albedo / normal planes when > 1).  torch's current stream is synchronised first; the call itself synchronises the
+        renderer's stream.  info: optional TraceInfo to fill."""
+        import torch
+        dev = torch.device("cuda", getattr(self.dev, "index", 0))
+        out = torch.empty((self.height, self.width, 16), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        ti = info if info is not None else TraceInfo()
+        _check(lib().gmupt_render_aovs(self.h, int(samples), C.c_void_p(out.data_ptr()), out.numel() * 4, C.byref(ti)))
+        self.last_aovs = ti
+        return out
+
     # reference-layout debug access
     def read_path_state(self):
         out = np.empty(self.pool * STATE_BYTES, dtype=np.uint8)
@@ -530,6 +559,33 @@ def hit_fields(hits):
     h = hits.cpu().numpy() if hasattr(hits, "cpu") else np.asarray(hits)
     rec = np.ascontiguousarray(h, dtype=np.float32).reshape(-1, 8).view(hit_dtype)[:, 0]
     return {k: rec[k].copy() for k in ("t", "u", "v", "triangle", "light", "material")}
+
+
+def aov_ray(cam_buffer, x, y, samples, k):
+    """gmupt_aov_ray (host only): ray k of whole-frame pixel (x, y) at `samples` -- k = 0 the centre ray, k = 1 + b*s + a the stratified ones."""
+    ray = Ray()
+    _check(lib().gmupt_aov_ray(C.byref(cam_buffer), int(x), int(y), int(samples), int(k), C.byref(ray)))
+    return ray
+
+
+def aov_rays(cam_buffer, xs, ys, samples):
+    """All AOV rays of the pixels (xs[i], ys[i]) as an (N, R, 8) float32 array (gmupt_aov_ray per ray; R = 1 or samples^2 + 1)."""
+    R = 1 if samples == 1 else samples * samples + 1
+    out = np.empty((len(xs), R, 8), np.float32)
+    for i, (x, y) in enumerate(zip(xs, ys)):
+        for k in range(R):
+            out[i, k] = np.frombuffer(bytes(aov_ray(cam_buffer, x, y, samples, k)), np.float32)
+    return out
+
+
+def aov_fields(aovs):
+    """Splits (..., 16) gmupt_aov records (torch or numpy) into a dict of numpy arrays of shape (...): albedo, normal, position (..., 3),
+    depth, roughness, metallic (float32), triangle (int32), material, light, coverage (uint32)."""
+    a = aovs.cpu().numpy() if hasattr(aovs, "cpu") else np.asarray(aovs)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    rec = a.reshape(-1, 16).view(aov_dtype)[:, 0]
+    shape = a.shape[:-1]
+    return {k: rec[k].reshape(shape + rec[k].shape[1:]).copy() for k in aov_dtype.names}
 
 
 def sbvh_build(verts, indices, vertex_material=None, params=None):

@@ -2,6 +2,7 @@
 // Host code only; the kernels live in pt_kernels.hip.
 #include "pt_device.hpp"
 #include "detmath.hpp"
+#include "pt_shading.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
 #include "../host/TextureLoader.hpp"
@@ -50,6 +51,10 @@ uint32_t traversal_top_capacity(uint32_t maxDepth);
 uint32_t traversal_wide_top_capacity();
 void launch_trace_wide(const RenderParams& p, const gmupt_ray* closest, uint32_t nClosest, gmupt_hit* hits, const gmupt_ray* any, uint32_t nAny,
                        uint32_t* occluded, uint32_t lightCount, hipStream_t s);
+void launch_aov_raygen(const gmupt_camera_buffer& cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t rows, uint32_t samples, uint32_t R,
+                       gmupt_ray* rays, hipStream_t s);
+void launch_aov_resolve(const RenderParams& p, uint32_t npix, uint32_t samples, uint32_t R, const gmupt_ray* rays, const gmupt_hit* hits,
+                        gmupt_aov* out, hipStream_t s);
 }
 using namespace gmupt;
 
@@ -222,6 +227,8 @@ struct gmupt_renderer {
     // ray queries (gmupt_trace_rays): work counters + statistics of their own, allocated on first use; one ray + one hit for gmupt_pick
     uint32_t* queryCounters = nullptr; DevStats* queryStats = nullptr; void* pickBuf = nullptr;
     hipEvent_t queryEv[2] = { nullptr, nullptr };
+    // AOV buffers (gmupt_render_aovs): rays and hits of one chunk (GMUPT_AOV_CHUNK_RAYS each, 128 MiB), allocated on first use
+    gmupt_ray* aovRays = nullptr; gmupt_hit* aovHits = nullptr;
 };
 
 static int dev_alloc(gmupt_renderer* r, void** ptr, size_t bytes, int fill)
@@ -924,6 +931,31 @@ static_assert(sizeof(gmupt_ray) == 32 && offsetof(gmupt_ray, tmax) == 12 && offs
 static_assert(sizeof(gmupt_hit) == 32 && offsetof(gmupt_hit, triangle) == 12 && offsetof(gmupt_hit, light) == 16 && offsetof(gmupt_hit, material) == 20, "gmupt_hit layout");
 static_assert(sizeof(gmupt_trace_info) == 24 && offsetof(gmupt_trace_info, redo_rays) == 8 && offsetof(gmupt_trace_info, ms) == 16, "gmupt_trace_info layout");
 
+// the wide collapse and the limits of launch_cast_wide's 32-bit buffer offsets, here including the TriPair table (gmupt_trace_rays, gmupt_render_aovs)
+static int query_supported(gmupt_renderer* r, const char* fn)
+{
+    const RenderParams& p = r->p;
+    if (!p.trav.wnodes || p.extendPrune || p.shadowPrune)
+        return fail(GMUPT_ERR_UNSUPPORTED, "%s: the bound scene has no wide collapse (it needs GMUPT_TRAVERSAL=wide, no GMUPT_EXTEND_PRUNE / GMUPT_SHADOW_PRUNE, "
+                    "and child boxes inside their parents)", fn);
+    if ((uint64_t)p.trav.wideCount * 128ull >= (1ull << 31) || ((uint64_t)p.scene.numTris + 1ull) * 48ull >= (1ull << 31) || (uint64_t)p.trav.numPairs * 80ull >= (1ull << 31))
+        return fail(GMUPT_ERR_UNSUPPORTED, "%s: the wide tables of the bound scene exceed 2 GiB (%u nodes, %u references, %u pairs)", fn, p.trav.wideCount, p.scene.numTris, p.trav.numPairs);
+    return GMUPT_OK;
+}
+
+// the query's own work counters, statistics and events, on first use
+static int query_buffers(gmupt_renderer* r)
+{
+    HIP_TRY(hipSetDevice(r->dev->id));
+    if (!r->queryStats) {
+        int rc = dev_alloc(r, (void**)&r->queryCounters, 128, 0);
+        if (rc == GMUPT_OK) rc = dev_alloc(r, (void**)&r->queryStats, sizeof(DevStats), 0);
+        if (rc != GMUPT_OK) { r->queryStats = nullptr; return rc; }
+        for (hipEvent_t& e : r->queryEv) HIP_TRY(hipEventCreate(&e));
+    }
+    return GMUPT_OK;
+}
+
 extern "C" int gmupt_trace_rays(gmupt_renderer* r, const gmupt_ray* closest, uint32_t n_closest, gmupt_hit* hits,
                                 const gmupt_ray* any, uint32_t n_any, uint32_t* occluded, uint32_t light_count, gmupt_trace_info* info)
 {
@@ -936,20 +968,10 @@ extern "C" int gmupt_trace_rays(gmupt_renderer* r, const gmupt_ray* closest, uin
     if (n_any && (!any || !occluded)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_trace_rays: null any-hit rays or occluded flags");
     if ((n_closest && (((uintptr_t)closest | (uintptr_t)hits) & 15u)) || (n_any && (((uintptr_t)any & 15u) || ((uintptr_t)occluded & 3u))))
         return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_trace_rays: misaligned pointer (rays and hits need 16 bytes, occluded flags 4)");
-    // the wide collapse and the limits of launch_cast_wide's 32-bit buffer offsets, here including the TriPair table
     const RenderParams& p = r->p;
-    if (!p.trav.wnodes || p.extendPrune || p.shadowPrune)
-        return fail(GMUPT_ERR_UNSUPPORTED, "gmupt_trace_rays: the bound scene has no wide collapse (it needs GMUPT_TRAVERSAL=wide, no GMUPT_EXTEND_PRUNE / GMUPT_SHADOW_PRUNE, "
-                    "and child boxes inside their parents)");
-    if ((uint64_t)p.trav.wideCount * 128ull >= (1ull << 31) || ((uint64_t)p.scene.numTris + 1ull) * 48ull >= (1ull << 31) || (uint64_t)p.trav.numPairs * 80ull >= (1ull << 31))
-        return fail(GMUPT_ERR_UNSUPPORTED, "gmupt_trace_rays: the wide tables of the bound scene exceed 2 GiB (%u nodes, %u references, %u pairs)", p.trav.wideCount, p.scene.numTris, p.trav.numPairs);
-    HIP_TRY(hipSetDevice(r->dev->id));
-    if (!r->queryStats) {
-        int rc = dev_alloc(r, (void**)&r->queryCounters, 128, 0);
-        if (rc == GMUPT_OK) rc = dev_alloc(r, (void**)&r->queryStats, sizeof(DevStats), 0);
-        if (rc != GMUPT_OK) { r->queryStats = nullptr; return rc; }
-        for (hipEvent_t& e : r->queryEv) HIP_TRY(hipEventCreate(&e));
-    }
+    int rc = query_supported(r, "gmupt_trace_rays");
+    if (rc == GMUPT_OK) rc = query_buffers(r);
+    if (rc != GMUPT_OK) return rc;
     const uint32_t launchFlags = GMUPT_STAT_FUSED_CAST | GMUPT_STAT_CAST_WIDE;
     if (n_closest == 0 && n_any == 0) { HIP_TRY(hipStreamSynchronize(r->stream)); if (info) info->flags = launchFlags; return GMUPT_OK; }
     // behind whatever the renderer has queued; the renderer's counters and statistics are left alone
@@ -977,11 +999,7 @@ extern "C" int gmupt_camera_pick_ray(const gmupt_camera_buffer* cam, float px, f
 {
     if (!cam || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_camera_pick_ray: null argument");
     // newPath.hlsl:36-39 with the jitter at 0: (x + 0) * pixelSize is x * pixelSize for every float x
-    const float u = px * cam->pixelSize[0], v = py * cam->pixelSize[1];
-    const f3 ulc = mk3(cam->upperLeftCorner[0], cam->upperLeftCorner[1], cam->upperLeftCorner[2]);
-    const f3 hor = mk3(cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]);
-    const f3 ver = mk3(cam->vertical[0], cam->vertical[1], cam->vertical[2]);
-    const f3 dir = normalize3((ulc + hor * u) - ver * v);
+    const f3 dir = camera_ray_direction(*cam, px, py);
     std::memset(out, 0, sizeof(*out));
     for (int k = 0; k < 3; k++) out->origin[k] = cam->position[k];
     out->direction[0] = dir.x; out->direction[1] = dir.y; out->direction[2] = dir.z;
@@ -1007,6 +1025,73 @@ extern "C" int gmupt_pick(gmupt_renderer* r, float px, float py, uint32_t light_
     HIP_TRY(hipMemcpyAsync(hit_out, dHit, sizeof(*hit_out), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
     if (ray_out) *ray_out = ray;
+    return GMUPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ AOV buffers
+static_assert(sizeof(gmupt_aov) == 64 && offsetof(gmupt_aov, depth) == 12 && offsetof(gmupt_aov, normal) == 16 && offsetof(gmupt_aov, roughness) == 28 &&
+              offsetof(gmupt_aov, position) == 32 && offsetof(gmupt_aov, metallic) == 44 && offsetof(gmupt_aov, triangle) == 48 &&
+              offsetof(gmupt_aov, material) == 52 && offsetof(gmupt_aov, light) == 56 && offsetof(gmupt_aov, coverage) == 60, "gmupt_aov layout");
+
+extern "C" int gmupt_aov_ray(const gmupt_camera_buffer* cam, uint32_t x, uint32_t y, uint32_t samples, uint32_t k, gmupt_ray* out)
+{
+    if (!cam || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_aov_ray: null argument");
+    if (samples < 1 || samples > GMUPT_AOV_MAX_SAMPLES) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_aov_ray: samples = %u (1..%d)", samples, GMUPT_AOV_MAX_SAMPLES);
+    const uint32_t R = samples == 1 ? 1u : samples * samples + 1u;
+    if (k >= R) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_aov_ray: ray %u of %u", k, R);
+    float px, py;
+    aov_ray_coords(x, y, samples, k, px, py);
+    return gmupt_camera_pick_ray(cam, px, py, out);
+}
+
+extern "C" int gmupt_render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info)
+{
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: null renderer");
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_aovs: no scene bound");
+    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_aovs: no camera set");
+    if (!out || ((uintptr_t)out & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: null or misaligned output (16 bytes)");
+    if (samples < 1 || samples > GMUPT_AOV_MAX_SAMPLES) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: samples = %u (1..%d)", samples, GMUPT_AOV_MAX_SAMPLES);
+    const uint32_t W = r->p.fbW, H = r->p.fbH;
+    if (bytes < (size_t)W * H * sizeof(gmupt_aov)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: %zu bytes for %ux%u records of 64 bytes", bytes, W, H);
+    const uint32_t R = samples == 1 ? 1u : samples * samples + 1u;
+    if ((uint64_t)W * R > GMUPT_AOV_CHUNK_RAYS) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: one row of %u pixels is %u rays at samples = %u (at most 2^21)", W, W * R, samples);
+    int rc = query_supported(r, "gmupt_render_aovs");
+    if (rc == GMUPT_OK) rc = query_buffers(r);
+    if (rc != GMUPT_OK) return rc;
+    if (!r->aovRays) {
+        rc = dev_alloc(r, (void**)&r->aovRays, (size_t)GMUPT_AOV_CHUNK_RAYS * sizeof(gmupt_ray), 0);
+        if (rc == GMUPT_OK) rc = dev_alloc(r, (void**)&r->aovHits, (size_t)GMUPT_AOV_CHUNK_RAYS * sizeof(gmupt_hit), 0);
+        if (rc != GMUPT_OK) { r->aovRays = nullptr; r->aovHits = nullptr; return rc; }
+    }
+    const RenderParams& p = r->p;
+    const uint32_t x0 = p.tileEnabled ? p.tileX0 : 0u, y0 = p.tileEnabled ? p.tileY0 : 0u;
+    const uint32_t rowsPerChunk = GMUPT_AOV_CHUNK_RAYS / (W * R);
+    // behind whatever the renderer has queued; the renderer's counters and statistics are left alone (the query's are used)
+    HIP_TRY(hipMemsetAsync(r->queryStats, 0, sizeof(DevStats), r->stream));
+    RenderParams q = p;
+    q.travCounters = r->queryCounters; q.stats = r->queryStats;
+    HIP_TRY(hipEventRecord(r->queryEv[0], r->stream));
+    for (uint32_t row = 0; row < H; row += rowsPerChunk) {
+        const uint32_t rows = std::min(rowsPerChunk, H - row), n = rows * W * R;
+        launch_aov_raygen(p.cam, x0, y0 + row, W, rows, samples, R, r->aovRays, r->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(r->queryCounters, 0, 128, r->stream));
+        launch_trace_wide(q, r->aovRays, n, r->aovHits, nullptr, 0, nullptr, p.cam.lightCount, r->stream);
+        HIP_TRY(hipGetLastError());
+        launch_aov_resolve(p, rows * W, samples, R, r->aovRays, r->aovHits, out + (size_t)row * W, r->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(r->queryEv[1], r->stream));
+    DevStats ds;
+    HIP_TRY(hipMemcpyAsync(&ds, r->queryStats, sizeof(ds), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, r->queryEv[0], r->queryEv[1]));
+    const uint32_t flags = GMUPT_STAT_FUSED_CAST | GMUPT_STAT_CAST_WIDE | ((ds.stackOverflow & 1u) ? GMUPT_STAT_STACK_OVERFLOW : 0u) | ((ds.stackOverflow & 2u) ? GMUPT_STAT_CAST_ABORTED : 0u);
+    if (info) { info->flags = flags; info->redo_rays = ds.castRedoRays; info->ms = ms; }
+    if (ds.stackOverflow & 2u) return fail(GMUPT_ERR_CAST_FAULT, "gmupt_render_aovs: a wave of the ray cast left its loop at the iteration limit (GMUPT_STAT_CAST_ABORTED): the records are invalid");
+    if (ds.stackOverflow & 1u) return fail(GMUPT_ERR_CAST_FAULT, "gmupt_render_aovs: a traversal stack overflowed (GMUPT_STAT_STACK_OVERFLOW): the records are invalid");
     return GMUPT_OK;
 }
 

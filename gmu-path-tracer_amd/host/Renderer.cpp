@@ -1,6 +1,7 @@
 #include <cstdio>
 #include "Renderer.hpp"
 #include "png_writer.hpp"
+#include <hip/hip_runtime_api.h>
 #include <cstdlib>
 #include <filesystem>
 #include <stdexcept>
@@ -88,6 +89,30 @@ Renderer::Pick Renderer::pick(float x, float y)
 	Pick p{};
 	check(gmupt_pick(mRenderer.get(), x, y, mScene.mCamera.getBuffer()->lightCount, &p.ray, &p.hit));
 	return p;
+}
+
+gmupt_trace_info Renderer::renderAovs(gmupt_aov* deviceOut, size_t bytes, unsigned samples)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	gmupt_trace_info info{};
+	check(gmupt_render_aovs(mRenderer.get(), samples, deviceOut, bytes, &info));
+	return info;
+}
+
+std::vector<gmupt_aov> Renderer::renderAovs(unsigned samples)
+{
+	const Resolution t = targetSize();
+	std::vector<gmupt_aov> out(static_cast<size_t>(t.first) * t.second);
+	const size_t bytes = out.size() * sizeof(gmupt_aov);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("renderAovs: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { renderAovs(static_cast<gmupt_aov*>(d), bytes, samples); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error("renderAovs: cannot read the records back");
+	return out;
 }
 
 void Renderer::bindScene()

@@ -45,6 +45,11 @@ public:
 	// and what it hits first, light spheres up to the camera's lightCount included
 	struct Pick { gmupt_ray ray; gmupt_hit hit; };
 	Pick pick(float x, float y);
+	// AOV buffers of the current camera (gmupt_render_aovs): one gmupt_aov per pixel of targetSize(), row-major -- albedo / normal guide images
+	// for a denoiser, depth, position, ids.  samples 1..8: s*s stratified rays per pixel for the albedo and normal planes when > 1.
+	// The first form writes caller-owned device memory (16-byte aligned, bytes >= pixels * 64); the second returns the records on the host.
+	gmupt_trace_info renderAovs(gmupt_aov* deviceOut, size_t bytes, unsigned samples = 1);
+	std::vector<gmupt_aov> renderAovs(unsigned samples = 1);
 
 private:
 	void createDevice(int hipDevice);

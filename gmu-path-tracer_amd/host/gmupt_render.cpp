@@ -8,8 +8,12 @@
 //                                                         rank 0 writes --dump / --pfm of the whole frame; --no-gather: every rank dumps its band
 //                [--print-bands H N]                      the row split, as JSON
 //                [--pick X,Y]                             after the frames: what lies under whole-frame pixel (X, Y), as one JSON line
+//                [--aov PREFIX [--aov-samples S]]         after the frames: the AOV buffers of the camera (gmupt_render_aovs, S = 1..8, default 1):
+//                                                         PREFIX_albedo.pfm, PREFIX_normal.pfm ("PF"), PREFIX_depth.pfm ("Pf") and PREFIX.aov,
+//                                                         the raw 64-byte gmupt_aov records, row-major from the top row (single process only)
 //                [--help]                                 this list
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,6 +47,21 @@ void writePfmFile(const std::string& path, const std::vector<float>& rgba, unsig
 	}
 	std::fclose(f);
 }
+// one AOV plane as a PFM: "PF" (3 channels) or "Pf" (1), little-endian, bottom row first; offset / channels pick the floats of a record
+void writeAovPfm(const std::string& path, const std::vector<gmupt_aov>& aov, unsigned w, unsigned h, size_t offset, int channels)
+{
+	std::FILE* f = std::fopen(path.c_str(), "wb");
+	if (!f) throw std::runtime_error("Failed to write " + path);
+	std::fprintf(f, "%s\n%u %u\n-1.0\n", channels == 3 ? "PF" : "Pf", w, h);
+	std::vector<float> row(static_cast<size_t>(w) * channels);
+	for (unsigned y = h; y-- > 0;)
+	{
+		for (unsigned x = 0; x < w; x++)
+			std::memcpy(&row[static_cast<size_t>(x) * channels], reinterpret_cast<const char*>(&aov[static_cast<size_t>(y) * w + x]) + offset, sizeof(float) * channels);
+		std::fwrite(row.data(), sizeof(float), row.size(), f);
+	}
+	std::fclose(f);
+}
 }
 
 int main(int argc, char** argv)
@@ -54,6 +73,7 @@ int main(int argc, char** argv)
 	unsigned ranks = 1, rank = 0; int device = -1;
 	std::string paramsOnly, rendezvous;
 	bool doPick = false; float pickX = 0.f, pickY = 0.f;
+	std::string aovPrefix; unsigned aovSamples = 1;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
 		auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -75,12 +95,16 @@ int main(int argc, char** argv)
 		else if (a == "--rendezvous") rendezvous = next();
 		else if (a == "--device") device = std::atoi(next());
 		else if (a == "--no-gather") noGather = true;
+		else if (a == "--aov") aovPrefix = next();
+		else if (a == "--aov-samples") aovSamples = std::strtoul(next(), nullptr, 10);
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
 			            "             [--build-only] [--dump-mesh out.gmesh] [--models-root DIR] [--list-scenes] [--params FILE]\n"
 			            "             [--ranks N --rank R --rendezvous FILE [--device D] [--no-gather]] [--print-bands H N]\n"
-			            "             [--pick X,Y]   after the frames: triangle / material / light sphere under whole-frame pixel (X, Y), one JSON line\n");
+			            "             [--pick X,Y]   after the frames: triangle / material / light sphere under whole-frame pixel (X, Y), one JSON line\n"
+			            "             [--aov PREFIX [--aov-samples S]]   after the frames: the AOV buffers of the camera, S = 1..8 samples per axis (default 1):\n"
+			            "                            PREFIX_albedo.pfm, PREFIX_normal.pfm (PF), PREFIX_depth.pfm (Pf), PREFIX.aov (64-byte gmupt_aov records); not with --ranks\n");
 			return 0;
 		}
 		else if (a == "--print-bands") { // H N: the row bands of an H-row frame over N ranks, as JSON (the CPU tests compare them with tiles.py)
@@ -146,6 +170,8 @@ int main(int argc, char** argv)
 			            mesh.numTriangles(), mesh.numVertices(), mesh.materials.size(), glass, bvh.tree().size(), bvh.indices().size(), bvh.sah(), s, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], texInfo.c_str());
 			return 0;
 		}
+		if (!aovPrefix.empty() && ranks > 1)
+			throw std::invalid_argument("--aov renders the AOV buffers of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
 		if (ranks > 1 || !rendezvous.empty())
 		{
 			// one process per GPU: row band `rank` of `ranks`, the camera of the whole frame; the bands meet on rank 0 (RCCL send / receive)
@@ -184,6 +210,16 @@ int main(int argc, char** argv)
 			            pickX, pickY, pk.hit.triangle, pk.hit.material, pk.hit.light, pk.hit.t, pk.hit.u, pk.hit.v, pk.ray.origin[0], pk.ray.origin[1], pk.ray.origin[2],
 			            pk.ray.direction[0], pk.ray.direction[1], pk.ray.direction[2]);
 			if (found) std::printf(", \"point\": [%.9g, %.9g, %.9g]}\n", pt[0], pt[1], pt[2]); else std::printf(", \"point\": null}\n");
+		}
+		if (!aovPrefix.empty()) {
+			const std::vector<gmupt_aov> aov = renderer.renderAovs(aovSamples);
+			writeAovPfm(aovPrefix + "_albedo.pfm", aov, w, h, offsetof(gmupt_aov, albedo), 3);
+			writeAovPfm(aovPrefix + "_normal.pfm", aov, w, h, offsetof(gmupt_aov, normal), 3);
+			writeAovPfm(aovPrefix + "_depth.pfm", aov, w, h, offsetof(gmupt_aov, depth), 1);
+			std::FILE* f = std::fopen((aovPrefix + ".aov").c_str(), "wb");
+			if (!f || std::fwrite(aov.data(), sizeof(gmupt_aov), aov.size(), f) != aov.size()) throw std::runtime_error("cannot write " + aovPrefix + ".aov");
+			std::fclose(f);
+			std::printf("aov %s: %ux%u, %u samples\n", aovPrefix.c_str(), w, h, aovSamples);
 		}
 		if (!pfm.empty()) renderer.writePfm(pfm);
 		if (!dump.empty()) {

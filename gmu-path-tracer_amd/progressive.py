@@ -56,6 +56,14 @@ class ProgressiveSession:
         return {"triangle": int(hit.triangle), "material": int(hit.material), "light": int(hit.light), "t": float(hit.t),
                 "point": (o + d * np.float32(hit.t)) if found else None}
 
+    def aovs(self, samples=1):
+        """The G-buffer of the session's current camera for a denoiser or a compositor: capi.Renderer.aovs (gmupt_render_aovs), split by
+        capi.aov_fields into named numpy arrays of shape (H, W) / (H, W, 3) -- albedo, normal, depth, position, roughness, metallic,
+        triangle, material, light, coverage.  samples: 1..8 stratified samples per axis for the albedo / normal planes.  Like pick, it
+        uses the camera the renderer was last given (the frame just drawn)."""
+        from . import capi
+        return capi.aov_fields(self.renderer.aovs(samples))
+
     # ---- frames
     def frame(self, dt=0.0):
         self.camera.update(dt)                       # Renderer::update: camera vectors, iterationCounter, randomSeed

@@ -257,6 +257,44 @@ int gmupt_camera_pick_ray(const gmupt_camera_buffer* cam, float px, float py, gm
  * GMUPT_ERR_NOT_BOUND also when no camera was set.  ray_out may be NULL. */
 int gmupt_pick(gmupt_renderer* r, float px, float py, uint32_t light_count, gmupt_ray* ray_out, gmupt_hit* hit_out);
 
+/* ---- AOV buffers: the per-pixel G-buffer of the camera rays (albedo, normal, depth, position, ids) ----
+ * One 64-byte gmupt_aov record per pixel of the renderer's framebuffer rectangle (the tile in tile mode), row-major, for a denoiser's guide
+ * images, compositing and masks.  The hit shading is the renderer's own (the setMaterialHitProperties code of k_logic, logic.hlsl:79-133):
+ * every value below is bit for bit what the logic stage computes for the same ray.
+ *
+ * Rays: samples = s in 1..8.  Pixel (x, y) in whole-frame coordinates (tile origin added) has R = 1 (s = 1) or s*s + 1 rays:
+ *   k = 0            the centre ray, bit for bit gmupt_camera_pick_ray(cam, x, y);
+ *   k = 1 + b*s + a  (a, b in 0..s-1, s > 1) the stratified ray through ((float)x + o(a), (float)y + o(b)), o(i) = (float)(2*i + 1) / (float)s - 1.0f,
+ *                    which spans newPath's jitter range [-1, 1] (newPath.hlsl:36-37): the filtered planes share the beauty image's pixel filter.
+ *   gmupt_aov_ray returns exactly these rays (host only).
+ * Per ray, the closest hit with the light spheres up to the camera's lightCount (the renderer's extension cast):
+ *   triangle hit, no nearer light: albedo / metallic / roughness / normal = what k_logic writes to matColor, matMR, normal for that ray --
+ *                                  texture samples, the normal map (oriented by the ray direction), the normal not renormalised;
+ *   light sphere nearer:           albedo = emission / max(emission) (sampleLight, logic.hlsl:192-197); normal, metallic, roughness 0;
+ *   miss:                          albedo = cam.envColor.rgb; normal, metallic, roughness 0.
+ * Filtered planes (albedo, normal): s = 1 the centre ray's values; s > 1 per component sum = 0.0f, then += the s*s stratified values in k
+ *   order, then sum / (float)(s*s).  Every other field is the centre ray's.
+ * Calling: `out` is caller-owned DEVICE memory, 16-byte aligned, bytes >= width * height * 64.  The call is enqueued on the renderer's stream
+ *   behind pending gmupt_iterate work and synchronises; it reads back its own fault flags (GMUPT_ERR_CAST_FAULT as gmupt_trace_rays).  The
+ *   frame, path state, queues, counters and gmupt_get_stats are not touched (the ray-query counters and statistics are used).  The rays are
+ *   cast in chunks of whole pixel rows of at most 2^21 rays; the scratch of one chunk (64 MiB of rays, 64 MiB of hits) is allocated on the
+ *   first call and kept until gmupt_renderer_destroy, whatever the image size or s.
+ * Errors: GMUPT_ERR_NOT_BOUND without a scene or a camera; GMUPT_ERR_INVALID_ARGUMENT for a NULL or misaligned out, too few bytes, samples
+ *   outside 1..8, or one row of more than 2^21 rays (width * R); GMUPT_ERR_UNSUPPORTED where gmupt_trace_rays returns it.  info (may be
+ *   NULL): flags and redo_rays summed over the chunks, ms = device time of the whole call. */
+typedef struct {
+    float albedo[3];   float depth;       /* depth = t of the centre ray (FLT_MAX on a miss) */
+    float normal[3];   float roughness;   /* roughness after max(0.014, .) (logic.hlsl:126), centre ray */
+    float position[3]; float metallic;    /* position = o + d * t of the centre ray (surfacePoint of finish_extension_ray); 0 on a miss */
+    int32_t triangle; uint32_t material; uint32_t light; uint32_t coverage;   /* triangle / material / light exactly as gmupt_hit of the centre ray;
+                                                                                  coverage = filtered samples that hit a triangle and no light */
+} gmupt_aov;           /* 64 bytes */
+#define GMUPT_AOV_MAX_SAMPLES 8
+#define GMUPT_AOV_CHUNK_RAYS (1u << 21)
+int gmupt_render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info /* may be NULL */);
+/* host only: ray k (0 .. R-1) of whole-frame pixel (x, y) at `samples` = s, as stated above; tmax = FLT_MAX */
+int gmupt_aov_ray(const gmupt_camera_buffer* cam, uint32_t x, uint32_t y, uint32_t samples, uint32_t k, gmupt_ray* out);
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);

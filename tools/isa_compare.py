@@ -5,6 +5,11 @@
         -fno-gpu-flush-denormals-to-zero -fno-fast-math --cuda-device-only -S -x hip csrc/pt_traverse_wide.hip -Iinclude -o wide.s
   python tools/isa_compare.py before.s after.s
 
+Other kernels of any source file: --kernel NAME (repeatable) pairs the kernels whose mangled name is gmupt::NAME with any parameter list,
+e.g. for csrc/pt_kernels.hip:
+
+  python tools/isa_compare.py --kernel k_clear --kernel k_logic --kernel k_material before.s after.s
+
 Kernels are paired by their template arguments <STATS, REPS> (the mangled names differ once the ray-source policy is a template
 parameter: only the StateIO instantiation of the new file is paired).  Bodies are compared after renumbering the local labels by first
 appearance and dropping comments and blank lines; .vgpr_count / .sgpr_count / LDS and scratch sizes are compared from the metadata.
@@ -17,20 +22,39 @@ KERNEL = re.compile(r"^(_ZN5gmupt8k_cast_wILb([01])ELi(\d+)E(NS_7StateIOE)?EEv\S
 META_KEYS = (".vgpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count")
 
 
-def kernels(path):
+def named(names):
+    """Matcher of the kernels gmupt::NAME for NAME in names: (line) -> (key, mangled name) or None."""
+    pat = re.compile(r"^(_ZN5gmupt(\d+)(\w+?)E\S*):(\s|$)")
+
+    def match(line):
+        m = pat.match(line)
+        if m and m.group(3)[:int(m.group(2))] in names and len(m.group(3)) >= int(m.group(2)):
+            return m.group(3)[:int(m.group(2))], m.group(1)
+        return None
+    return match
+
+
+def cast_w(line):
+    m = KERNEL.match(line)
+    if m and (m.group(4) or "QueryIO" not in m.group(1)):
+        return (m.group(2) == "1", int(m.group(3))), m.group(1)
+    return None
+
+
+def kernels(path, match=cast_w):
     lines = open(path).read().splitlines()
     out = {}
     i = 0
     while i < len(lines):
-        m = KERNEL.match(lines[i])
-        if m and (m.group(4) or "QueryIO" not in m.group(1)):
-            key = (m.group(2) == "1", int(m.group(3)))
+        km = match(lines[i])
+        if km:
+            key, name = km
             body = []
             i += 1
             while i < len(lines) and not lines[i].startswith(".Lfunc_end"):
                 body.append(lines[i])
                 i += 1
-            out[key] = {"name": m.group(1), "body": normalise(body)}
+            out[key] = {"name": name, "body": normalise(body)}
         i += 1
     # metadata (the YAML note at the end): .name follows the keys of its kernel's map in alphabetical order
     text = "\n".join(lines)
@@ -54,20 +78,27 @@ def normalise(body):
         for lab in re.findall(r"\.LBB\d+_\d+", l):
             labels.setdefault(lab, ".L%d" % len(labels))
         l = re.sub(r"\.LBB\d+_\d+", lambda m: labels[m.group(0)], l)
-        l = re.sub(r"_ZN5gmupt8k_cast_w\S*?(?=[@+\s,)]|$)", "KERNEL", l)
+        l = re.sub(r"_ZN5gmupt\d+k_\w+?E\S*?(?=[@+\s,)]|$)", "KERNEL", l)
         res.append(l)
     return res
 
 
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-    ok = True
+    args = sys.argv[1:]
+    names = [args[i + 1] for i in range(len(args) - 1) if args[i] == "--kernel"]
+    files = [a for i, a in enumerate(args) if a != "--kernel" and (i == 0 or args[i - 1] != "--kernel")]
+    match = named(set(names)) if names else cast_w
+    a, b = kernels(files[0], match), kernels(files[1], match)
+    ok = bool(a) or not names
+    if names and sorted(a) != sorted(names):
+        print("kernels not found in %s: %s" % (files[0], sorted(set(names) - set(a)))); ok = False
     for key in sorted(a):
         if key not in b:
-            print("%s: missing in %s" % (a[key]["name"], sys.argv[2])); ok = False; continue
+            print("%s: missing in %s" % (a[key]["name"], files[1])); ok = False; continue
         same = a[key]["body"] == b[key]["body"]
         meta_same = a[key].get("meta") == b[key].get("meta")
-        print("k_cast_w<%s, %d>: %d lines, body %s, metadata %s %s" % ("true" if key[0] else "false", key[1], len(a[key]["body"]),
+        label = key if names else "k_cast_w<%s, %d>" % ("true" if key[0] else "false", key[1])
+        print("%s: %d lines, body %s, metadata %s %s" % (label, len(a[key]["body"]),
               "identical" if same else "DIFFERS", "identical" if meta_same else "DIFFERS", a[key].get("meta")))
         if not meta_same:
             print("   after:", b[key].get("meta"))
