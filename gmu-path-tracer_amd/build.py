@@ -10,9 +10,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libgmupt.so")
 
-DEVICE_SOURCES = ["csrc/pt_kernels.hip", "csrc/pt_traverse.hip", "csrc/pt_traverse_wide.hip", "csrc/pt_traverse_variants.hip", "csrc/pt_aov.hip", "csrc/gmupt_capi.hip"]   # pt_traverse_variants.hip is empty without -DGMUPT_VARIANTS
+DEVICE_SOURCES = ["csrc/pt_kernels.hip", "csrc/pt_traverse.hip", "csrc/pt_traverse_wide.hip", "csrc/pt_traverse_variants.hip", "csrc/pt_aov.hip", "csrc/pt_denoise.hip", "csrc/gmupt_capi.hip"]   # pt_traverse_variants.hip is empty without -DGMUPT_VARIANTS
 HOST_SOURCES = ["host/sbvh_builder.cpp", "host/Camera.cpp", "host/TextureLoader.cpp", "host/AvirResize.cpp"]
-HEADERS = ["csrc/pt_traverse_common.hpp", "csrc/pt_shading.hpp", "csrc/pt_traverse_deferred.hpp", "csrc/pt_kernel_util.hpp", "host/MeshData.hpp", "host/BVHWrapper.hpp", "csrc/pt_device.hpp", "csrc/detmath.hpp", "host/sbvh_builder.hpp", "host/Camera.hpp", "host/TextureLoader.hpp", "host/png_reader.hpp", "host/Constants.hpp", "../include/gmupt.h"]
+HEADERS = ["csrc/pt_traverse_common.hpp", "csrc/pt_shading.hpp", "csrc/pt_denoise.hpp", "csrc/pt_traverse_deferred.hpp", "csrc/pt_kernel_util.hpp", "host/MeshData.hpp", "host/BVHWrapper.hpp", "csrc/pt_device.hpp", "csrc/detmath.hpp", "host/sbvh_builder.hpp", "host/Camera.hpp", "host/TextureLoader.hpp", "host/png_reader.hpp", "host/Constants.hpp", "../include/gmupt.h"]
 
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -26,7 +26,7 @@ FLAGS = [
 # and a build of the wide ray cast whose stacks overflow on ordinary scenes.
 TEST_BUILDS = {"variants": ["-DGMUPT_VARIANTS"], "scan1": ["-DGMUPT_SCAN_GROUP=1"],
                "wides8": ["-DGMUPT_WIDE_STACK=8", "-DGMUPT_WIDE_TOP=64", "-DGMUPT_WIDE_PARK=4"]}   # wide ray cast with a tiny LDS share per lane: stacks run full, rays are parked for the exact walk all the time
-EXPERIMENT_BUILDS = {"wxcd": ["-DGMUPT_WIDE_XCD_EXPERIMENT=1"], "wsg0": ["-DGMUPT_WIDE_SIGNED=0"], "mrg0": ["-DGMUPT_MATERIAL_REGROUP=0"], "wq0": ["-DGMUPT_WIDE_QUADPK=0"], "wqt0": ["-DGMUPT_WIDE_QUADTRI=0"]}   # name -> extra flags of A/B timing builds (tools/ only, never loaded by tests), e.g. {"wg1024": ["-DGMUPT_DEF_BLOCK=1024", "-DGMUPT_TOP_NODES=512"]}
+EXPERIMENT_BUILDS = {"wxcd": ["-DGMUPT_WIDE_XCD_EXPERIMENT=1"], "wsg0": ["-DGMUPT_WIDE_SIGNED=0"], "mrg0": ["-DGMUPT_MATERIAL_REGROUP=0"], "wq0": ["-DGMUPT_WIDE_QUADPK=0"], "wqt0": ["-DGMUPT_WIDE_QUADTRI=0"], "dnb0": ["-DGMUPT_DN_BATCH=0"]}   # name -> extra flags of A/B timing builds (tools/ only, never loaded by tests), e.g. {"wg1024": ["-DGMUPT_DEF_BLOCK=1024", "-DGMUPT_TOP_NODES=512"]}
 
 
 def lib_path(name=None):

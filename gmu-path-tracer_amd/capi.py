@@ -110,6 +110,16 @@ aov_dtype = np.dtype([("albedo", "<f4", 3), ("depth", "<f4"), ("normal", "<f4", 
 assert ray_dtype.itemsize == 32 and hit_dtype.itemsize == 32 and aov_dtype.itemsize == 64
 
 
+class DenoiseParams(C.Structure):
+    """gmupt_denoise_params: 20 bytes (passes 1..5; every sigma finite and > 0)."""
+    _fields_ = [("passes", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("sigma_albedo", C.c_float)]
+
+
+DENOISE_MAX_PASSES = 5
+assert C.sizeof(DenoiseParams) == 20
+
+
 class GmuptError(RuntimeError):
     def __init__(self, msg, code=0):
         super().__init__(msg)
@@ -152,6 +162,10 @@ SYMBOLS = {
     "gmupt_pick": (C.c_int, [_P, C.c_float, C.c_float, C.c_uint32, C.POINTER(Ray), C.POINTER(Hit)]),
     "gmupt_render_aovs": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(TraceInfo)]),
     "gmupt_aov_ray": (C.c_int, [C.POINTER(CameraBuffer), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Ray)]),
+    "gmupt_denoise_default_params": (None, [C.POINTER(DenoiseParams)]),
+    "gmupt_denoise_image": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _P, C.c_size_t, C.POINTER(C.c_float)]),
+    "gmupt_render_denoised": (C.c_int, [_P, C.c_uint32, C.POINTER(DenoiseParams), _P, C.c_size_t, C.POINTER(TraceInfo)]),
+    "gmupt_denoise_host": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _P, C.c_size_t, C.c_uint32]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -513,6 +527,22 @@ class Renderer:
         self.last_aovs = ti
         return out
 
+    # denoiser (gmupt_render_denoised)
+    def denoise(self, aov_samples=1, info=None, **params):
+        """The a-trous denoiser on this renderer's frame (the tile in tile mode): gmupt_render_aovs(aov_samples) into internal scratch,
+        a copy of the framebuffer, then the filter (include/gmupt.h states it).  Returns an (H, W, 4) float32 torch tensor on this
+        renderer's GPU: rgb denoised, alpha the sample-count bits of the frame.  params: passes, sigma_color, sigma_normal, sigma_plane,
+        sigma_albedo (the rest keep gmupt_denoise_default_params).  info: optional TraceInfo to fill (ms = AOVs + filter)."""
+        import torch
+        dev = torch.device("cuda", getattr(self.dev, "index", 0))
+        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+        dp = denoise_params(**params)
+        torch.cuda.current_stream(dev).synchronize()
+        ti = info if info is not None else TraceInfo()
+        _check(lib().gmupt_render_denoised(self.h, int(aov_samples), C.byref(dp), C.c_void_p(out.data_ptr()), out.numel() * 4, C.byref(ti)))
+        self.last_denoise = ti
+        return out
+
     # reference-layout debug access
     def read_path_state(self):
         out = np.empty(self.pool * STATE_BYTES, dtype=np.uint8)
@@ -586,6 +616,56 @@ def aov_fields(aovs):
     rec = a.reshape(-1, 16).view(aov_dtype)[:, 0]
     shape = a.shape[:-1]
     return {k: rec[k].reshape(shape + rec[k].shape[1:]).copy() for k in aov_dtype.names}
+
+
+def denoise_params(**params):
+    """gmupt_denoise_default_params with the given fields replaced (passes, sigma_color, sigma_normal, sigma_plane, sigma_albedo)."""
+    dp = DenoiseParams()
+    lib().gmupt_denoise_default_params(C.byref(dp))
+    for k, v in params.items():
+        if k not in ("passes", "sigma_color", "sigma_normal", "sigma_plane", "sigma_albedo"):
+            raise TypeError("unknown denoiser parameter %r" % k)
+        setattr(dp, k, v)
+    return dp
+
+
+def denoise_image(renderer, beauty, aov, ms=None, **params):
+    """gmupt_denoise_image on torch tensors on the renderer's GPU: beauty (H, W, 4) float32 (a = sample-count bits), aov (H, W, 16)
+    float32 gmupt_aov records.  Returns the (H, W, 4) float32 result.  Any image size; enqueued on the renderer's stream after torch's
+    current stream is synchronised.  ms: optional list that receives the filter's device time."""
+    import torch
+    if beauty.dim() != 3 or beauty.shape[2] != 4 or aov.dim() != 3 or aov.shape[2] != 16 or tuple(aov.shape[:2]) != tuple(beauty.shape[:2]):
+        raise GmuptError("denoise_image: beauty must be (H, W, 4) and aov (H, W, 16)", ERR_INVALID_ARGUMENT)
+    if beauty.dtype != torch.float32 or aov.dtype != torch.float32 or not beauty.is_cuda or not aov.is_cuda:
+        raise GmuptError("denoise_image: float32 tensors on the GPU", ERR_INVALID_ARGUMENT)
+    beauty, aov = beauty.contiguous(), aov.contiguous()
+    H, W = beauty.shape[0], beauty.shape[1]
+    out = torch.empty_like(beauty)
+    dp = denoise_params(**params)
+    torch.cuda.current_stream(beauty.device).synchronize()
+    t = C.c_float(0.0)
+    _check(lib().gmupt_denoise_image(renderer.h, C.c_void_p(beauty.data_ptr()), C.c_void_p(aov.data_ptr()), W, H, C.byref(dp),
+                                     C.c_void_p(out.data_ptr()), out.numel() * 4, C.byref(t)))
+    if ms is not None:
+        ms.append(t.value)
+    return out
+
+
+def denoise_host(beauty, aov, threads=16, **params):
+    """gmupt_denoise_host: the same filter on the CPU, bit for bit the device result.  beauty (H, W, 4) float32, aov (H, W, 16) float32
+    (or an (H, W) array of aov_dtype); numpy or torch.  Returns an (H, W, 4) float32 numpy array."""
+    b = beauty.cpu().numpy() if hasattr(beauty, "cpu") else np.asarray(beauty)
+    a = aov.cpu().numpy() if hasattr(aov, "cpu") else np.asarray(aov)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.dtype == aov_dtype:
+        a = a.view(np.float32).reshape(a.shape + (16,))
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if b.ndim != 3 or b.shape[2] != 4 or a.shape != b.shape[:2] + (16,):
+        raise GmuptError("denoise_host: beauty must be (H, W, 4) and aov (H, W, 16)", ERR_INVALID_ARGUMENT)
+    out = np.empty_like(b)
+    dp = denoise_params(**params)
+    _check(lib().gmupt_denoise_host(_ptr(b), _ptr(a), b.shape[1], b.shape[0], C.byref(dp), _ptr(out), out.nbytes, int(threads)))
+    return out
 
 
 def sbvh_build(verts, indices, vertex_material=None, params=None):

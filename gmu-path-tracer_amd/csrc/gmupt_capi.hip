@@ -3,6 +3,7 @@
 #include "pt_device.hpp"
 #include "detmath.hpp"
 #include "pt_shading.hpp"
+#include "pt_denoise.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
 #include "../host/TextureLoader.hpp"
@@ -10,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -55,6 +57,8 @@ void launch_aov_raygen(const gmupt_camera_buffer& cam, uint32_t x0, uint32_t y0,
                        gmupt_ray* rays, hipStream_t s);
 void launch_aov_resolve(const RenderParams& p, uint32_t npix, uint32_t samples, uint32_t R, const gmupt_ray* rays, const gmupt_hit* hits,
                         gmupt_aov* out, hipStream_t s);
+void launch_denoise(const float4* beauty, const float4* aov, int W, int H, const DnParams& prm, void* scratch, float4* out, hipStream_t s);
+void denoise_host(const float* beauty, const void* aov, int W, int H, const DnParams& prm, float* out, int threads);
 }
 using namespace gmupt;
 
@@ -229,6 +233,11 @@ struct gmupt_renderer {
     hipEvent_t queryEv[2] = { nullptr, nullptr };
     // AOV buffers (gmupt_render_aovs): rays and hits of one chunk (GMUPT_AOV_CHUNK_RAYS each, 128 MiB), allocated on first use
     gmupt_ray* aovRays = nullptr; gmupt_hit* aovHits = nullptr;
+    // denoiser (gmupt_denoise_image): the filter's scratch (kDnScratchBytes per pixel) and, for gmupt_render_denoised, the AOV records and
+    // the framebuffer copy (80 bytes per pixel); allocated on first use, grown when a larger image comes, freed by gmupt_renderer_destroy
+    void* dnScratch = nullptr; size_t dnScratchBytes = 0;
+    void* dnInput = nullptr; size_t dnInputBytes = 0;
+    hipEvent_t dnEv[2] = { nullptr, nullptr };
 };
 
 static int dev_alloc(gmupt_renderer* r, void** ptr, size_t bytes, int fill)
@@ -259,7 +268,10 @@ extern "C" void gmupt_renderer_destroy(gmupt_renderer* r)
     if (r->stream) (void)hipStreamSynchronize(r->stream);
     for (auto& se : r->evPool) for (auto& e : se.e) (void)hipEventDestroy(e);
     for (hipEvent_t e : r->queryEv) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : r->dnEv) if (e) (void)hipEventDestroy(e);
     for (void* a : r->allocs) (void)hipFree(a);
+    if (r->dnScratch) (void)hipFree(r->dnScratch);
+    if (r->dnInput) (void)hipFree(r->dnInput);
     if (r->p.fb) (void)hipFree(r->p.fb);
     if (r->p.listHead) (void)hipFree(r->p.listHead);
     if (r->travNodes) (void)hipFree(r->travNodes);
@@ -1092,6 +1104,129 @@ extern "C" int gmupt_render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov*
     if (info) { info->flags = flags; info->redo_rays = ds.castRedoRays; info->ms = ms; }
     if (ds.stackOverflow & 2u) return fail(GMUPT_ERR_CAST_FAULT, "gmupt_render_aovs: a wave of the ray cast left its loop at the iteration limit (GMUPT_STAT_CAST_ABORTED): the records are invalid");
     if (ds.stackOverflow & 1u) return fail(GMUPT_ERR_CAST_FAULT, "gmupt_render_aovs: a traversal stack overflowed (GMUPT_STAT_STACK_OVERFLOW): the records are invalid");
+    return GMUPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ denoiser
+static_assert(sizeof(gmupt_denoise_params) == 20 && offsetof(gmupt_denoise_params, sigma_color) == 4 && offsetof(gmupt_denoise_params, sigma_normal) == 8 &&
+              offsetof(gmupt_denoise_params, sigma_plane) == 12 && offsetof(gmupt_denoise_params, sigma_albedo) == 16, "gmupt_denoise_params layout");
+
+extern "C" void gmupt_denoise_default_params(gmupt_denoise_params* p)
+{
+    if (!p) return;
+    p->passes = 5; p->sigma_color = 4.0f; p->sigma_normal = 128.0f; p->sigma_plane = 0.02f; p->sigma_albedo = 0.1f;
+}
+
+static int denoise_params(const char* fn, const gmupt_denoise_params* p, DnParams& out)
+{
+    gmupt_denoise_params d;
+    if (!p) { gmupt_denoise_default_params(&d); p = &d; }
+    if (p->passes < 1 || p->passes > GMUPT_DENOISE_MAX_PASSES) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: passes = %u (1..%d)", fn, p->passes, GMUPT_DENOISE_MAX_PASSES);
+    const float s[4] = { p->sigma_color, p->sigma_normal, p->sigma_plane, p->sigma_albedo };
+    const char* names[4] = { "sigma_color", "sigma_normal", "sigma_plane", "sigma_albedo" };
+    for (int k = 0; k < 4; k++)
+        if (!(std::isfinite(s[k]) && s[k] > 0.0f)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %s = %g (finite and > 0)", fn, names[k], (double)s[k]);
+    out.passes = (int)p->passes; out.sigmaColor = s[0]; out.sigmaNormal = s[1]; out.sigmaPlane = s[2]; out.sigmaAlbedo = s[3];
+    return GMUPT_OK;
+}
+
+// the arguments every denoiser entry checks; device pointers must be 16-byte aligned
+static int denoise_args(const char* fn, const void* beauty, const void* aov, uint32_t W, uint32_t H, const gmupt_denoise_params* p, const void* out, size_t bytes,
+                        bool device, DnParams& prm)
+{
+    if (!beauty || !aov || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null beauty, aov or output", fn);
+    if (device && (((uintptr_t)beauty | (uintptr_t)aov | (uintptr_t)out) & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: misaligned pointer (16 bytes)", fn);
+    if (W == 0 || H == 0 || W > 65535 || H > 65535 || (uint64_t)W * H > (1ull << 28)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: image of %ux%u (1..65535 each, at most 2^28 pixels)", fn, W, H);
+    {   // the last pass reads beauty texels of other pixels while it writes the output: the two ranges must not overlap at all
+        const uintptr_t b0 = (uintptr_t)beauty, o0 = (uintptr_t)out, n = (uintptr_t)W * H * 16;
+        if (o0 < b0 + n && b0 < o0 + n) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: the output overlaps the beauty image", fn);
+    }
+    if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu output bytes for %ux%u RGBA32F texels", fn, bytes, W, H);
+    return denoise_params(fn, p, prm);
+}
+
+// device memory of at least `need` bytes in *ptr, kept between calls (the old contents are not kept when it grows)
+static int grow_scratch(gmupt_renderer* r, void** ptr, size_t* have, size_t need)
+{
+    if (*have >= need) return GMUPT_OK;
+    if (*ptr) { HIP_TRY(hipStreamSynchronize(r->stream)); HIP_TRY(hipFree(*ptr)); *ptr = nullptr; *have = 0; }
+    HIP_TRY(hipMalloc(ptr, need));
+    *have = need;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_denoise_image(gmupt_renderer* r, const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height,
+                                   const gmupt_denoise_params* p, float* out_rgba, size_t out_bytes, float* ms)
+{
+    if (ms) *ms = 0.0f;
+    if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_denoise_image: null renderer");
+    DnParams prm;
+    int rc = denoise_args("gmupt_denoise_image", beauty_rgba, aov, width, height, p, out_rgba, out_bytes, true, prm);
+    if (rc != GMUPT_OK) return rc;
+    HIP_TRY(hipSetDevice(r->dev->id));
+    rc = grow_scratch(r, &r->dnScratch, &r->dnScratchBytes, (size_t)width * height * kDnScratchBytes);
+    if (rc != GMUPT_OK) return rc;
+    if (!r->dnEv[0]) for (hipEvent_t& e : r->dnEv) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(r->dnEv[0], r->stream));
+    launch_denoise(reinterpret_cast<const float4*>(beauty_rgba), reinterpret_cast<const float4*>(aov), (int)width, (int)height, prm, r->dnScratch,
+                   reinterpret_cast<float4*>(out_rgba), r->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(r->dnEv[1], r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    float t = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&t, r->dnEv[0], r->dnEv[1]));
+    if (ms) *ms = t;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_render_denoised(gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, float* out_rgba, size_t bytes, gmupt_trace_info* info)
+{
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_denoised: null renderer");
+    const uint32_t W = r->p.fbW, H = r->p.fbH;
+    if (!out_rgba || ((uintptr_t)out_rgba & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_denoised: null or misaligned output (16 bytes)");
+    if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_denoised: %zu output bytes for %ux%u RGBA32F texels", bytes, W, H);
+    DnParams prm;
+    int rc = denoise_params("gmupt_render_denoised", p, prm);
+    if (rc != GMUPT_OK) return rc;
+    // what gmupt_render_aovs would refuse, before the scratch is grown for it
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_denoised: no scene bound");
+    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_denoised: no camera set");
+    if (aov_samples < 1 || aov_samples > GMUPT_AOV_MAX_SAMPLES) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_denoised: aov_samples = %u (1..%d)", aov_samples, GMUPT_AOV_MAX_SAMPLES);
+    const uint32_t R = aov_samples == 1 ? 1u : aov_samples * aov_samples + 1u;
+    if ((uint64_t)W * R > GMUPT_AOV_CHUNK_RAYS) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_denoised: one row of %u pixels is %u rays at aov_samples = %u (at most 2^21)", W, W * R, aov_samples);
+    rc = query_supported(r, "gmupt_render_denoised");
+    if (rc != GMUPT_OK) return rc;
+    HIP_TRY(hipSetDevice(r->dev->id));
+    rc = grow_scratch(r, &r->dnInput, &r->dnInputBytes, (size_t)W * H * (sizeof(gmupt_aov) + 16));
+    if (rc != GMUPT_OK) return rc;
+    gmupt_aov* aov = static_cast<gmupt_aov*>(r->dnInput);
+    float* beauty = reinterpret_cast<float*>(static_cast<char*>(r->dnInput) + (size_t)W * H * sizeof(gmupt_aov));
+    gmupt_trace_info ai;
+    rc = gmupt_render_aovs(r, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai);
+    if (info) *info = ai;
+    if (rc != GMUPT_OK) return rc;
+    rc = gmupt_copy_framebuffer_to_device(r, beauty, (size_t)W * H * 16);
+    if (rc != GMUPT_OK) return rc;
+    float ms = 0.0f;
+    rc = gmupt_denoise_image(r, beauty, aov, W, H, p, out_rgba, bytes, &ms);
+    if (info) info->ms = ai.ms + ms;
+    return rc;
+}
+
+extern "C" int gmupt_denoise_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height, const gmupt_denoise_params* p,
+                                  float* out_rgba, size_t out_bytes, uint32_t threads)
+{
+    DnParams prm;
+    int rc = denoise_args("gmupt_denoise_host", beauty_rgba, aov, width, height, p, out_rgba, out_bytes, false, prm);
+    if (rc != GMUPT_OK) return rc;
+    try {
+        denoise_host(beauty_rgba, aov, (int)width, (int)height, prm, out_rgba, (int)std::min(std::max(threads, 1u), 16u));
+    } catch (const std::bad_alloc&) {
+        return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_denoise_host: out of host memory for %ux%u pixels", width, height);
+    } catch (const std::exception& e) {
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_denoise_host: %s", e.what());
+    }
     return GMUPT_OK;
 }
 

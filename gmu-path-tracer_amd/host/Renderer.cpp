@@ -115,6 +115,30 @@ std::vector<gmupt_aov> Renderer::renderAovs(unsigned samples)
 	return out;
 }
 
+gmupt_trace_info Renderer::denoise(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_denoise_params* params)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	gmupt_trace_info info{};
+	check(gmupt_render_denoised(mRenderer.get(), aovSamples, params, deviceOut, bytes, &info));
+	return info;
+}
+
+std::vector<float> Renderer::denoise(unsigned aovSamples, const gmupt_denoise_params* params)
+{
+	const Resolution t = targetSize();
+	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
+	const size_t bytes = out.size() * sizeof(float);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoise: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { denoise(static_cast<float*>(d), bytes, aovSamples, params); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error("denoise: cannot read the image back");
+	return out;
+}
+
 void Renderer::bindScene()
 {
 	if (!mSceneBound)

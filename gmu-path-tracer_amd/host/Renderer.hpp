@@ -50,6 +50,11 @@ public:
 	// The first form writes caller-owned device memory (16-byte aligned, bytes >= pixels * 64); the second returns the records on the host.
 	gmupt_trace_info renderAovs(gmupt_aov* deviceOut, size_t bytes, unsigned samples = 1);
 	std::vector<gmupt_aov> renderAovs(unsigned samples = 1);
+	// the a-trous denoiser on the current frame (gmupt_render_denoised): AOVs of the current camera at aovSamples, then the filter over
+	// targetSize(); RGBA32F, rgb denoised, a = the frame's sample-count bits.  params == nullptr: gmupt_denoise_default_params.
+	// The first form writes caller-owned device memory (16-byte aligned, bytes >= pixels * 16); the second returns the texels on the host.
+	gmupt_trace_info denoise(float* deviceOut, size_t bytes, unsigned aovSamples = 1, const gmupt_denoise_params* params = nullptr);
+	std::vector<float> denoise(unsigned aovSamples = 1, const gmupt_denoise_params* params = nullptr);
 
 private:
 	void createDevice(int hipDevice);

@@ -11,6 +11,9 @@
 //                [--aov PREFIX [--aov-samples S]]         after the frames: the AOV buffers of the camera (gmupt_render_aovs, S = 1..8, default 1):
 //                                                         PREFIX_albedo.pfm, PREFIX_normal.pfm ("PF"), PREFIX_depth.pfm ("Pf") and PREFIX.aov,
 //                                                         the raw 64-byte gmupt_aov records, row-major from the top row (single process only)
+//                [--denoise PREFIX [--aov-samples S]]     after the frames: the frame through the a-trous denoiser (gmupt_render_denoised, AOVs at
+//                                                         S samples per axis): PREFIX.pfm ("PF") and PREFIX.png (the capture's truncation, alpha 255)
+//                                                         (single process only)
 //                [--help]                                 this list
 #include <chrono>
 #include <cstddef>
@@ -23,6 +26,7 @@
 #include <string>
 #include "Renderer.hpp"
 #include "TileGather.hpp"
+#include "png_writer.hpp"
 #include <hip/hip_runtime_api.h>
 #include <memory>
 #include <vector>
@@ -74,6 +78,7 @@ int main(int argc, char** argv)
 	std::string paramsOnly, rendezvous;
 	bool doPick = false; float pickX = 0.f, pickY = 0.f;
 	std::string aovPrefix; unsigned aovSamples = 1;
+	std::string denoisePrefix;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
 		auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -97,6 +102,7 @@ int main(int argc, char** argv)
 		else if (a == "--no-gather") noGather = true;
 		else if (a == "--aov") aovPrefix = next();
 		else if (a == "--aov-samples") aovSamples = std::strtoul(next(), nullptr, 10);
+		else if (a == "--denoise") denoisePrefix = next();
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -104,7 +110,9 @@ int main(int argc, char** argv)
 			            "             [--ranks N --rank R --rendezvous FILE [--device D] [--no-gather]] [--print-bands H N]\n"
 			            "             [--pick X,Y]   after the frames: triangle / material / light sphere under whole-frame pixel (X, Y), one JSON line\n"
 			            "             [--aov PREFIX [--aov-samples S]]   after the frames: the AOV buffers of the camera, S = 1..8 samples per axis (default 1):\n"
-			            "                            PREFIX_albedo.pfm, PREFIX_normal.pfm (PF), PREFIX_depth.pfm (Pf), PREFIX.aov (64-byte gmupt_aov records); not with --ranks\n");
+			            "                            PREFIX_albedo.pfm, PREFIX_normal.pfm (PF), PREFIX_depth.pfm (Pf), PREFIX.aov (64-byte gmupt_aov records); not with --ranks\n"
+			            "             [--denoise PREFIX [--aov-samples S]]   after the frames: the frame through the a-trous denoiser guided by the AOV buffers\n"
+			            "                            (S samples per axis): PREFIX.pfm (PF) and PREFIX.png (8-bit, truncated like --capture); not with --ranks\n");
 			return 0;
 		}
 		else if (a == "--print-bands") { // H N: the row bands of an H-row frame over N ranks, as JSON (the CPU tests compare them with tiles.py)
@@ -172,6 +180,8 @@ int main(int argc, char** argv)
 		}
 		if (!aovPrefix.empty() && ranks > 1)
 			throw std::invalid_argument("--aov renders the AOV buffers of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
+		if (!denoisePrefix.empty() && ranks > 1)
+			throw std::invalid_argument("--denoise filters the frame of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
 		if (ranks > 1 || !rendezvous.empty())
 		{
 			// one process per GPU: row band `rank` of `ranks`, the camera of the whole frame; the bands meet on rank 0 (RCCL send / receive)
@@ -220,6 +230,20 @@ int main(int argc, char** argv)
 			if (!f || std::fwrite(aov.data(), sizeof(gmupt_aov), aov.size(), f) != aov.size()) throw std::runtime_error("cannot write " + aovPrefix + ".aov");
 			std::fclose(f);
 			std::printf("aov %s: %ux%u, %u samples\n", aovPrefix.c_str(), w, h, aovSamples);
+		}
+		if (!denoisePrefix.empty()) {
+			const std::vector<float> img = renderer.denoise(aovSamples);
+			writePfmFile(denoisePrefix + ".pfm", img, w, h);
+			std::vector<unsigned char> png(img.size());
+			for (size_t i = 0; i < img.size(); i += 4) // Renderer::captureScreen's conversion: float * 255 truncated, alpha 255
+			{
+				png[i] = static_cast<unsigned char>(img[i] * 255);
+				png[i + 1] = static_cast<unsigned char>(img[i + 1] * 255);
+				png[i + 2] = static_cast<unsigned char>(img[i + 2] * 255);
+				png[i + 3] = 255;
+			}
+			if (!gmupt::writePngRGBA8(denoisePrefix + ".png", png.data(), w, h)) throw std::runtime_error("Failed to write " + denoisePrefix + ".png");
+			std::printf("denoise %s: %ux%u, %u aov samples\n", denoisePrefix.c_str(), w, h, aovSamples);
 		}
 		if (!pfm.empty()) renderer.writePfm(pfm);
 		if (!dump.empty()) {

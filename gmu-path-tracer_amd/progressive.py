@@ -64,6 +64,12 @@ class ProgressiveSession:
         from . import capi
         return capi.aov_fields(self.renderer.aovs(samples))
 
+    def denoised(self, aov_samples=1, **params):
+        """A clean preview of the session's current frame: capi.Renderer.denoise (gmupt_render_denoised) as an (H, W, 4) float32 numpy
+        array -- rgb denoised, alpha the sample-count bits -- so to_rgba8 and the frame writers take it as they take a preview.  On a
+        tile renderer it is this rank's tile, denoised on its own (tile edges are image edges).  params: the gmupt_denoise_params fields."""
+        return self.renderer.denoise(aov_samples, **params).cpu().numpy()
+
     # ---- frames
     def frame(self, dt=0.0):
         self.camera.update(dt)                       # Renderer::update: camera vectors, iterationCounter, randomSeed

@@ -295,6 +295,65 @@ int gmupt_render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_
 /* host only: ray k (0 .. R-1) of whole-frame pixel (x, y) at `samples` = s, as stated above; tmax = FLT_MAX */
 int gmupt_aov_ray(const gmupt_camera_buffer* cam, uint32_t x, uint32_t y, uint32_t samples, uint32_t k, gmupt_ray* out);
 
+/* ---- denoiser: edge-avoiding a-trous wavelet filter guided by the AOV buffers (Dammertz et al. 2010, with the variance steering of
+ * SVGF, Schied et al. 2017, sections 4.3-4.4, without the temporal part) ----
+ * Inputs per pixel: the beauty RGBA32F texel of an accumulation target (rgb = running mean of tonemapped samples, a = sample count as
+ * uint bits) and its gmupt_aov record.  All arithmetic is binary32 in the order stated here, no contraction; dpow / dexp2 / dsqrt are the
+ * deterministic functions of DESIGN.md ("Deterministic math"), normalize3(v) = v * (1 / sqrt((v.x*v.x + v.y*v.y) + v.z*v.z)).
+ *
+ * Valid pixel: sample count > 0, aov.triangle != -1, aov.light == 0 and sqrt(dot3(aov.normal, aov.normal)) > 0.  Invalid pixels (misses,
+ *   light spheres, pixels without samples) are copied to the output bit for bit and have weight 0 as a neighbour.  A valid pixel has
+ *   n = normalize3(aov.normal), z = aov.depth, x = aov.position, a = aov.albedo, l = (0.2126f*r + 0.7152f*g) + 0.0722f*b of its beauty.
+ *   The filter works on the stored (tonemapped) values: there is no albedo demodulation, albedo is an edge-stopping guide.
+ * Initial variance of a valid p: over the valid pixels q of p's 3x3 neighbourhood inside the image (p included), row-major (dy outer),
+ *   S1 = sum l_q, S2 = sum l_q*l_q from 0.0f, m1 = S1 / (float)count, m2 = S2 / (float)count, v_p = max(0, m2 - m1*m1).
+ * Pass k = 0 .. passes-1, step s = 1 << k, colour c and variance v of the previous pass (pass 0: the beauty rgb and v_p); per valid p:
+ *   g_p = sum (h3[dx] * h3[dy]) * v_q / sum h3[dx] * h3[dy] over the valid q = p + (dx, dy) of the 3x3 neighbourhood inside the image,
+ *         h3 = {0.25, 0.5, 0.25}, both sums from 0.0f in row-major order, one division;
+ *   taps q = p + s * (i, j), j = -2..2 outer, i = -2..2 inner, skipped when outside the image or invalid (the centre is a tap):
+ *     w   = ((h[i] * h[j]) * w_n) * E,  h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *     w_n = dpow(max(0, dot3(n_p, n_q)), sigma_normal)
+ *     E   = dexp2(-((d_l + d_x) + d_a) * 1.44269504f)
+ *     d_l = |l_p - l_q| / (sigma_color * dsqrt(g_p) + 1e-6f)
+ *     d_x = |dot3(n_p, x_q - x_p)| / (sigma_plane * z_p)
+ *     d_a = ((|a_q.r - a_p.r| + |a_q.g - a_p.g|) + |a_q.b - a_p.b|) / sigma_albedo
+ *   W = sum w, C = sum w * c_q (per channel), V = sum (w * w) * v_q, all from 0.0f in tap order; c'_p = C / W, v'_p = V / (W * W).
+ *   (W > 0 whenever the centre weight is: with sane sigmas always.  If W is not > 0 the pixel keeps c_p and v_p.)
+ * Output: RGBA32F, rgb = the last pass's colour of a valid pixel, alpha = the input alpha bits; an invalid pixel is its input texel.
+ *   The PNG / PFM writers and progressive.to_rgba8 take it unchanged.
+ * Parameters: passes 1..5, every sigma finite and > 0, else GMUPT_ERR_INVALID_ARGUMENT. */
+typedef struct {
+    uint32_t passes;      /* a-trous passes (steps 1, 2, 4, ..); default 5 */
+    float sigma_color;    /* luminance edge stop, in units of the local standard deviation; default 4 */
+    float sigma_normal;   /* exponent of the normal cosine; default 128 */
+    float sigma_plane;    /* distance from p's tangent plane, relative to p's depth; default 0.02 */
+    float sigma_albedo;   /* L1 albedo difference; default 0.1 */
+} gmupt_denoise_params;   /* 20 bytes */
+#define GMUPT_DENOISE_MAX_PASSES 5
+void gmupt_denoise_default_params(gmupt_denoise_params* p);
+/* beauty_rgba (width * height RGBA32F texels), aov (width * height records) and out_rgba are caller-owned DEVICE memory, 16-byte aligned,
+ * row-major; any size (e.g. a gathered whole frame).  out_rgba must not overlap beauty_rgba (the last pass reads other pixels' beauty
+ * texels while it writes).  Enqueued on the renderer's stream behind pending work,
+ * then synchronises; the renderer's frame, state and statistics are not touched.  The filter's scratch (76 bytes per pixel) is allocated
+ * on first use, grown when a larger image comes, and kept until gmupt_renderer_destroy.  ms (may be NULL): device time of the filter.
+ * p may be NULL (the defaults).  Errors: GMUPT_ERR_INVALID_ARGUMENT for a NULL or misaligned pointer, an output overlapping the beauty,
+ * out_bytes < width * height * 16, an empty image or bad parameters. */
+int gmupt_denoise_image(gmupt_renderer* r, const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height,
+                        const gmupt_denoise_params* p, float* out_rgba, size_t out_bytes, float* ms /* may be NULL */);
+/* The renderer's framebuffer rectangle (the tile in tile mode; tile edges are image edges, so a tile's result differs from a whole-frame
+ * denoise near the seams): gmupt_render_aovs(r, aov_samples) into internal scratch, a copy of the framebuffer, then gmupt_denoise_image
+ * into out (device memory, 16-byte aligned, bytes >= width * height * 16).  Errors of gmupt_render_aovs (GMUPT_ERR_NOT_BOUND,
+ * GMUPT_ERR_UNSUPPORTED, GMUPT_ERR_CAST_FAULT ...) and of gmupt_copy_framebuffer_to_device are returned as they are; the ones that need no
+ * device work are checked before the internal scratch (80 bytes per pixel) is allocated or grown.  The frame, path
+ * state, queues, counters and statistics are not touched.  info (may be NULL): as gmupt_render_aovs, ms = AOV time + filter time. */
+int gmupt_render_denoised(gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, float* out_rgba, size_t bytes,
+                          gmupt_trace_info* info /* may be NULL */);
+/* The same filter on host arrays (the same binary32 sequence, bit for bit the device result), in row bands on up to `threads` std::threads
+ * (0 -> 1, at most 16); the result does not depend on the thread count.  out_rgba must not overlap beauty_rgba.  Errors as
+ * gmupt_denoise_image. */
+int gmupt_denoise_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height, const gmupt_denoise_params* p,
+                       float* out_rgba, size_t out_bytes, uint32_t threads);
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);
