@@ -120,6 +120,19 @@ DENOISE_MAX_PASSES = 5
 assert C.sizeof(DenoiseParams) == 20
 
 
+class TemporalParams(C.Structure):
+    """gmupt_temporal_params: 32 bytes (the spatial filter's parameters, then history_cap, min_normal_cos, plane_dist)."""
+    _fields_ = [("spatial", DenoiseParams), ("history_cap", C.c_float), ("min_normal_cos", C.c_float), ("plane_dist", C.c_float)]
+
+
+TEMPORAL_MAX_CAP = 65536.0
+assert C.sizeof(TemporalParams) == 32
+# gmupt_history: the integrated unfiltered colour, its effective sample count and the guides of one pixel (48 bytes)
+history_dtype = np.dtype([("color", "<f4", 3), ("count", "<f4"), ("normal", "<f4", 3), ("material", "<u4"), ("position", "<f4", 3),
+                          ("valid", "<u4")])
+assert history_dtype.itemsize == 48
+
+
 class GmuptError(RuntimeError):
     def __init__(self, msg, code=0):
         super().__init__(msg)
@@ -166,6 +179,15 @@ SYMBOLS = {
     "gmupt_denoise_image": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _P, C.c_size_t, C.POINTER(C.c_float)]),
     "gmupt_render_denoised": (C.c_int, [_P, C.c_uint32, C.POINTER(DenoiseParams), _P, C.c_size_t, C.POINTER(TraceInfo)]),
     "gmupt_denoise_host": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _P, C.c_size_t, C.c_uint32]),
+    "gmupt_temporal_default_params": (None, [C.POINTER(TemporalParams)]),
+    "gmupt_temporal_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "gmupt_temporal_destroy": (None, [_P]),
+    "gmupt_temporal_reset": (C.c_int, [_P]),
+    "gmupt_temporal_denoise_image": (C.c_int, [_P, _P, _P, C.POINTER(CameraBuffer), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                               C.POINTER(TemporalParams), _P, C.c_size_t, C.POINTER(C.c_float)]),
+    "gmupt_render_denoised_temporal": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(TemporalParams), _P, C.c_size_t, C.POINTER(TraceInfo)]),
+    "gmupt_temporal_integrate_host": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(CameraBuffer), C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _P, _P, C.c_uint32]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -418,6 +440,7 @@ class Renderer:
         self.width, self.height = width, height
         self.pool = pool_paths or PATHCOUNT
         self._scene = None
+        self._temporals = []   # history handles of this renderer: closed before it
 
     def bind_scene(self, sb):
         self._scene = sb  # keep the buffers alive
@@ -543,6 +566,24 @@ class Renderer:
         self.last_denoise = ti
         return out
 
+    # temporal reuse (gmupt_render_denoised_temporal)
+    def denoise_temporal(self, handle, aov_samples=1, info=None, **params):
+        """The denoiser with temporal reuse on this renderer's frame (the tile in tile mode): AOVs and a framebuffer copy as denoise(),
+        then the frame integrated with the reprojected history of `handle` (a Temporal of this renderer) and filtered.  The first call
+        after an iteration that cleared the frame, or after a resize, starts a new accumulation epoch (include/gmupt.h).  Returns an
+        (H, W, 4) float32 torch tensor on this renderer's GPU: rgb denoised, alpha the effective sample-count bits.  params: the
+        temporal_params fields.  info: optional TraceInfo to fill (ms = AOVs + integration + filter)."""
+        import torch
+        dev = torch.device("cuda", getattr(self.dev, "index", 0))
+        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+        tp = temporal_params(**params)
+        torch.cuda.current_stream(dev).synchronize()
+        ti = info if info is not None else TraceInfo()
+        _check(lib().gmupt_render_denoised_temporal(self.h, handle.h, int(aov_samples), C.byref(tp), C.c_void_p(out.data_ptr()), out.numel() * 4,
+                                                    C.byref(ti)))
+        self.last_denoise = ti
+        return out
+
     # reference-layout debug access
     def read_path_state(self):
         out = np.empty(self.pool * STATE_BYTES, dtype=np.uint8)
@@ -572,7 +613,29 @@ class Renderer:
 
     def close(self):
         if self.h:
+            for t in self._temporals:
+                t.close()
             lib().gmupt_renderer_destroy(self.h)
+            self.h = _P()
+
+
+class Temporal:
+    """gmupt_temporal: the history of one renderer's denoised frames (two record sets: the frozen history of earlier accumulations and
+    the records of the latest call).  It uses the renderer's device and stream and is closed with it at the latest."""
+
+    def __init__(self, renderer):
+        self.renderer = renderer
+        self.h = _P()
+        _check(lib().gmupt_temporal_create(renderer.h, C.byref(self.h)))
+        renderer._temporals.append(self)
+
+    def reset(self):
+        """Drops both record sets: the next output is the plain spatial denoise."""
+        _check(lib().gmupt_temporal_reset(self.h))
+
+    def close(self):
+        if self.h:
+            lib().gmupt_temporal_destroy(self.h)
             self.h = _P()
 
 
@@ -666,6 +729,79 @@ def denoise_host(beauty, aov, threads=16, **params):
     dp = denoise_params(**params)
     _check(lib().gmupt_denoise_host(_ptr(b), _ptr(a), b.shape[1], b.shape[0], C.byref(dp), _ptr(out), out.nbytes, int(threads)))
     return out
+
+
+TEMPORAL_FIELDS = ("history_cap", "min_normal_cos", "plane_dist")
+
+
+def temporal_params(**params):
+    """gmupt_temporal_default_params with the given fields replaced: history_cap, min_normal_cos, plane_dist, and the spatial filter's
+    passes, sigma_color, sigma_normal, sigma_plane, sigma_albedo."""
+    tp = TemporalParams()
+    lib().gmupt_temporal_default_params(C.byref(tp))
+    for k, v in params.items():
+        if k in TEMPORAL_FIELDS:
+            setattr(tp, k, v)
+        elif k in ("passes", "sigma_color", "sigma_normal", "sigma_plane", "sigma_albedo"):
+            setattr(tp.spatial, k, v)
+        else:
+            raise TypeError("unknown temporal denoiser parameter %r" % k)
+    return tp
+
+
+def temporal_denoise_image(handle, beauty, aov, cam_buffer, new_accumulation, origin=(0, 0), ms=None, **params):
+    """gmupt_temporal_denoise_image on torch tensors on the handle's GPU: beauty (H, W, 4) float32 (a = sample-count bits), aov (H, W, 16)
+    float32 records, rendered with cam_buffer (a CameraBuffer) at `origin` of its whole frame.  new_accumulation: move the latest
+    call's records into the history first.  Returns the (H, W, 4) float32 result.  ms: optional list that receives the device time."""
+    import torch
+    if beauty.dim() != 3 or beauty.shape[2] != 4 or aov.dim() != 3 or aov.shape[2] != 16 or tuple(aov.shape[:2]) != tuple(beauty.shape[:2]):
+        raise GmuptError("temporal_denoise_image: beauty must be (H, W, 4) and aov (H, W, 16)", ERR_INVALID_ARGUMENT)
+    if beauty.dtype != torch.float32 or aov.dtype != torch.float32 or not beauty.is_cuda or not aov.is_cuda:
+        raise GmuptError("temporal_denoise_image: float32 tensors on the GPU", ERR_INVALID_ARGUMENT)
+    beauty, aov = beauty.contiguous(), aov.contiguous()
+    H, W = beauty.shape[0], beauty.shape[1]
+    out = torch.empty_like(beauty)
+    tp = temporal_params(**params)
+    torch.cuda.current_stream(beauty.device).synchronize()
+    t = C.c_float(0.0)
+    _check(lib().gmupt_temporal_denoise_image(handle.h, C.c_void_p(beauty.data_ptr()), C.c_void_p(aov.data_ptr()), C.byref(cam_buffer),
+                                              int(origin[0]), int(origin[1]), W, H, 1 if new_accumulation else 0, C.byref(tp),
+                                              C.c_void_p(out.data_ptr()), out.numel() * 4, C.byref(t)))
+    if ms is not None:
+        ms.append(t.value)
+    return out
+
+
+def temporal_integrate_host(beauty, aov, prev=None, prev_cam=None, prev_origin=(0, 0), threads=16, **params):
+    """gmupt_temporal_integrate_host: the integration step on the CPU, bit for bit the device's.  beauty (H, W, 4) float32, aov (H, W, 16)
+    float32 (or aov_dtype); prev: an (h, w) history_dtype array (or (h, w, 12) float32) rendered with prev_cam at prev_origin, or None.
+    Returns (integrated (H, W, 4) float32, history (H, W) history_dtype) as numpy arrays."""
+    b = beauty.cpu().numpy() if hasattr(beauty, "cpu") else np.asarray(beauty)
+    a = aov.cpu().numpy() if hasattr(aov, "cpu") else np.asarray(aov)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.dtype == aov_dtype:
+        a = a.view(np.float32).reshape(a.shape + (16,))
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if b.ndim != 3 or b.shape[2] != 4 or a.shape != b.shape[:2] + (16,):
+        raise GmuptError("temporal_integrate_host: beauty must be (H, W, 4) and aov (H, W, 16)", ERR_INVALID_ARGUMENT)
+    H, W = b.shape[:2]
+    ph = pw = 0
+    pp = None
+    if prev is not None:
+        pv = np.asarray(prev)
+        if pv.dtype != history_dtype:
+            pv = np.ascontiguousarray(pv, dtype=np.float32).view(history_dtype)[..., 0]
+        pv = np.ascontiguousarray(pv)
+        if pv.ndim != 2:
+            raise GmuptError("temporal_integrate_host: prev must be (h, w) records", ERR_INVALID_ARGUMENT)
+        ph, pw = pv.shape
+        pp = _ptr(pv)
+    out = np.empty_like(b)
+    hist = np.empty((H, W), history_dtype)
+    tp = temporal_params(**params)
+    _check(lib().gmupt_temporal_integrate_host(_ptr(b), _ptr(a), W, H, pp, C.byref(prev_cam) if prev_cam is not None else None,
+                                               int(prev_origin[0]), int(prev_origin[1]), pw, ph, C.byref(tp), _ptr(out), _ptr(hist), int(threads)))
+    return out, hist
 
 
 def sbvh_build(verts, indices, vertex_material=None, params=None):

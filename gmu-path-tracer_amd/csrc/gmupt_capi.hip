@@ -4,6 +4,7 @@
 #include "detmath.hpp"
 #include "pt_shading.hpp"
 #include "pt_denoise.hpp"
+#include "pt_temporal.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
 #include "../host/TextureLoader.hpp"
@@ -59,6 +60,10 @@ void launch_aov_resolve(const RenderParams& p, uint32_t npix, uint32_t samples, 
                         gmupt_aov* out, hipStream_t s);
 void launch_denoise(const float4* beauty, const float4* aov, int W, int H, const DnParams& prm, void* scratch, float4* out, hipStream_t s);
 void denoise_host(const float* beauty, const void* aov, int W, int H, const DnParams& prm, float* out, int threads);
+void launch_temporal(const float4* beauty, const float4* aov, int W, int H, const TpPrev& prev, const TpParams& prm, float4* out, float4* hist,
+                     hipStream_t s);
+void temporal_host(const float* beauty, const void* aov, int W, int H, const void* prev, const gmupt_camera_buffer* prevCam, int px0, int py0,
+                   int pW, int pH, const TpParams& prm, float* out, void* outHist, int threads);
 }
 using namespace gmupt;
 
@@ -238,6 +243,8 @@ struct gmupt_renderer {
     void* dnScratch = nullptr; size_t dnScratchBytes = 0;
     void* dnInput = nullptr; size_t dnInputBytes = 0;
     hipEvent_t dnEv[2] = { nullptr, nullptr };
+    // temporal reuse (gmupt_render_denoised_temporal): advanced by an iteration that clears the frame and by gmupt_resize (host only)
+    uint64_t accumGeneration = 0;
 };
 
 static int dev_alloc(gmupt_renderer* r, void** ptr, size_t bytes, int fill)
@@ -767,7 +774,7 @@ static int run_iteration(gmupt_renderer* r, bool doShade, bool doExtend, bool do
     }
     if (doShade) {
         r->p.groupParity ^= 1u;    // p is a reference to r->p: the launches of this iteration see the flipped half of the group totals
-        if (clearFrame) launch_clear(p, r->stream); else launch_logic(p, r->stream);
+        if (clearFrame) { launch_clear(p, r->stream); r->accumGeneration++; } else launch_logic(p, r->stream);
         if (ev && !extOnly) HIP_TRY(hipEventRecord(ev->e[1], r->stream));
         launch_material(p, clearFrame, r->stream);  // computes its own queue offsets (no scan launch)
         if (ev) HIP_TRY(hipEventRecord(ev->e[2], r->stream));
@@ -847,6 +854,7 @@ extern "C" int gmupt_resize(gmupt_renderer* r, uint32_t width, uint32_t height)
     HIP_TRY(hipStreamSynchronize(r->stream));
     (void)hipFree(oldFb); (void)hipFree(oldHead);
     r->desc.width = width; r->desc.height = height;
+    r->accumGeneration++;
     return GMUPT_OK;
 }
 
@@ -1226,6 +1234,205 @@ extern "C" int gmupt_denoise_host(const float* beauty_rgba, const gmupt_aov* aov
         return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_denoise_host: out of host memory for %ux%u pixels", width, height);
     } catch (const std::exception& e) {
         return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_denoise_host: %s", e.what());
+    }
+    return GMUPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ temporal reuse
+static_assert(sizeof(gmupt_history) == 48 && offsetof(gmupt_history, count) == 12 && offsetof(gmupt_history, normal) == 16 &&
+              offsetof(gmupt_history, material) == 28 && offsetof(gmupt_history, position) == 32 && offsetof(gmupt_history, valid) == 44, "gmupt_history layout");
+static_assert(sizeof(gmupt_temporal_params) == 32 && offsetof(gmupt_temporal_params, history_cap) == 20 && offsetof(gmupt_temporal_params, min_normal_cos) == 24 &&
+              offsetof(gmupt_temporal_params, plane_dist) == 28, "gmupt_temporal_params layout");
+
+// one record set with the camera and rectangle it was made for
+struct TpSlot {
+    void* rec = nullptr; size_t bytes = 0;
+    bool present = false;
+    gmupt_camera_buffer cam{};
+    uint32_t x0 = 0, y0 = 0, W = 0, H = 0;
+};
+
+struct gmupt_temporal {
+    gmupt_renderer* r = nullptr;
+    TpSlot frozen, last;                        // history of earlier accumulations; the records of the latest call
+    void* integrated = nullptr; size_t integratedBytes = 0;   // the integrated image the spatial filter reads (16 bytes per pixel)
+    bool seen = false; uint64_t generation = 0; // the renderer's accumulation generation at the last gmupt_render_denoised_temporal
+    hipEvent_t ev[2] = { nullptr, nullptr };
+};
+
+extern "C" void gmupt_temporal_default_params(gmupt_temporal_params* p)
+{
+    if (!p) return;
+    gmupt_denoise_default_params(&p->spatial);
+    p->history_cap = 32.0f; p->min_normal_cos = 0.9f; p->plane_dist = 0.02f;
+}
+
+static int temporal_params(const char* fn, const gmupt_temporal_params* p, DnParams& dn, TpParams& tp)
+{
+    gmupt_temporal_params d;
+    if (!p) { gmupt_temporal_default_params(&d); p = &d; }
+    int rc = denoise_params(fn, &p->spatial, dn);
+    if (rc != GMUPT_OK) return rc;
+    if (!(std::isfinite(p->history_cap) && p->history_cap >= 0.0f && p->history_cap <= GMUPT_TEMPORAL_MAX_CAP))
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: history_cap = %g (0..%g)", fn, (double)p->history_cap, (double)GMUPT_TEMPORAL_MAX_CAP);
+    if (!(std::isfinite(p->min_normal_cos) && p->min_normal_cos <= 1.0f)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: min_normal_cos = %g (finite, <= 1)", fn, (double)p->min_normal_cos);
+    if (!(std::isfinite(p->plane_dist) && p->plane_dist >= 0.0f)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: plane_dist = %g (finite and >= 0)", fn, (double)p->plane_dist);
+    tp.cap = p->history_cap; tp.minCos = p->min_normal_cos; tp.planeDist = p->plane_dist;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_temporal_create(gmupt_renderer* r, gmupt_temporal** out)
+{
+    if (out) *out = nullptr;
+    if (!r || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_temporal_create: null argument");
+    gmupt_temporal* t = new (std::nothrow) gmupt_temporal();
+    if (!t) return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_temporal_create: out of host memory");
+    t->r = r;
+    *out = t;
+    return GMUPT_OK;
+}
+
+extern "C" void gmupt_temporal_destroy(gmupt_temporal* t)
+{
+    if (!t) return;
+    (void)hipSetDevice(t->r->dev->id);
+    (void)hipStreamSynchronize(t->r->stream);
+    for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
+    for (void* a : { t->frozen.rec, t->last.rec, t->integrated }) if (a) (void)hipFree(a);
+    delete t;
+}
+
+extern "C" int gmupt_temporal_reset(gmupt_temporal* t)
+{
+    if (!t) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_temporal_reset: null handle");
+    t->frozen.present = false; t->last.present = false;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_temporal_denoise_image(gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_camera_buffer* cam,
+                                            uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
+                                            const gmupt_temporal_params* p, float* out_rgba, size_t out_bytes, float* ms)
+{
+    const char* fn = "gmupt_temporal_denoise_image";
+    if (ms) *ms = 0.0f;
+    gmupt_temporal_params d;
+    if (!p) { gmupt_temporal_default_params(&d); p = &d; }
+    DnParams dn; TpParams tp;
+    int rc = denoise_args(fn, beauty_rgba, aov, width, height, &p->spatial, out_rgba, out_bytes, true, dn);   // needs no device: checked first
+    if (rc == GMUPT_OK) rc = temporal_params(fn, p, dn, tp);
+    if (rc != GMUPT_OK) return rc;
+    if (!cam) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null camera", fn);
+    if (!t) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null handle", fn);
+    gmupt_renderer* r = t->r;
+    const size_t n = (size_t)width * height;
+    HIP_TRY(hipSetDevice(r->dev->id));
+    if (new_accumulation) std::swap(t->frozen, t->last);   // the records of the accumulation that ended become the history
+    rc = grow_scratch(r, &t->last.rec, &t->last.bytes, n * sizeof(gmupt_history));
+    if (rc == GMUPT_OK) rc = grow_scratch(r, &t->integrated, &t->integratedBytes, n * 16);
+    if (rc == GMUPT_OK) rc = grow_scratch(r, &r->dnScratch, &r->dnScratchBytes, n * kDnScratchBytes);
+    if (rc != GMUPT_OK) { t->last.present = false; return rc; }
+    if (!t->ev[0]) for (hipEvent_t& e : t->ev) HIP_TRY(hipEventCreate(&e));
+    TpPrev prev{};
+    if (t->frozen.present) {
+        prev.rec = static_cast<const float4*>(t->frozen.rec);
+        prev.x0 = (int)t->frozen.x0; prev.y0 = (int)t->frozen.y0; prev.W = (int)t->frozen.W; prev.H = (int)t->frozen.H;
+        prev.cam = tp_camera(t->frozen.cam);
+    }
+    float4* integrated = static_cast<float4*>(t->integrated);
+    t->last.present = false;                                // until its records are written
+    HIP_TRY(hipEventRecord(t->ev[0], r->stream));
+    launch_temporal(reinterpret_cast<const float4*>(beauty_rgba), reinterpret_cast<const float4*>(aov), (int)width, (int)height, prev, tp, integrated,
+                    static_cast<float4*>(t->last.rec), r->stream);
+    HIP_TRY(hipGetLastError());
+    launch_denoise(integrated, reinterpret_cast<const float4*>(aov), (int)width, (int)height, dn, r->dnScratch, reinterpret_cast<float4*>(out_rgba), r->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(t->ev[1], r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    t->last.present = true; t->last.cam = *cam; t->last.x0 = x0; t->last.y0 = y0; t->last.W = width; t->last.H = height;
+    float e = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&e, t->ev[0], t->ev[1]));
+    if (ms) *ms = e;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_render_denoised_temporal(gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
+                                              float* out_rgba, size_t bytes, gmupt_trace_info* info)
+{
+    const char* fn = "gmupt_render_denoised_temporal";
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!r || !t) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer or handle", fn);
+    if (t->r != r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: the handle belongs to another renderer", fn);
+    const uint32_t W = r->p.fbW, H = r->p.fbH;
+    if (!out_rgba || ((uintptr_t)out_rgba & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned output (16 bytes)", fn);
+    if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu output bytes for %ux%u RGBA32F texels", fn, bytes, W, H);
+    DnParams dn; TpParams tp;
+    int rc = temporal_params(fn, p, dn, tp);
+    if (rc != GMUPT_OK) return rc;
+    // what gmupt_render_aovs would refuse, before the scratch is grown for it
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
+    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "%s: no camera set", fn);
+    if (aov_samples < 1 || aov_samples > GMUPT_AOV_MAX_SAMPLES) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: aov_samples = %u (1..%d)", fn, aov_samples, GMUPT_AOV_MAX_SAMPLES);
+    const uint32_t R = aov_samples == 1 ? 1u : aov_samples * aov_samples + 1u;
+    if ((uint64_t)W * R > GMUPT_AOV_CHUNK_RAYS) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: one row of %u pixels is %u rays at aov_samples = %u (at most 2^21)", fn, W, W * R, aov_samples);
+    rc = query_supported(r, fn);
+    if (rc != GMUPT_OK) return rc;
+    HIP_TRY(hipSetDevice(r->dev->id));
+    rc = grow_scratch(r, &r->dnInput, &r->dnInputBytes, (size_t)W * H * (sizeof(gmupt_aov) + 16));
+    if (rc != GMUPT_OK) return rc;
+    gmupt_aov* aov = static_cast<gmupt_aov*>(r->dnInput);
+    float* beauty = reinterpret_cast<float*>(static_cast<char*>(r->dnInput) + (size_t)W * H * sizeof(gmupt_aov));
+    gmupt_trace_info ai;
+    rc = gmupt_render_aovs(r, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai);
+    if (info) *info = ai;
+    if (rc != GMUPT_OK) return rc;
+    rc = gmupt_copy_framebuffer_to_device(r, beauty, (size_t)W * H * 16);
+    if (rc != GMUPT_OK) return rc;
+    const bool fold = !t->seen || t->generation != r->accumGeneration;
+    const uint32_t x0 = r->p.tileEnabled ? r->p.tileX0 : 0u, y0 = r->p.tileEnabled ? r->p.tileY0 : 0u;
+    float ms = 0.0f;
+    rc = gmupt_temporal_denoise_image(t, beauty, aov, &r->p.cam, x0, y0, W, H, fold ? 1 : 0, p, out_rgba, bytes, &ms);
+    if (info) info->ms = ai.ms + ms;
+    if (rc != GMUPT_OK) return rc;
+    t->seen = true; t->generation = r->accumGeneration;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_temporal_integrate_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height,
+                                             const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
+                                             uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
+                                             float* out_rgba, gmupt_history* out_history, uint32_t threads)
+{
+    const char* fn = "gmupt_temporal_integrate_host";
+    if (!beauty_rgba || !aov || !out_rgba || !out_history) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null beauty, aov or output", fn);
+    if (width == 0 || height == 0 || width > 65535 || height > 65535 || (uint64_t)width * height > (1ull << 28))
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: image of %ux%u (1..65535 each, at most 2^28 pixels)", fn, width, height);
+    if (prev) {
+        if (!prev_cam) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: a previous record set without its camera", fn);
+        if (prev_width == 0 || prev_height == 0 || prev_width > 65535 || prev_height > 65535 || (uint64_t)prev_width * prev_height > (1ull << 28) ||
+            prev_x0 > 65535 || prev_y0 > 65535)
+            return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: previous rectangle of %ux%u at (%u, %u) (1..65535 each, at most 2^28 pixels)", fn, prev_width, prev_height, prev_x0, prev_y0);
+    }
+    {   // the outputs may not overlap each other or any input
+        const size_t n = (size_t)width * height;
+        const uintptr_t o[2] = { (uintptr_t)out_rgba, (uintptr_t)out_history }, on[2] = { n * 16, n * sizeof(gmupt_history) };
+        const uintptr_t i[4] = { (uintptr_t)beauty_rgba, (uintptr_t)aov, (uintptr_t)prev, (uintptr_t)out_history },
+                        in[4] = { n * 16, n * sizeof(gmupt_aov), prev ? (size_t)prev_width * prev_height * sizeof(gmupt_history) : 0, n * sizeof(gmupt_history) };
+        for (int a = 0; a < 2; a++)
+            for (int b = 0; b < (a == 0 ? 4 : 3); b++)
+                if (in[b] && o[a] < i[b] + in[b] && i[b] < o[a] + on[a]) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: an output overlaps another array", fn);
+    }
+    gmupt_temporal_params d;
+    if (!p) { gmupt_temporal_default_params(&d); p = &d; }
+    DnParams dn; TpParams tp;
+    int rc = temporal_params(fn, p, dn, tp);
+    if (rc != GMUPT_OK) return rc;
+    try {
+        temporal_host(beauty_rgba, aov, (int)width, (int)height, prev, prev_cam, (int)prev_x0, (int)prev_y0, (int)prev_width, (int)prev_height, tp,
+                      out_rgba, out_history, (int)std::min(std::max(threads, 1u), 16u));
+    } catch (const std::bad_alloc&) {
+        return fail(GMUPT_ERR_OUT_OF_MEMORY, "%s: out of host memory for %ux%u pixels", fn, width, height);
+    } catch (const std::exception& e) {
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %s", fn, e.what());
     }
     return GMUPT_OK;
 }

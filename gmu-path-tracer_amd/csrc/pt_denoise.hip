@@ -11,9 +11,7 @@
 #include "detmath.hpp"
 #include "pt_denoise.hpp"
 
-#include <algorithm>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 namespace gmupt {
@@ -95,23 +93,6 @@ void launch_denoise(const float4* beauty, const float4* aov, int W, int H, const
 
 // ---- the host filter (gmupt_denoise_host): the same phases over row bands of std::threads.  Every pixel of a phase reads only the
 // previous phase's buffers, so neither the bands nor the thread count can change a bit of the result.
-template <class F> static void dn_bands(int H, int threads, const F& fn)
-{
-    threads = std::max(1, std::min(threads, H));
-    if (threads == 1) { fn(0, H); return; }
-    const int per = (H + threads - 1) / threads;
-    std::vector<std::thread> pool;
-    pool.reserve((size_t)threads);
-    int y0 = 0;
-    try {
-        for (; y0 < H; y0 += per) pool.emplace_back([&fn, y0, per, H]() { fn(y0, std::min(H, y0 + per)); });
-    } catch (...) {
-        // a thread could not be started: the bands not yet handed out run here (the bands never depend on who computes them)
-        for (; y0 < H; y0 += per) fn(y0, std::min(H, y0 + per));
-    }
-    for (std::thread& t : pool) t.join();
-}
-
 // beauty / out: W*H RGBA float texels, aov: W*H 64-byte records; any alignment (copied into aligned buffers)
 void denoise_host(const float* beauty, const void* aov, int W, int H, const DnParams& prm, float* out, int threads)
 {

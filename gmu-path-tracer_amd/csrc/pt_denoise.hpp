@@ -13,6 +13,10 @@
 #include "detmath.hpp"
 #include "../../include/gmupt.h"
 
+#include <algorithm>
+#include <thread>
+#include <vector>
+
 namespace gmupt {
 
 constexpr float kDnInvalid = -1.0f;        // variance word of an invalid pixel
@@ -174,6 +178,25 @@ GM_HD float4 dn_atrous(const float4* col, const DnPlanes& g, int W, int H, int x
     }
     if (!(a.sw > 0.0f)) return col[p];
     return make_float4(a.sr / a.sw, a.sg / a.sw, a.sb / a.sw, a.sv / (a.sw * a.sw));
+}
+
+// the host filters' row bands (gmupt_denoise_host, gmupt_temporal_integrate_host): fn(y0, y1) over bands of H rows on up to `threads`
+// std::threads
+template <class F> void dn_bands(int H, int threads, const F& fn)
+{
+    threads = std::max(1, std::min(threads, H));
+    if (threads == 1) { fn(0, H); return; }
+    const int per = (H + threads - 1) / threads;
+    std::vector<std::thread> pool;
+    pool.reserve((size_t)threads);
+    int y0 = 0;
+    try {
+        for (; y0 < H; y0 += per) pool.emplace_back([&fn, y0, per, H]() { fn(y0, std::min(H, y0 + per)); });
+    } catch (...) {
+        // a thread could not be started: the bands not yet handed out run here (the bands never depend on who computes them)
+        for (; y0 < H; y0 += per) fn(y0, std::min(H, y0 + per));
+    }
+    for (std::thread& t : pool) t.join();
 }
 
 } // namespace gmupt

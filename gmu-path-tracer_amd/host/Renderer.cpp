@@ -139,6 +139,36 @@ std::vector<float> Renderer::denoise(unsigned aovSamples, const gmupt_denoise_pa
 	return out;
 }
 
+gmupt_trace_info Renderer::denoiseTemporal(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_temporal_params* params)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	if (!mTemporal) { gmupt_temporal* t = nullptr; check(gmupt_temporal_create(mRenderer.get(), &t)); mTemporal.reset(t); }
+	gmupt_trace_info info{};
+	check(gmupt_render_denoised_temporal(mRenderer.get(), mTemporal.get(), aovSamples, params, deviceOut, bytes, &info));
+	return info;
+}
+
+std::vector<float> Renderer::denoiseTemporal(unsigned aovSamples, const gmupt_temporal_params* params)
+{
+	const Resolution t = targetSize();
+	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
+	const size_t bytes = out.size() * sizeof(float);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoiseTemporal: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { denoiseTemporal(static_cast<float*>(d), bytes, aovSamples, params); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error("denoiseTemporal: cannot read the image back");
+	return out;
+}
+
+void Renderer::resetHistory()
+{
+	if (mTemporal) check(gmupt_temporal_reset(mTemporal.get()));
+}
+
 void Renderer::bindScene()
 {
 	if (!mSceneBound)

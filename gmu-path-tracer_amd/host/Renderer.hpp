@@ -55,6 +55,13 @@ public:
 	// The first form writes caller-owned device memory (16-byte aligned, bytes >= pixels * 16); the second returns the texels on the host.
 	gmupt_trace_info denoise(float* deviceOut, size_t bytes, unsigned aovSamples = 1, const gmupt_denoise_params* params = nullptr);
 	std::vector<float> denoise(unsigned aovSamples = 1, const gmupt_denoise_params* params = nullptr);
+	// the denoiser with temporal reuse (gmupt_render_denoised_temporal) through this renderer's own history handle, created on first use:
+	// the frame integrated with the reprojected history of earlier accumulations, then filtered; a = the effective sample-count bits.
+	// params == nullptr: gmupt_temporal_default_params.  The two forms as denoise().  resetHistory() drops the history (gmupt_temporal_reset),
+	// e.g. after a light edit, which makes the old history wrong.
+	gmupt_trace_info denoiseTemporal(float* deviceOut, size_t bytes, unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
+	std::vector<float> denoiseTemporal(unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
+	void resetHistory();
 
 private:
 	void createDevice(int hipDevice);
@@ -65,10 +72,12 @@ private:
 
 	struct DeviceDeleter { void operator()(gmupt_device* d) const { gmupt_device_destroy(d); } };
 	struct RendererDeleter { void operator()(gmupt_renderer* r) const { gmupt_renderer_destroy(r); } };
+	struct TemporalDeleter { void operator()(gmupt_temporal* t) const { gmupt_temporal_destroy(t); } };
 
 	void* mHwnd;
 	std::unique_ptr<gmupt_device, DeviceDeleter> mDevice;
 	std::unique_ptr<gmupt_renderer, RendererDeleter> mRenderer; // path state, queues, counters, accumulation target
+	std::unique_ptr<gmupt_temporal, TemporalDeleter> mTemporal; // history of denoiseTemporal (declared after mRenderer: destroyed before it)
 	Scene mScene;
 	Resolution mResolution;
 	RowBand mBand;

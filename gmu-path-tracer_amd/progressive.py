@@ -28,6 +28,7 @@ class ProgressiveSession:
         self.preview_every, self.on_preview = preview_every, on_preview
         self.frames = 0
         self.previews = 0
+        self.temporal = None   # the history handle of denoised_temporal, created on first use
 
     # ---- events (applied before the next frame, like the GUI callbacks of the reference)
     def move_camera(self, mouse_dx=0.0, mouse_dy=0.0, w=False, s=False, a=False, d=False):
@@ -38,6 +39,8 @@ class ProgressiveSession:
         light_buffer.update(lights)
         self.camera.buffer.lightCount = count
         self.camera.reset_accumulation()
+        if self.temporal is not None:
+            self.temporal.reset()                    # the history was lit by the old lights
 
     def resize(self, width, height, rows=None):
         """Resolution switch (Renderer.cpp:146-150,408-413): new accumulation target, camera vectors for the new aspect, restart."""
@@ -69,6 +72,16 @@ class ProgressiveSession:
         array -- rgb denoised, alpha the sample-count bits -- so to_rgba8 and the frame writers take it as they take a preview.  On a
         tile renderer it is this rank's tile, denoised on its own (tile edges are image edges).  params: the gmupt_denoise_params fields."""
         return self.renderer.denoise(aov_samples, **params).cpu().numpy()
+
+    def denoised_temporal(self, aov_samples=1, **params):
+        """A preview that survives camera motion: capi.Renderer.denoise_temporal (gmupt_render_denoised_temporal) with a history handle the
+        session owns, as an (H, W, 4) float32 numpy array -- rgb denoised, alpha the effective sample-count bits.  Pixels the new
+        accumulation has not reached yet show the reprojected history of the frames before the restart.  set_lights drops the history;
+        resize keeps it.  On a tile renderer each rank keeps its own tile's history.  params: the capi.temporal_params fields."""
+        if self.temporal is None:
+            from . import capi
+            self.temporal = capi.Temporal(self.renderer)
+        return self.renderer.denoise_temporal(self.temporal, aov_samples, **params).cpu().numpy()
 
     # ---- frames
     def frame(self, dt=0.0):

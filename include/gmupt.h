@@ -296,7 +296,7 @@ int gmupt_render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_
 int gmupt_aov_ray(const gmupt_camera_buffer* cam, uint32_t x, uint32_t y, uint32_t samples, uint32_t k, gmupt_ray* out);
 
 /* ---- denoiser: edge-avoiding a-trous wavelet filter guided by the AOV buffers (Dammertz et al. 2010, with the variance steering of
- * SVGF, Schied et al. 2017, sections 4.3-4.4, without the temporal part) ----
+ * SVGF, Schied et al. 2017, sections 4.3-4.4; the temporal part is gmupt_temporal_* below) ----
  * Inputs per pixel: the beauty RGBA32F texel of an accumulation target (rgb = running mean of tonemapped samples, a = sample count as
  * uint bits) and its gmupt_aov record.  All arithmetic is binary32 in the order stated here, no contraction; dpow / dexp2 / dsqrt are the
  * deterministic functions of DESIGN.md ("Deterministic math"), normalize3(v) = v * (1 / sqrt((v.x*v.x + v.y*v.y) + v.z*v.z)).
@@ -353,6 +353,92 @@ int gmupt_render_denoised(gmupt_renderer* r, uint32_t aov_samples, const gmupt_d
  * gmupt_denoise_image. */
 int gmupt_denoise_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height, const gmupt_denoise_params* p,
                        float* out_rgba, size_t out_bytes, uint32_t threads);
+
+/* ---- temporal reuse: the denoiser's input integrated with the reprojected history of earlier accumulations (the temporal part of SVGF,
+ * Schied et al. 2017, section 4.1, on the unfiltered colour) ----
+ * History record (gmupt_history, 48 bytes, one per pixel of a rectangle): the INTEGRATED, UNFILTERED colour of the pixel, its effective
+ * sample count, and the guides of the consistency tests.  Filtered colour is never fed back, so blur does not compound from call to call.
+ * All arithmetic is binary32 in the order stated here, no contraction (as the denoiser).
+ *
+ * Projection of a world point X into a previous camera (P, U, Hv, V, ps = its position, upperLeftCorner, horizontal, vertical, pixelSize):
+ *   F = (U + 0.5f*Hv) - 0.5f*V (per component); d = X - P; lambda = dot3(d, F) / dot3(F, F); behind the camera unless lambda > 0;
+ *   r = d / lambda (per component); e = r - U;
+ *   u = (dot3(e, Hv) / dot3(Hv, Hv)) / ps.x, v = (-dot3(e, V) / dot3(V, V)) / ps.y   (whole-frame pixel coordinates, centres at integers).
+ *   This inverts the primary ray normalize(U + Hv*(px*ps.x) - V*(py*ps.y)) of newPath.hlsl:36-39 / gmupt_camera_pick_ray; it needs
+ *   Hv, V and F mutually orthogonal, which the host camera guarantees (Camera.cpp:92-94 builds them from one orthonormal frame).
+ * Integration of pixel p of the current rectangle (W x H; beauty texel: rgb B, sample count n = alpha bits, nf = (float)n; record aov):
+ *   Surface pixel: aov.triangle != -1, aov.light == 0, sqrt(dot3(aov.normal, aov.normal)) > 0 (the denoiser's test without n > 0);
+ *     n_p = normalize3(aov.normal), x_p = aov.position, z_p = aov.depth.
+ *   Any other pixel: the integrated texel is the beauty texel bit for bit; its new record is all zero (valid = 0).
+ *   Surface pixel: (u, v) = the projection of x_p into the previous camera, minus the previous rectangle's origin; fu = floorf(u),
+ *     fv = floorf(v), fx = u - fu, fy = v - fv; taps k = 0..3 at (fu, fv), (fu+1, fv), (fu, fv+1), (fu+1, fv+1) with weights
+ *     (1-fx)*(1-fy), fx*(1-fy), (1-fx)*fy, fx*fy.  Tap q counts when it lies inside the previous rectangle, its record has valid == 1 and
+ *     count > 0, material_q == aov.material, dot3(n_p, n_q) >= min_normal_cos and |dot3(n_p, x_q - x_p)| <= plane_dist * z_p.
+ *     Over the counted taps in k order, sums from 0.0f: Sw = sum w, Sc = sum w*color_q (per channel), Sn = sum w*count_q;
+ *     Hc = Sc / Sw, N_h = min(history_cap, Sn / Sw).  N_h = 0 when the point is behind the previous camera, when Sw is not > 0, or
+ *     without a previous record set.
+ *     N_h == 0: the integrated texel is the beauty texel bit for bit;
+ *     n == 0:   rgb = Hc, alpha = the bits of (uint32_t)ceilf(N_h);
+ *     else:     rgb = ((N_h*Hc) + (nf*B)) / (N_h + nf) per channel, alpha = the bits of n + (uint32_t)ceilf(N_h).
+ *     New record: color = the integrated rgb, count = N_h + nf (nf when N_h == 0), normal = n_p, material = aov.material,
+ *     position = x_p, valid = (count > 0).
+ * Output = gmupt_denoise_image of the integrated image with the spatial parameters.  Hence, bit for bit: (a) without history (first call,
+ *   after gmupt_temporal_reset, history_cap = 0) the output is gmupt_denoise_image(beauty, aov); (b) always, the output is
+ *   gmupt_denoise_image(integrated, aov) with the integrated image of gmupt_temporal_integrate_host.  The output alpha is therefore the
+ *   effective count word, not the frame's sample count (progressive.to_rgba8 and the PNG / PFM writers ignore alpha).
+ * Accumulation epochs (no double counting): while the camera stands still the beauty keeps accumulating, so the last call's records
+ *   are already contained in the frame.  A handle keeps two record sets, each with its camera and rectangle: FROZEN, the history of
+ *   earlier accumulations, and LAST, the records of the latest call.  A call with new_accumulation != 0 first moves LAST into FROZEN (a
+ *   pointer swap); every call integrates against FROZEN and then replaces LAST with its own records.  The samples drawn between the last
+ *   call of an accumulation and its restart are not in the history.  The previous rectangle may have any size and origin (reprojection
+ *   needs no matching size), so a resize keeps the history.
+ * Parameters: the spatial ones as gmupt_denoise_params; history_cap in [0, 65536]; min_normal_cos finite and <= 1; plane_dist finite
+ *   and >= 0; else GMUPT_ERR_INVALID_ARGUMENT. */
+typedef struct {
+    float color[3];    float count;        /* integrated unfiltered rgb; effective sample count */
+    float normal[3];   uint32_t material;  /* normalised guide normal; aov.material */
+    float position[3]; uint32_t valid;     /* aov.position; 1 when count > 0, else 0 */
+} gmupt_history;       /* 48 bytes */
+typedef struct {
+    gmupt_denoise_params spatial;   /* the filter run on the integrated image; default gmupt_denoise_default_params */
+    float history_cap;              /* most samples the history may stand for; default 32 */
+    float min_normal_cos;           /* tap test: dot3(n_p, n_q) >= this; default 0.9 */
+    float plane_dist;               /* tap test: distance from p's tangent plane, relative to p's depth; default 0.02 */
+} gmupt_temporal_params;            /* 32 bytes */
+#define GMUPT_TEMPORAL_MAX_CAP 65536.0f
+void gmupt_temporal_default_params(gmupt_temporal_params* p);
+/* A history handle of a renderer: its device and stream, its spatial scratch, and two record sets allocated on first use and grown for
+ * larger images.  It must not outlive its renderer.  gmupt_temporal_reset drops both record sets (the next output is consequence (a)). */
+typedef struct gmupt_temporal gmupt_temporal;
+int gmupt_temporal_create(gmupt_renderer* r, gmupt_temporal** out);
+void gmupt_temporal_destroy(gmupt_temporal* t);
+int gmupt_temporal_reset(gmupt_temporal* t);
+/* beauty_rgba, aov, out_rgba: caller-owned DEVICE memory as for gmupt_denoise_image (any size, e.g. a gathered whole frame; out must not
+ * overlap beauty).  cam: the camera the image was rendered with (host memory); (x0, y0): the image's origin in that camera's whole frame.
+ * Both are stored with the new records.  Enqueued on the renderer's stream: k_tp_integrate, then the denoiser's launches, no host
+ * synchronisation between them; then synchronises.  ms (may be NULL): device time of the whole call.  p may be NULL (the defaults).
+ * Errors: those of gmupt_denoise_image, a NULL handle or camera, bad parameters (GMUPT_ERR_INVALID_ARGUMENT). */
+int gmupt_temporal_denoise_image(gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_camera_buffer* cam,
+                                 uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
+                                 const gmupt_temporal_params* p, float* out_rgba, size_t out_bytes, float* ms /* may be NULL */);
+/* gmupt_render_denoised with temporal reuse, on the renderer t was created for: gmupt_render_aovs(aov_samples) and a copy of the
+ * framebuffer into internal scratch, then gmupt_temporal_denoise_image with the renderer's current camera and rectangle (the tile in tile
+ * mode).  new_accumulation is set from the renderer's accumulation generation, which an iteration that clears the frame
+ * (iterationCounter == 0) and gmupt_resize advance: the first call after such an event folds.  That generation is host bookkeeping; the
+ * frame, path state, queues, counters and statistics are not touched.  Errors and info as gmupt_render_denoised; t of another renderer
+ * is GMUPT_ERR_INVALID_ARGUMENT. */
+int gmupt_render_denoised_temporal(gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
+                                   float* out_rgba, size_t bytes, gmupt_trace_info* info /* may be NULL */);
+/* The integration step on host arrays (the same binary32 sequence as k_tp_integrate, bit for bit), in row bands on up to `threads`
+ * std::threads (0 -> 1, at most 16; the result does not depend on the count).  beauty_rgba / aov: width * height texels / records of the
+ * current image.  prev: prev_width * prev_height records with origin (prev_x0, prev_y0) in prev_cam's whole frame, or NULL (no history;
+ * prev_cam may then be NULL too).  Outputs: out_rgba (width * height RGBA32F, the integrated image) and out_history (width * height
+ * records).  Together with gmupt_denoise_host it is the reference of gmupt_temporal_denoise_image.  Errors: NULL or overlapping
+ * arrays, an empty image, more than 2^28 pixels, bad parameters (GMUPT_ERR_INVALID_ARGUMENT). */
+int gmupt_temporal_integrate_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height,
+                                  const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
+                                  uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
+                                  float* out_rgba, gmupt_history* out_history, uint32_t threads);
 
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
