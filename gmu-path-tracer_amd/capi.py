@@ -133,6 +133,15 @@ history_dtype = np.dtype([("color", "<f4", 3), ("count", "<f4"), ("normal", "<f4
 assert history_dtype.itemsize == 48
 
 
+class RefitInfo(C.Structure):
+    """gmupt_refit_info: 24 bytes."""
+    _fields_ = [("rebuilt", C.c_uint32), ("reason", C.c_uint32), ("levels", C.c_uint32), ("opened_nodes", C.c_uint32), ("ms", C.c_double)]
+
+
+REFIT_FLAT_CHILD, REFIT_VARIANTS_BUILD = 1, 2
+assert C.sizeof(RefitInfo) == 24
+
+
 class GmuptError(RuntimeError):
     def __init__(self, msg, code=0):
         super().__init__(msg)
@@ -148,6 +157,7 @@ SYMBOLS = {
     "gmupt_device_count": (C.c_int, []),
     "gmupt_buffer_create": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
     "gmupt_buffer_update": (C.c_int, [_P, _P, C.c_size_t]),
+    "gmupt_buffer_read": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_buffer_destroy": (None, [_P]),
     "gmupt_buffer_size": (C.c_size_t, [_P]),
     "gmupt_texture_array_create": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
@@ -188,6 +198,8 @@ SYMBOLS = {
     "gmupt_render_denoised_temporal": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(TemporalParams), _P, C.c_size_t, C.POINTER(TraceInfo)]),
     "gmupt_temporal_integrate_host": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(CameraBuffer), C.c_uint32, C.c_uint32,
                                                 C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _P, _P, C.c_uint32]),
+    "gmupt_bvh_refit_host": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32]),
+    "gmupt_renderer_refit": (C.c_int, [_P, C.POINTER(RefitInfo)]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -308,6 +320,14 @@ class Buffer:
     def update(self, array):
         array = np.ascontiguousarray(array)
         _check(lib().gmupt_buffer_update(self.h, _ptr(array), array.nbytes))
+
+    def read(self, dtype=np.uint8):
+        """The buffer's bytes as a new array of `dtype` (gmupt_buffer_read: synchronous)."""
+        dtype = np.dtype(dtype)
+        nbytes = int(lib().gmupt_buffer_size(self.h))
+        out = np.empty(nbytes // dtype.itemsize, dtype=dtype)
+        _check(lib().gmupt_buffer_read(self.h, _ptr(out), out.nbytes))
+        return out
 
     def close(self):
         if self.h:
@@ -446,6 +466,12 @@ class Renderer:
         self._scene = sb  # keep the buffers alive
         _check(lib().gmupt_renderer_bind_scene(self.h, *[b.h for b in sb.all()]))
         _check(lib().gmupt_renderer_bind_textures(self.h, *[(t.h if t is not None else None) for t in sb.textures]))
+
+    def refit(self):
+        """gmupt_renderer_refit after the vertex buffer was updated: the info fields as a dict."""
+        info = RefitInfo()
+        _check(lib().gmupt_renderer_refit(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in RefitInfo._fields_}
 
     def set_camera(self, cam_buffer):
         _check(lib().gmupt_set_camera(self.h, C.byref(cam_buffer)))
@@ -802,6 +828,15 @@ def temporal_integrate_host(beauty, aov, prev=None, prev_cam=None, prev_origin=(
     _check(lib().gmupt_temporal_integrate_host(_ptr(b), _ptr(a), W, H, pp, C.byref(prev_cam) if prev_cam is not None else None,
                                                int(prev_origin[0]), int(prev_origin[1]), pw, ph, C.byref(tp), _ptr(out), _ptr(hist), int(threads)))
     return out, hist
+
+
+def bvh_refit_host(nodes, tris, verts, threads=16):
+    """gmupt_bvh_refit_host on a copy: the nodes with the boxes of the given vertices, topology untouched."""
+    out = np.array(nodes, dtype=bvh_node_dtype, copy=True)
+    tris = np.ascontiguousarray(tris, dtype=triangle_dtype)
+    verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    _check(lib().gmupt_bvh_refit_host(_ptr(out), out.shape[0], _ptr(tris), tris.shape[0], _ptr(verts), verts.shape[0], threads))
+    return out
 
 
 def sbvh_build(verts, indices, vertex_material=None, params=None):

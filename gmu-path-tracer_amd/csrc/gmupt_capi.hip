@@ -5,6 +5,7 @@
 #include "pt_shading.hpp"
 #include "pt_denoise.hpp"
 #include "pt_temporal.hpp"
+#include "pt_refit.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
 #include "../host/TextureLoader.hpp"
@@ -64,6 +65,10 @@ void launch_temporal(const float4* beauty, const float4* aov, int W, int H, cons
                      hipStream_t s);
 void temporal_host(const float* beauty, const void* aov, int W, int H, const void* prev, const gmupt_camera_buffer* prevCam, int px0, int py0,
                    int pW, int pH, const TpParams& prm, float* out, void* outHist, int threads);
+void launch_refit_check(const RfArgs& a, hipStream_t s);
+uint32_t launch_refit_boxes(const RfArgs& a, const std::vector<uint32_t>& levelOff, hipStream_t s);
+void launch_refit_tables(const RfArgs& a, hipStream_t s);
+void refit_host(gmupt_bvh_node* nodes, size_t N, const gmupt_triangle* tris, const float* verts, int threads);
 }
 using namespace gmupt;
 
@@ -203,6 +208,16 @@ extern "C" int gmupt_buffer_update(gmupt_buffer* buf, const void* data, size_t b
     return GMUPT_OK;
 }
 
+extern "C" int gmupt_buffer_read(const gmupt_buffer* buf, void* dst, size_t bytes)
+{
+    if (!buf || (!dst && bytes)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_buffer_read: null argument");
+    if (bytes > buf->bytes) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_buffer_read: %zu bytes from a %zu-byte buffer", bytes, buf->bytes);
+    HIP_TRY(hipSetDevice(buf->dev->id));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(dst, buf->dptr, bytes, hipMemcpyDeviceToHost));
+    return GMUPT_OK;
+}
+
 extern "C" void gmupt_buffer_destroy(gmupt_buffer* buf)
 {
     if (!buf) return;
@@ -245,6 +260,13 @@ struct gmupt_renderer {
     hipEvent_t dnEv[2] = { nullptr, nullptr };
     // temporal reuse (gmupt_render_denoised_temporal): advanced by an iteration that clears the frame and by gmupt_resize (host only)
     uint64_t accumGeneration = 0;
+    // refit (gmupt_renderer_refit): the buffers of the binding with their element counts, and what build_traversal_copy knows about the
+    // topology of its tables -- host vectors, uploaded into one allocation (rfDev) by the first refit after a bind
+    const gmupt_buffer* boundNodes = nullptr; const gmupt_buffer* boundTris = nullptr; const gmupt_buffer* boundVerts = nullptr;
+    size_t boundElems[3] = { 0, 0, 0 };
+    std::vector<uint32_t> rfLevelNodes, rfLevelOff, rfNodeMap, rfWideMap, rfOpened;
+    void* rfDev = nullptr;
+    hipEvent_t rfEv[2] = { nullptr, nullptr };
 };
 
 static int dev_alloc(gmupt_renderer* r, void** ptr, size_t bytes, int fill)
@@ -276,6 +298,8 @@ extern "C" void gmupt_renderer_destroy(gmupt_renderer* r)
     for (auto& se : r->evPool) for (auto& e : se.e) (void)hipEventDestroy(e);
     for (hipEvent_t e : r->queryEv) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : r->dnEv) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : r->rfEv) if (e) (void)hipEventDestroy(e);
+    if (r->rfDev) (void)hipFree(r->rfDev);
     for (void* a : r->allocs) (void)hipFree(a);
     if (r->dnScratch) (void)hipFree(r->dnScratch);
     if (r->dnInput) (void)hipFree(r->dnInput);
@@ -563,6 +587,7 @@ static int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, c
     }
 
     std::vector<WNode> wide;
+    std::vector<uint32_t> rfOpened, rfWideMap;   // refit: the nodes the collapse opened; 4 * wide node + slot -> reference node
     uint32_t wideTop = 0, wideBound = 0;
     bool contained = true;
     for (size_t i = 0; i < N && contained && wantWide; i++) {
@@ -590,6 +615,7 @@ static int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, c
         std::vector<Slots> created;                    // creation order: parents before children
         std::vector<int32_t> createdOf(N, -1);
         std::vector<int32_t> todo{ 0 };
+        rfOpened.clear();
         while (!todo.empty()) {
             const int32_t v = todo.back(); todo.pop_back();
             Slots w; w.bin = v; w.n = 2; w.s[0] = nodes[(size_t)v].left; w.s[1] = nodes[(size_t)v].right; w.s[2] = w.s[3] = -1;
@@ -598,6 +624,7 @@ static int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, c
                 for (int k = 0; k < w.n; k++) if (!nodes[(size_t)w.s[k]].isLeaf && opens(w.s[k]) && (best < 0 || area(w.s[k]) > area(w.s[best]))) best = k;
                 if (best < 0) break;
                 const int32_t c = w.s[best];
+                rfOpened.push_back((uint32_t)c);
                 for (int k = w.n; k > best + 1; k--) w.s[k] = w.s[k - 1];
                 w.s[best] = nodes[(size_t)c].left; w.s[best + 1] = nodes[(size_t)c].right; w.n++;
             }
@@ -625,6 +652,7 @@ static int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, c
         }
         for (size_t c = 0; c < W; c++) if (number[c] < 0) number[c] = nextW++;
         wide.resize(W);
+        rfWideMap.assign(4 * W, kRfNone);
         const float qnan = std::numeric_limits<float>::quiet_NaN();
         for (size_t c = 0; c < W; c++) {
             const Slots& w = created[c];
@@ -634,6 +662,7 @@ static int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, c
                     const gmupt_bvh_node& b = nodes[(size_t)w.s[k]];
                     for (int a = 0; a < 3; a++) { o.p[a][k] = b.min[a]; o.p[5 - a][k] = b.max[a]; }   // rows: min x, y, z, max z, y, x
                     o.link[k] = b.isLeaf ? ~leafPair[(size_t)w.s[k]] : number[(size_t)createdOf[(size_t)w.s[k]]];
+                    rfWideMap[4 * (size_t)number[c] + (size_t)k] = (uint32_t)w.s[k];
                 } else {
                     for (int a = 0; a < 6; a++) o.p[a][k] = qnan;      // never hit
                     o.link[k] = (int32_t)0x80000000;
@@ -693,6 +722,115 @@ static int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, c
     t.nodes = (const Node64*)r->travNodes; t.tris = (const Tri48*)r->travTris;
     t.rootDesc = nodes[0].isLeaf ? ~(nodes[0].right > nodes[0].left ? nodes[0].left : (int32_t)R) : innerIndex[0];
     for (int k = 0; k < 3; k++) { t.rootMin[k] = nodes[0].min[k]; t.rootMax[k] = nodes[0].max[k]; }
+
+    // what a refit needs to rewrite these tables in place (host vectors; the first gmupt_renderer_refit uploads them)
+    if (r->rfDev) { HIP_TRY(hipFree(r->rfDev)); r->rfDev = nullptr; }
+    r->rfNodeMap.assign(packed.size(), kRfNone);
+    for (size_t i = 0; i < N; i++) if (!nodes[i].isLeaf) r->rfNodeMap[(size_t)innerIndex[i]] = (uint32_t)i;
+    {   // inner nodes by height (a leaf has height 0), lowest first: every node comes after its children, whatever the shape of the tree
+        std::vector<int32_t>& height = depth;                          // (the depths are not needed any more)
+        int32_t top = 0;
+        for (size_t i = N; i-- > 0;) { height[i] = nodes[i].isLeaf ? 0 : 1 + std::max(height[(size_t)nodes[i].left], height[(size_t)nodes[i].right]); top = std::max(top, height[i]); }
+        r->rfLevelOff.assign((size_t)top + 1, 0);
+        for (size_t i = 0; i < N; i++) if (height[i] > 0) r->rfLevelOff[(size_t)height[i]]++;
+        for (size_t h = 1; h <= (size_t)top; h++) r->rfLevelOff[h] += r->rfLevelOff[h - 1];    // rfLevelOff[h] = end of height h
+        r->rfLevelNodes.resize(r->rfLevelOff[(size_t)top]);
+        std::vector<uint32_t> at(r->rfLevelOff.begin(), r->rfLevelOff.end());
+        for (size_t i = N; i-- > 0;) if (height[i] > 0) r->rfLevelNodes[--at[(size_t)height[i]]] = (uint32_t)i;
+    }
+    if (wide.empty()) { rfWideMap.clear(); rfOpened.clear(); }
+    r->rfWideMap.swap(rfWideMap); r->rfOpened.swap(rfOpened);
+    r->boundNodes = nodesB; r->boundTris = trisB; r->boundVerts = vertsB;
+    r->boundElems[0] = N; r->boundElems[1] = R; r->boundElems[2] = V;
+    return GMUPT_OK;
+}
+
+static_assert(sizeof(gmupt_refit_info) == 24 && offsetof(gmupt_refit_info, ms) == 16, "gmupt_refit_info layout");
+
+extern "C" int gmupt_renderer_refit(gmupt_renderer* r, gmupt_refit_info* info)
+{
+    if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_renderer_refit: null renderer");
+    if (info) *info = gmupt_refit_info{};
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_renderer_refit: no scene bound");
+    if (r->boundNodes->elems != r->boundElems[0] || r->boundTris->elems != r->boundElems[1] || r->boundVerts->elems != r->boundElems[2])
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_renderer_refit: the bound buffers hold (%zu, %zu, %zu) nodes / triangle records / vertices, at bind time (%zu, %zu, %zu)",
+                    r->boundNodes->elems, r->boundTris->elems, r->boundVerts->elems, r->boundElems[0], r->boundElems[1], r->boundElems[2]);
+    HIP_TRY(hipSetDevice(r->dev->id));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    // one allocation: 16 words of flags and results, then the maps (each starts at a multiple of 16 bytes)
+    const std::vector<uint32_t>* maps[4] = { &r->rfLevelNodes, &r->rfNodeMap, &r->rfWideMap, &r->rfOpened };
+    size_t off[4], words = 16;
+    for (int k = 0; k < 4; k++) { off[k] = words; words += (maps[k]->size() + 3) & ~(size_t)3; }
+    if (!r->rfDev) {
+        HIP_TRY(hipMalloc(&r->rfDev, words * 4));
+        for (int k = 0; k < 4; k++)
+            if (!maps[k]->empty()) HIP_TRY(hipMemcpy((uint32_t*)r->rfDev + off[k], maps[k]->data(), maps[k]->size() * 4, hipMemcpyHostToDevice));
+    }
+    for (hipEvent_t& e : r->rfEv) if (!e) HIP_TRY(hipEventCreate(&e));
+    uint32_t* dev = (uint32_t*)r->rfDev;
+    const TravScene& t = r->p.trav;
+    RfArgs a{};
+    a.nodes = (DNode*)r->boundNodes->dptr; a.tris = (const gmupt_triangle*)r->boundTris->dptr; a.verts = (const float*)r->boundVerts->dptr;
+    a.numNodes = (uint32_t)r->boundElems[0]; a.numTris = (uint32_t)r->boundElems[1]; a.numVerts = (uint32_t)r->boundElems[2];
+    a.levelNodes = dev + off[0];
+    a.ttris = (Tri48*)r->travTris; a.pairs = (TriPair*)r->travPairs; a.pairRef = t.pairRef; a.numPairs = t.numPairs;
+    a.tnodes = (Node64*)r->travNodes; a.nodeMap = dev + off[1]; a.numPacked = (uint32_t)r->rfNodeMap.size();
+    a.wnodes = (WNode*)r->travWide; a.wideMap = dev + off[2]; a.wideCount = r->travWide ? t.wideCount : 0u;
+    a.opened = dev + off[3]; a.numOpened = r->travWide ? (uint32_t)r->rfOpened.size() : 0u;
+    a.flags = dev;
+
+    uint32_t back[16] = { 0 };
+    HIP_TRY(hipMemsetAsync(dev, 0, 64, r->stream));
+    launch_refit_check(a, r->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(back, dev, 4, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (back[0] & kRfFlagBadIndex) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_renderer_refit: a triangle record references a vertex outside the vertex buffer (the triangle records changed since bind)");
+    if (back[0] & kRfFlagNonFinite) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_renderer_refit: a vertex used by a triangle record is not finite; nothing was written");
+
+    uint32_t reason = 0;
+#ifdef GMUPT_VARIANTS
+    reason = GMUPT_REFIT_VARIANTS_BUILD;
+#endif
+    HIP_TRY(hipEventRecord(r->rfEv[0], r->stream));
+    const uint32_t levels = launch_refit_boxes(a, r->rfLevelOff, r->stream);
+    if (!reason) launch_refit_tables(a, r->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dev + 4, a.nodes, 32, hipMemcpyDeviceToDevice, r->stream));      // the root box next to the flags
+    HIP_TRY(hipEventRecord(r->rfEv[1], r->stream));
+    HIP_TRY(hipMemcpyAsync(back, dev, 64, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, r->rfEv[0], r->rfEv[1]));
+    if (back[1]) reason |= GMUPT_REFIT_FLAT_CHILD;
+    const uint32_t openedNodes = a.numOpened;
+    if (reason) {
+        int rc = build_traversal_copy(r, r->boundNodes, r->boundTris, r->boundVerts);
+        if (rc != GMUPT_OK) return rc;
+    } else {
+        for (int k = 0; k < 3; k++) { std::memcpy(&r->p.trav.rootMin[k], &back[4 + k], 4); std::memcpy(&r->p.trav.rootMax[k], &back[8 + k], 4); }
+    }
+    if (info) { info->rebuilt = reason ? 1u : 0u; info->reason = reason; info->levels = levels; info->opened_nodes = openedNodes; info->ms = (double)ms; }
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_bvh_refit_host(gmupt_bvh_node* nodes, uint32_t num_nodes, const gmupt_triangle* tris, uint32_t num_tris,
+                                    const float* verts, uint32_t num_verts, uint32_t threads)
+{
+    if (!nodes || num_nodes == 0 || (!tris && num_tris) || (!verts && num_verts)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_bvh_refit_host: null or empty array");
+    const size_t N = num_nodes, R = num_tris, V = num_verts;
+    for (size_t i = 0; i < N; i++) {
+        const gmupt_bvh_node& n = nodes[i];
+        if (n.isLeaf) {
+            if (n.left < 0 || n.right < n.left || (size_t)n.right > R) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_bvh_refit_host: leaf %zu has triangle range [%d, %d) outside [0, %zu)", i, n.left, n.right, R);
+        } else if (n.left <= (int32_t)i || n.right <= (int32_t)i || (size_t)n.left >= N || (size_t)n.right >= N) {
+            return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_bvh_refit_host: inner node %zu has children (%d, %d) outside (%zu, %zu)", i, n.left, n.right, i, N);
+        }
+    }
+    for (size_t i = 0; i < R; i++)
+        for (int k = 0; k < 3; k++)
+            if (tris[i].v[k] < 0 || (size_t)tris[i].v[k] >= V) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_bvh_refit_host: triangle record %zu references vertex %d of %zu", i, tris[i].v[k], V);
+    refit_host(nodes, N, tris, verts, (int)std::min(std::max(threads, 1u), 16u));
     return GMUPT_OK;
 }
 

@@ -164,6 +164,16 @@ std::vector<float> Renderer::denoiseTemporal(unsigned aovSamples, const gmupt_te
 	return out;
 }
 
+gmupt_refit_info Renderer::refitScene()
+{
+	gmupt_refit_info info{};
+	bindScene(); // (the scene is bound on first use: a refit before the first frame starts from the loaded tree)
+	check(gmupt_renderer_refit(mRenderer.get(), &info));
+	mScene.mCamera.getBuffer()->iterationCounter = -1; // paths in flight carry hits of the old geometry
+	resetHistory();
+	return info;
+}
+
 void Renderer::resetHistory()
 {
 	if (mTemporal) check(gmupt_temporal_reset(mTemporal.get()));

@@ -62,6 +62,10 @@ public:
 	gmupt_trace_info denoiseTemporal(float* deviceOut, size_t bytes, unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
 	std::vector<float> denoiseTemporal(unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
 	void resetHistory();
+	// after Scene::setVertices: the tree's boxes and this renderer's traversal tables recomputed on the GPU for the moved vertices
+	// (gmupt_renderer_refit; the topology of the tree stays), the accumulation restarted, the temporal history dropped.  Throws like the
+	// other wrappers.
+	gmupt_refit_info refitScene();
 
 private:
 	void createDevice(int hipDevice);

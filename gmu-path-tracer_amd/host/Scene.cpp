@@ -122,6 +122,22 @@ void Scene::createLights(const std::vector<Light>& lights)
 	mLightBuffer.reset(b);
 }
 
+void Scene::setVertices(const std::vector<float>& xyz, const std::vector<float>* normals)
+{
+	if (xyz.size() != mScene.vertices.size()) throw std::runtime_error("setVertices: " + std::to_string(xyz.size() / 3) + " vertices for a mesh of " + std::to_string(mScene.numVertices()));
+	if (normals && normals->size() != xyz.size()) throw std::runtime_error("setVertices: one normal per vertex");
+	check(gmupt_buffer_update(mVertexBuffer.get(), xyz.data(), xyz.size() * sizeof(float)));
+	mScene.vertices = xyz;
+	if (normals)
+	{
+		std::vector<gmupt_tri_props> props(mScene.numVertices());
+		check(gmupt_buffer_read(mTriangleProperties.get(), props.data(), props.size() * sizeof(gmupt_tri_props)));
+		for (size_t i = 0; i < props.size(); ++i) for (int k = 0; k < 3; ++k) props[i].normal[k] = (*normals)[3 * i + k];
+		check(gmupt_buffer_update(mTriangleProperties.get(), props.data(), props.size() * sizeof(gmupt_tri_props)));
+		mScene.normals = *normals;
+	}
+}
+
 void Scene::setLights(const std::vector<Light>& lights)
 {
 	if (lights.size() > MAX_LIGHTS) throw std::runtime_error("More than 128 lights");

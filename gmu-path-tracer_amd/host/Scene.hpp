@@ -62,6 +62,10 @@ public:
 	void update(float dt);
 	size_t lightCount() const { return mLightCount; }
 	void setLights(const std::vector<Light>& lights); // GUI light editor: re-upload (Source/GUI.cpp:125-130)
+	// moved geometry (an extension; the reference has none): new positions for ALL vertices (3 floats each, the count of the loaded mesh) and,
+	// optionally, new normals -- into the mesh data, the vertex buffer and the normals inside the property buffer.  The tree keeps its
+	// topology: call Renderer::refitScene() afterwards.  Throws std::runtime_error on a wrong count or a failed upload.
+	void setVertices(const std::vector<float>& xyz, const std::vector<float>* normals = nullptr);
 
 private:
 	void loadScene(const std::string& path);

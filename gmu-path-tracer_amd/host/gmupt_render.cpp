@@ -14,6 +14,9 @@
 //                [--denoise PREFIX [--aov-samples S]]     after the frames: the frame through the a-trous denoiser (gmupt_render_denoised, AOVs at
 //                                                         S samples per axis): PREFIX.pfm ("PF") and PREFIX.png (the capture's truncation, alpha 255)
 //                                                         (single process only)
+//                [--vertices FILE]                        before the frames: moved positions for all vertices of the scene (raw little-endian float32,
+//                                                         3 per vertex) through Scene::setVertices + Renderer::refitScene; one JSON line with the
+//                                                         refit info; not with --ranks
 //                [--help]                                 this list
 #include <chrono>
 #include <cstddef>
@@ -77,6 +80,7 @@ int main(int argc, char** argv)
 	unsigned ranks = 1, rank = 0; int device = -1;
 	std::string paramsOnly, rendezvous;
 	bool doPick = false; float pickX = 0.f, pickY = 0.f;
+	std::string verticesFile;
 	std::string aovPrefix; unsigned aovSamples = 1;
 	std::string denoisePrefix;
 	for (int i = 1; i < argc; i++) {
@@ -103,6 +107,7 @@ int main(int argc, char** argv)
 		else if (a == "--aov") aovPrefix = next();
 		else if (a == "--aov-samples") aovSamples = std::strtoul(next(), nullptr, 10);
 		else if (a == "--denoise") denoisePrefix = next();
+		else if (a == "--vertices") verticesFile = next();
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -111,6 +116,7 @@ int main(int argc, char** argv)
 			            "             [--pick X,Y]   after the frames: triangle / material / light sphere under whole-frame pixel (X, Y), one JSON line\n"
 			            "             [--aov PREFIX [--aov-samples S]]   after the frames: the AOV buffers of the camera, S = 1..8 samples per axis (default 1):\n"
 			            "                            PREFIX_albedo.pfm, PREFIX_normal.pfm (PF), PREFIX_depth.pfm (Pf), PREFIX.aov (64-byte gmupt_aov records); not with --ranks\n"
+			            "             [--vertices FILE]   before the frames: moved positions of all vertices (raw float32 xyz), refitted on the GPU; not with --ranks\n"
 			            "             [--denoise PREFIX [--aov-samples S]]   after the frames: the frame through the a-trous denoiser guided by the AOV buffers\n"
 			            "                            (S samples per axis): PREFIX.pfm (PF) and PREFIX.png (8-bit, truncated like --capture); not with --ranks\n");
 			return 0;
@@ -182,6 +188,8 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--aov renders the AOV buffers of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
 		if (!denoisePrefix.empty() && ranks > 1)
 			throw std::invalid_argument("--denoise filters the frame of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
+		if (!verticesFile.empty() && ranks > 1)
+			throw std::invalid_argument("--vertices moves the geometry of a single process: it cannot be combined with --ranks N > 1");
 		if (ranks > 1 || !rendezvous.empty())
 		{
 			// one process per GPU: row band `rank` of `ranks`, the camera of the whole frame; the bands meet on rank 0 (RCCL send / receive)
@@ -209,6 +217,17 @@ int main(int argc, char** argv)
 			return 0;
 		}
 		Renderer renderer(nullptr, { w, h }, scene, 0, pool, live);
+		if (!verticesFile.empty()) {
+			std::FILE* f = std::fopen(verticesFile.c_str(), "rb");
+			if (!f) throw std::runtime_error("cannot read " + verticesFile);
+			std::vector<float> xyz;
+			float chunk[3072];
+			for (size_t n; (n = std::fread(chunk, sizeof(float), 3072, f)) > 0;) xyz.insert(xyz.end(), chunk, chunk + n);
+			std::fclose(f);
+			renderer.scene().setVertices(xyz);
+			const gmupt_refit_info info = renderer.refitScene();
+			std::printf("{\"refit\": {\"rebuilt\": %u, \"reason\": %u, \"levels\": %u, \"opened_nodes\": %u, \"ms\": %.6g}}\n", info.rebuilt, info.reason, info.levels, info.opened_nodes, info.ms);
+		}
 		for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
 		if (capture) { renderer.requestCapture(); renderer.update(0.f); std::printf("capture %s\n", renderer.lastCapturePath().c_str()); }
 		if (doPick) {

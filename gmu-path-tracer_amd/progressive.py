@@ -42,6 +42,23 @@ class ProgressiveSession:
         if self.temporal is not None:
             self.temporal.reset()                    # the history was lit by the old lights
 
+    def set_vertices(self, scene_buffers, verts, normals=None):
+        """The geometry moved (same vertex count, same triangles): upload the vertices, and `normals` (when given) into the property
+        records, refit the tree and the renderer's traversal tables on the GPU (gmupt_renderer_refit), restart the accumulation.  The
+        temporal history shows the old surface and is dropped.  scene_buffers: the capi.SceneBuffers the renderer is bound to.
+        Returns the refit info dict."""
+        scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
+        if normals is not None:
+            from . import capi
+            props = scene_buffers.props.read(capi.tri_props_dtype)
+            props["normal"] = np.asarray(normals, np.float32).reshape(-1, 3)
+            scene_buffers.props.update(props)
+        info = self.renderer.refit()
+        self.camera.reset_accumulation()
+        if self.temporal is not None:
+            self.temporal.reset()
+        return info
+
     def resize(self, width, height, rows=None):
         """Resolution switch (Renderer.cpp:146-150,408-413): new accumulation target, camera vectors for the new aspect, restart."""
         self.width, self.height = width, height

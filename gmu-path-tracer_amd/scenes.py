@@ -247,6 +247,58 @@ def build_scene(mesh, sbvh_params=None):
     return scene
 
 
+def vertex_normals(verts, indices):
+    """Smooth per-vertex normals of a triangle mesh: the face normals summed with their area as weight (the cross product's length),
+    normalised; a vertex no triangle uses, or whose sum vanishes, gets (0, 1, 0).  float64 inside, float32 out."""
+    v = np.asarray(verts, np.float64).reshape(-1, 3)
+    t = np.asarray(indices, np.int64).reshape(-1, 3)
+    fn = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+    n = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(n, t[:, k], fn)
+    length = np.linalg.norm(n, axis=1, keepdims=True)
+    n = np.where(length > 1e-30, n / np.maximum(length, 1e-30), np.array([0.0, 1.0, 0.0]))
+    return n.astype(np.float32)
+
+
+def wobble(mesh_or_scene, phase, amplitude=0.05):
+    """Moved vertices for the refit tests and tools: every vertex displaced by a smooth field, a sum of three sines of its position
+    (fixed directions and frequencies relative to the mesh's extent), scaled to `amplitude` x the largest extent.  phase 0 returns the
+    vertices unchanged, bit for bit; the field is periodic in phase with period 1.  It vanishes at the minimum corner of the mesh and
+    grows smoothly from there, so features that shrink towards that corner (deep_chain_mesh) keep their shape in binary32."""
+    v = np.ascontiguousarray(mesh_or_scene["verts"], np.float32).reshape(-1, 3)
+    if phase == 0:
+        return v.copy()
+    x = v.astype(np.float64)
+    lo, hi = x.min(axis=0), x.max(axis=0)
+    extent = float(max((hi - lo).max(), 1e-30))
+    u = (x - lo) / extent
+    rng = np.random.default_rng(20240607)
+    disp = np.zeros_like(x)
+    for k in range(3):
+        direction = rng.normal(size=3); direction /= np.linalg.norm(direction)
+        freq = rng.uniform(1.0, 3.0, size=3) * 2.0 * np.pi
+        turn = 2.0 * np.pi * phase
+        wave = (np.sin(u @ freq + turn) - np.sin(turn)) - np.sin(u @ freq)
+        disp += wave[:, None] * direction[None, :]
+    return (x + disp * (amplitude * extent / 3.0)).astype(np.float32)
+
+
+def refit_scene(scene, verts, normals=None):
+    """A copy of a scene dict for moved vertices with the topology of its tree kept: the new vertices, `normals` (when given) in the
+    property records, and the node boxes of gmupt_bvh_refit_host -- what gmupt_renderer_refit leaves on the device."""
+    verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    if verts.shape != scene["verts"].shape:
+        raise ValueError("refit_scene: %d vertices for a scene of %d" % (verts.shape[0], scene["verts"].shape[0]))
+    out = dict(scene)
+    out["verts"] = verts
+    out["props"] = scene["props"].copy()
+    if normals is not None:
+        out["props"]["normal"] = np.asarray(normals, np.float32).reshape(-1, 3)
+    out["nodes"] = capi.bvh_refit_host(scene["nodes"], scene["tris"], verts)
+    return out
+
+
 def save_gmesh(mesh, path, params_path=None):
     """Writes the ".gmesh" dump host/MeshData.cpp reads, and optionally the sibling ".params" CSV in the reference's format
     (row 0: camera x,y,z,pitch,yaw; rows 1..: light x,y,z,falloff,r,g,b,radius -- Source/Scene.cpp:34-55)."""

@@ -97,8 +97,11 @@ typedef struct gmupt_buffer gmupt_buffer;
 /* replaces createBuffer<T> (Include/Util.hpp:17-43) + ID3D11Device::CreateBuffer with initial data */
 int gmupt_buffer_create(gmupt_device* dev, gmupt_buffer_kind kind, const void* data, size_t bytes, gmupt_buffer** out);
 /* replaces the light-buffer re-upload of the GUI (Source/GUI.cpp:125-130): UpdateSubresource on an existing buffer.
- * After updating node / triangle / vertex buffers call gmupt_renderer_bind_scene again (it rebuilds the traversal copy). */
+ * After updating node / triangle / vertex buffers call gmupt_renderer_bind_scene again (it rebuilds the traversal copy); when only vertex
+ * POSITIONS changed (same count, same triangle records), gmupt_renderer_refit does instead, without the host round trip. */
 int gmupt_buffer_update(gmupt_buffer* buf, const void* data, size_t bytes);
+/* synchronous device-to-host copy of the first `bytes` bytes of a buffer (bytes <= gmupt_buffer_size), after the device has finished */
+int gmupt_buffer_read(const gmupt_buffer* buf, void* dst, size_t bytes);
 void gmupt_buffer_destroy(gmupt_buffer* buf);
 size_t gmupt_buffer_size(const gmupt_buffer* buf);
 /* replaces Scene::createTextures (Source/Scene.cpp:247-303): `layers` square RGBA8 images of `size` x `size` texels, tightly packed
@@ -439,6 +442,58 @@ int gmupt_temporal_integrate_host(const float* beauty_rgba, const gmupt_aov* aov
                                   const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
                                   uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
                                   float* out_rgba, gmupt_history* out_history, uint32_t threads);
+
+/* ---- refit: moved vertices without a rebuild or a rebind (an extension; the reference has no moving geometry) ----
+ * After the caller has updated the vertex buffer (same vertex count, same triangle records), every box of the bound tree is recomputed
+ * bottom-up and every traversal table of the renderer is rewritten in place, on the GPU.  The topology stays: the same nodes, leaves,
+ * reference order, 4-wide collapse, numbering and tie words.
+ *
+ * Box rule (binary32; gmupt_bvh_refit_host and the kernels run the same statements, csrc/pt_refit.hpp):
+ *   lo(a, b) = b < a ? b : a, hi(a, b) = b > a ? b : a, per component.
+ *   Leaf [left, right) with right > left: start from vertex v[0] of reference `left`, fold in v[1], v[2], then the three vertices of each
+ *     further reference in index order (min = lo(min, p), max = hi(max, p)).  The box is that of the WHOLE triangles: a reference that a
+ *     spatial split of the builder had clipped gets a looser box than the builder gave it.  That is correct (the triangle test decides
+ *     the hit) and is the price of refitting an SBVH.
+ *   Empty leaf (right == left): its box is left as it is.
+ *   Inner node: min = lo(left child's min, right child's min), max = hi(left child's max, right child's max).  Children have larger
+ *     indices than their parent (bind validates this), so any order in which a node comes after its children is valid; the device
+ *     runs one launch per node height, lowest first.
+ *   pad0 / pad1 / pad2, left, right, isLeaf are not written.
+ * gmupt_bvh_refit_host: the rule on host arrays, in place.  Leaves on up to `threads` std::threads (0 -> 1, at most 16; the result does
+ *   not depend on the count).  Errors, with the nodes untouched: NULL arrays, no nodes, an inner node with a child index not above its
+ *   own or outside the array, a leaf range outside [0, num_tris], a triangle record with a vertex index outside [0, num_verts)
+ *   (GMUPT_ERR_INVALID_ARGUMENT).
+ * gmupt_renderer_refit, in this order:
+ *   1. GMUPT_ERR_NOT_BOUND without a bound scene.  The renderer remembers the node, triangle and vertex buffers it was bound to (they
+ *      must outlive the binding); element counts other than at bind time: GMUPT_ERR_INVALID_ARGUMENT.
+ *   2. Waits for the renderer's stream.  k_rf_finite checks that every vertex a triangle record uses is finite; one word is read back.
+ *      A non-finite vertex: GMUPT_ERR_INVALID_ARGUMENT, nothing has been written.  A vertex no record uses may hold anything.
+ *   3. On the renderer's stream, no host synchronisation in between: the node boxes in the caller's GMUPT_BUFFER_BVH_NODES buffer
+ *      (leaves in one launch, then one launch per height: `levels`), then Tri48 (v0, e1 = v1 - v0, e2 = v2 - v0; flag and
+ *      first-equal-reference words kept), TriPair, Node64 (filler records untouched), WNode planes (links, aux, NaN slots kept), and
+ *      rootMin / rootMax.  A renderer without a wide copy (GMUPT_TRAVERSAL other than wide, or a bound tree whose child boxes stuck out of
+ *      their parents) skips the TriPair / WNode parts and step 4; the wide copy appears only with the next bind.
+ *   4. The wide walk equals the binary one only if no OPENED node (one whose own slot the collapse replaced by its children) has a child
+ *      that is flat on an axis, on which the node is not flat, in the plane of one of the node's faces.  Bind chose what to open by that
+ *      rule on the old boxes; the WNode kernel evaluates it for every opened node on the new boxes.
+ *   5. One small readback (flag, root box).  Flag clear: rebuilt = 0.  Flag set: the host pass of gmupt_renderer_bind_scene runs on the
+ *      refitted node buffer, exactly what a fresh bind of these buffers would do: rebuilt = 1, reason = GMUPT_REFIT_FLAT_CHILD.  A
+ *      -DGMUPT_VARIANTS build (it also keeps Rec64 records) always takes this path, reason = GMUPT_REFIT_VARIANTS_BUILD.  Either way
+ *      the results are those of a fresh renderer bound to the same buffers.
+ *   6. ms = device time of step 3 (hipEvents on the stream); opened_nodes = size of the checked list.
+ * Refit does not touch the frame, path state, queues or statistics.  Paths in flight carry hits of the old geometry: restart the
+ * accumulation (iterationCounter = 0) as after a light edit.  Shading normals live in the GMUPT_BUFFER_TRI_PROPS buffer, whose pointer is
+ * bound: update it with gmupt_buffer_update, no refit involved.  Several renderers bound to the same buffers each call refit; the node
+ * boxes are recomputed to the same bytes each time.
+ * What stays as bind left it: which nodes live in LDS, the line pairing of Node64 and the collapse choices were made by surface area of
+ * the OLD boxes.  They affect speed only.  A caller whose mesh has moved far rebuilds the SBVH and rebinds; refit is for the frames in
+ * between. */
+#define GMUPT_REFIT_FLAT_CHILD 1u      /* an opened node of the 4-wide collapse got a flat child in one of its face planes */
+#define GMUPT_REFIT_VARIANTS_BUILD 2u  /* a -DGMUPT_VARIANTS build: the tables always come from the host pass */
+typedef struct { uint32_t rebuilt; uint32_t reason; uint32_t levels; uint32_t opened_nodes; double ms; } gmupt_refit_info;   /* 24 bytes */
+int gmupt_bvh_refit_host(gmupt_bvh_node* nodes, uint32_t num_nodes, const gmupt_triangle* tris, uint32_t num_tris,
+                         const float* verts, uint32_t num_verts, uint32_t threads);
+int gmupt_renderer_refit(gmupt_renderer* r, gmupt_refit_info* info /* may be NULL */);
 
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
