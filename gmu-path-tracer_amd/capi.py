@@ -131,6 +131,9 @@ assert C.sizeof(TemporalParams) == 32
 history_dtype = np.dtype([("color", "<f4", 3), ("count", "<f4"), ("normal", "<f4", 3), ("material", "<u4"), ("position", "<f4", 3),
                           ("valid", "<u4")])
 assert history_dtype.itemsize == 48
+# gmupt_motion: where the pixel's surface point was in the previous vertex pose; flags = 1 on a triangle hit without a nearer light (16 bytes)
+motion_dtype = np.dtype([("prev_position", "<f4", 3), ("flags", "<u4")])
+assert motion_dtype.itemsize == 16
 
 
 class RefitInfo(C.Structure):
@@ -200,6 +203,13 @@ SYMBOLS = {
                                                 C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _P, _P, C.c_uint32]),
     "gmupt_bvh_refit_host": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32]),
     "gmupt_renderer_refit": (C.c_int, [_P, C.POINTER(RefitInfo)]),
+    "gmupt_render_aovs_motion": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(TraceInfo)]),
+    "gmupt_motion_host": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
+    "gmupt_temporal_integrate_motion_host": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(CameraBuffer), C.c_uint32, C.c_uint32,
+                                                       C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _P, _P, C.c_uint32]),
+    "gmupt_temporal_denoise_image_motion": (C.c_int, [_P, _P, _P, _P, C.POINTER(CameraBuffer), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                                      C.POINTER(TemporalParams), _P, C.c_size_t, C.POINTER(C.c_float)]),
+    "gmupt_render_denoised_temporal_motion": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(TemporalParams), _P, C.c_size_t, C.POINTER(TraceInfo)]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -576,6 +586,27 @@ class Renderer:
         self.last_aovs = ti
         return out
 
+    # motion plane (gmupt_render_aovs_motion)
+    def aovs_motion(self, prev_verts, samples=1, info=None):
+        """aovs() plus the motion plane against `prev_verts`: a float32 torch tensor on this renderer's GPU with the previous position of
+        every vertex of the bound vertex buffer ((V, 3) or flat).  Returns (aov (H, W, 16), motion (H, W, 4)) float32 torch tensors; a
+        motion record is gmupt_motion (motion_fields() splits it -- word 3 is an integer, compare it as bits)."""
+        import torch
+        dev = torch.device("cuda", getattr(self.dev, "index", 0))
+        if not hasattr(prev_verts, "is_cuda") or not prev_verts.is_cuda or prev_verts.dtype != torch.float32 or prev_verts.numel() % 3:
+            raise GmuptError("aovs_motion: prev_verts must be a float32 tensor of 3 floats per vertex on the GPU", ERR_INVALID_ARGUMENT)
+        if prev_verts.device.index != dev.index:
+            raise GmuptError("aovs_motion: prev_verts lives on %s, the renderer on %s" % (prev_verts.device, dev), ERR_INVALID_ARGUMENT)
+        pv = prev_verts.contiguous()
+        out = torch.empty((self.height, self.width, 16), dtype=torch.float32, device=dev)
+        mv = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        ti = info if info is not None else TraceInfo()
+        _check(lib().gmupt_render_aovs_motion(self.h, int(samples), C.c_void_p(pv.data_ptr()), pv.numel() // 3, C.c_void_p(out.data_ptr()),
+                                              out.numel() * 4, C.c_void_p(mv.data_ptr()), mv.numel() * 4, C.byref(ti)))
+        self.last_aovs = ti
+        return out, mv
+
     # denoiser (gmupt_render_denoised)
     def denoise(self, aov_samples=1, info=None, **params):
         """The a-trous denoiser on this renderer's frame (the tile in tile mode): gmupt_render_aovs(aov_samples) into internal scratch,
@@ -607,6 +638,21 @@ class Renderer:
         ti = info if info is not None else TraceInfo()
         _check(lib().gmupt_render_denoised_temporal(self.h, handle.h, int(aov_samples), C.byref(tp), C.c_void_p(out.data_ptr()), out.numel() * 4,
                                                     C.byref(ti)))
+        self.last_denoise = ti
+        return out
+
+    def denoise_temporal_motion(self, handle, aov_samples=1, info=None, **params):
+        """denoise_temporal() for geometry that moves (gmupt_render_denoised_temporal_motion): the handle keeps the vertex pose of its
+        record sets, and after a refit() the history is looked up where each surface point was.  Without a refit since the history
+        was written it is denoise_temporal() bit for bit."""
+        import torch
+        dev = torch.device("cuda", getattr(self.dev, "index", 0))
+        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+        tp = temporal_params(**params)
+        torch.cuda.current_stream(dev).synchronize()
+        ti = info if info is not None else TraceInfo()
+        _check(lib().gmupt_render_denoised_temporal_motion(self.h, handle.h, int(aov_samples), C.byref(tp), C.c_void_p(out.data_ptr()),
+                                                           out.numel() * 4, C.byref(ti)))
         self.last_denoise = ti
         return out
 
@@ -775,10 +821,11 @@ def temporal_params(**params):
     return tp
 
 
-def temporal_denoise_image(handle, beauty, aov, cam_buffer, new_accumulation, origin=(0, 0), ms=None, **params):
+def temporal_denoise_image(handle, beauty, aov, cam_buffer, new_accumulation, origin=(0, 0), ms=None, motion=None, **params):
     """gmupt_temporal_denoise_image on torch tensors on the handle's GPU: beauty (H, W, 4) float32 (a = sample-count bits), aov (H, W, 16)
     float32 records, rendered with cam_buffer (a CameraBuffer) at `origin` of its whole frame.  new_accumulation: move the latest
-    call's records into the history first.  Returns the (H, W, 4) float32 result.  ms: optional list that receives the device time."""
+    call's records into the history first.  Returns the (H, W, 4) float32 result.  ms: optional list that receives the device time.
+    motion: an (H, W, 4) float32 tensor of gmupt_motion records on the same GPU (gmupt_temporal_denoise_image_motion), or None."""
     import torch
     if beauty.dim() != 3 or beauty.shape[2] != 4 or aov.dim() != 3 or aov.shape[2] != 16 or tuple(aov.shape[:2]) != tuple(beauty.shape[:2]):
         raise GmuptError("temporal_denoise_image: beauty must be (H, W, 4) and aov (H, W, 16)", ERR_INVALID_ARGUMENT)
@@ -788,11 +835,24 @@ def temporal_denoise_image(handle, beauty, aov, cam_buffer, new_accumulation, or
     H, W = beauty.shape[0], beauty.shape[1]
     out = torch.empty_like(beauty)
     tp = temporal_params(**params)
+    if motion is not None:
+        if motion.dtype != torch.float32 or not motion.is_cuda or tuple(motion.shape) != (H, W, 4) or motion.device != beauty.device:
+            raise GmuptError("temporal_denoise_image: motion must be an (H, W, 4) float32 tensor on the GPU of beauty", ERR_INVALID_ARGUMENT)
+        hdev = getattr(handle.renderer.dev, "index", 0)
+        if beauty.device.index != hdev or aov.device != beauty.device:
+            raise GmuptError("temporal_denoise_image: the tensors live on %s, the handle's renderer on cuda:%d" % (beauty.device, hdev), ERR_INVALID_ARGUMENT)
+        motion = motion.contiguous()
     torch.cuda.current_stream(beauty.device).synchronize()
     t = C.c_float(0.0)
-    _check(lib().gmupt_temporal_denoise_image(handle.h, C.c_void_p(beauty.data_ptr()), C.c_void_p(aov.data_ptr()), C.byref(cam_buffer),
-                                              int(origin[0]), int(origin[1]), W, H, 1 if new_accumulation else 0, C.byref(tp),
-                                              C.c_void_p(out.data_ptr()), out.numel() * 4, C.byref(t)))
+    if motion is not None:
+        _check(lib().gmupt_temporal_denoise_image_motion(handle.h, C.c_void_p(beauty.data_ptr()), C.c_void_p(aov.data_ptr()),
+                                                         C.c_void_p(motion.data_ptr()), C.byref(cam_buffer), int(origin[0]), int(origin[1]), W, H,
+                                                         1 if new_accumulation else 0, C.byref(tp), C.c_void_p(out.data_ptr()), out.numel() * 4,
+                                                         C.byref(t)))
+    else:
+        _check(lib().gmupt_temporal_denoise_image(handle.h, C.c_void_p(beauty.data_ptr()), C.c_void_p(aov.data_ptr()), C.byref(cam_buffer),
+                                                  int(origin[0]), int(origin[1]), W, H, 1 if new_accumulation else 0, C.byref(tp),
+                                                  C.c_void_p(out.data_ptr()), out.numel() * 4, C.byref(t)))
     if ms is not None:
         ms.append(t.value)
     return out
@@ -828,6 +888,81 @@ def temporal_integrate_host(beauty, aov, prev=None, prev_cam=None, prev_origin=(
     _check(lib().gmupt_temporal_integrate_host(_ptr(b), _ptr(a), W, H, pp, C.byref(prev_cam) if prev_cam is not None else None,
                                                int(prev_origin[0]), int(prev_origin[1]), pw, ph, C.byref(tp), _ptr(out), _ptr(hist), int(threads)))
     return out, hist
+
+
+def temporal_integrate_motion_host(beauty, aov, motion, prev=None, prev_cam=None, prev_origin=(0, 0), threads=16, **params):
+    """gmupt_temporal_integrate_motion_host: temporal_integrate_host with a motion plane -- (H, W) motion_dtype records or (H, W, 4)
+    float32, numpy or torch; None = temporal_integrate_host.  Returns (integrated, history) as that function."""
+    b = beauty.cpu().numpy() if hasattr(beauty, "cpu") else np.asarray(beauty)
+    a = aov.cpu().numpy() if hasattr(aov, "cpu") else np.asarray(aov)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.dtype == aov_dtype:
+        a = a.view(np.float32).reshape(a.shape + (16,))
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if b.ndim != 3 or b.shape[2] != 4 or a.shape != b.shape[:2] + (16,):
+        raise GmuptError("temporal_integrate_motion_host: beauty must be (H, W, 4) and aov (H, W, 16)", ERR_INVALID_ARGUMENT)
+    H, W = b.shape[:2]
+    mp = None
+    if motion is not None:
+        m = motion.cpu().numpy() if hasattr(motion, "cpu") else np.asarray(motion)
+        if m.dtype == motion_dtype:
+            m = m.view(np.float32).reshape(m.shape + (4,))
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        if m.shape != (H, W, 4):
+            raise GmuptError("temporal_integrate_motion_host: motion must be (H, W) records", ERR_INVALID_ARGUMENT)
+        mp = _ptr(m)
+    ph = pw = 0
+    pp = None
+    if prev is not None:
+        pv = np.asarray(prev)
+        if pv.dtype != history_dtype:
+            pv = np.ascontiguousarray(pv, dtype=np.float32).view(history_dtype)[..., 0]
+        pv = np.ascontiguousarray(pv)
+        if pv.ndim != 2:
+            raise GmuptError("temporal_integrate_motion_host: prev must be (h, w) records", ERR_INVALID_ARGUMENT)
+        ph, pw = pv.shape
+        pp = _ptr(pv)
+    out = np.empty_like(b)
+    hist = np.empty((H, W), history_dtype)
+    tp = temporal_params(**params)
+    _check(lib().gmupt_temporal_integrate_motion_host(_ptr(b), _ptr(a), mp, W, H, pp, C.byref(prev_cam) if prev_cam is not None else None,
+                                                      int(prev_origin[0]), int(prev_origin[1]), pw, ph, C.byref(tp), _ptr(out), _ptr(hist),
+                                                      int(threads)))
+    return out, hist
+
+
+def motion_host(hits, aov, tris, verts_now, verts_prev):
+    """gmupt_motion_host: the motion plane's rule on the CPU, bit for bit the device's.  hits: (..., 8) float32 gmupt_hit records of the
+    centre rays (or hit_dtype), aov: their (..., 16) float32 records (or aov_dtype), tris: triangle_dtype records, verts_now / verts_prev:
+    (V, 3) float32.  Returns an array of motion_dtype with the leading shape of `aov`."""
+    h = hits.cpu().numpy() if hasattr(hits, "cpu") else np.asarray(hits)
+    a = aov.cpu().numpy() if hasattr(aov, "cpu") else np.asarray(aov)
+    if h.dtype == hit_dtype:
+        h = h.view(np.float32).reshape(h.shape + (8,))
+    if a.dtype == aov_dtype:
+        a = a.view(np.float32).reshape(a.shape + (16,))
+    h = np.ascontiguousarray(h, dtype=np.float32)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    n = a.size // 16
+    if h.size != n * 8:
+        raise GmuptError("motion_host: one hit per AOV record", ERR_INVALID_ARGUMENT)
+    tris = np.ascontiguousarray(tris, dtype=triangle_dtype)
+    vn = np.ascontiguousarray(verts_now, dtype=np.float32).reshape(-1, 3)
+    vp = np.ascontiguousarray(verts_prev, dtype=np.float32).reshape(-1, 3)
+    if vn.shape != vp.shape:
+        raise GmuptError("motion_host: %d vertices now, %d before" % (vn.shape[0], vp.shape[0]), ERR_INVALID_ARGUMENT)
+    out = np.zeros(a.shape[:-1], motion_dtype)
+    _check(lib().gmupt_motion_host(_ptr(h), _ptr(a), n, _ptr(tris), tris.shape[0], _ptr(vn), _ptr(vp), vn.shape[0], _ptr(out)))
+    return out
+
+
+def motion_fields(motion):
+    """Splits (..., 4) gmupt_motion records (torch or numpy) into a dict of numpy arrays: prev_position (..., 3) float32, flags uint32."""
+    m = motion.cpu().numpy() if hasattr(motion, "cpu") else np.asarray(motion)
+    m = np.ascontiguousarray(m, dtype=np.float32)
+    rec = m.reshape(-1, 4).view(motion_dtype)[:, 0]
+    shape = m.shape[:-1]
+    return {k: rec[k].reshape(shape + rec[k].shape[1:]).copy() for k in motion_dtype.names}
 
 
 def bvh_refit_host(nodes, tris, verts, threads=16):

@@ -6,6 +6,7 @@
 #include "pt_denoise.hpp"
 #include "pt_temporal.hpp"
 #include "pt_refit.hpp"
+#include "pt_motion.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
 #include "../host/TextureLoader.hpp"
@@ -63,7 +64,12 @@ void launch_denoise(const float4* beauty, const float4* aov, int W, int H, const
 void denoise_host(const float* beauty, const void* aov, int W, int H, const DnParams& prm, float* out, int threads);
 void launch_temporal(const float4* beauty, const float4* aov, int W, int H, const TpPrev& prev, const TpParams& prm, float4* out, float4* hist,
                      hipStream_t s);
-void temporal_host(const float* beauty, const void* aov, int W, int H, const void* prev, const gmupt_camera_buffer* prevCam, int px0, int py0,
+void launch_temporal_motion(const float4* beauty, const float4* aov, const float4* motion, int W, int H, const TpPrev& prev, const TpParams& prm,
+                            float4* out, float4* hist, hipStream_t s);
+void launch_mv_resolve(const SceneView& scene, const float* prevVerts, uint32_t npix, uint32_t R, const gmupt_hit* hits, const gmupt_aov* aov,
+                       gmupt_motion* out, hipStream_t s);
+void motion_host(const gmupt_hit* hits, const gmupt_aov* aov, size_t n, const gmupt_triangle* tris, const float* now, const float* prev, gmupt_motion* out);
+void temporal_host(const float* beauty, const void* aov, const void* motion, int W, int H, const void* prev, const gmupt_camera_buffer* prevCam, int px0, int py0,
                    int pW, int pH, const TpParams& prm, float* out, void* outHist, int threads);
 void launch_refit_check(const RfArgs& a, hipStream_t s);
 uint32_t launch_refit_boxes(const RfArgs& a, const std::vector<uint32_t>& levelOff, hipStream_t s);
@@ -260,6 +266,8 @@ struct gmupt_renderer {
     hipEvent_t dnEv[2] = { nullptr, nullptr };
     // temporal reuse (gmupt_render_denoised_temporal): advanced by an iteration that clears the frame and by gmupt_resize (host only)
     uint64_t accumGeneration = 0;
+    // motion (gmupt_render_denoised_temporal_motion): which binding the renderer has and how many refits it has seen (host only)
+    uint64_t bindingId = 0, geomGeneration = 0;
     // refit (gmupt_renderer_refit): the buffers of the binding with their element counts, and what build_traversal_copy knows about the
     // topology of its tables -- host vectors, uploaded into one allocation (rfDev) by the first refit after a bind
     const gmupt_buffer* boundNodes = nullptr; const gmupt_buffer* boundTris = nullptr; const gmupt_buffer* boundVerts = nullptr;
@@ -810,6 +818,7 @@ extern "C" int gmupt_renderer_refit(gmupt_renderer* r, gmupt_refit_info* info)
     } else {
         for (int k = 0; k < 3; k++) { std::memcpy(&r->p.trav.rootMin[k], &back[4 + k], 4); std::memcpy(&r->p.trav.rootMax[k], &back[8 + k], 4); }
     }
+    r->geomGeneration++;
     if (info) { info->rebuilt = reason ? 1u : 0u; info->reason = reason; info->levels = levels; info->opened_nodes = openedNodes; info->ms = (double)ms; }
     return GMUPT_OK;
 }
@@ -850,6 +859,7 @@ extern "C" int gmupt_renderer_bind_scene(gmupt_renderer* r, const gmupt_buffer* 
     int rc = build_traversal_copy(r, nodes, triangles, vertices);
     if (rc != GMUPT_OK) return rc;
     r->sceneBound = true;
+    r->bindingId++;
     return GMUPT_OK;
 }
 
@@ -1202,9 +1212,32 @@ extern "C" int gmupt_aov_ray(const gmupt_camera_buffer* cam, uint32_t x, uint32_
     return gmupt_camera_pick_ray(cam, px, py, out);
 }
 
+// gmupt_render_aovs, and with motion != nullptr gmupt_render_aovs_motion: k_mv_resolve follows k_aov_resolve on every chunk's hits
+static int render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info, const float* prevVerts, gmupt_motion* motion);
+
 extern "C" int gmupt_render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info)
 {
     if (info) std::memset(info, 0, sizeof(*info));
+    return render_aovs(r, samples, out, bytes, info, nullptr, nullptr);
+}
+
+extern "C" int gmupt_render_aovs_motion(gmupt_renderer* r, uint32_t samples, const float* prev_verts, uint32_t num_verts, gmupt_aov* aov_out, size_t aov_bytes,
+                                        gmupt_motion* motion_out, size_t motion_bytes, gmupt_trace_info* info)
+{
+    const char* fn = "gmupt_render_aovs_motion";
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer", fn);
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
+    if (!prev_verts || ((uintptr_t)prev_verts & 3u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned previous vertices (4 bytes)", fn);
+    if (!motion_out || ((uintptr_t)motion_out & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned motion output (16 bytes)", fn);
+    if (num_verts != r->p.scene.numVerts) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %u previous vertices, the bound buffer holds %u", fn, num_verts, r->p.scene.numVerts);
+    if (motion_bytes < (size_t)r->p.fbW * r->p.fbH * sizeof(gmupt_motion))
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu bytes for %ux%u records of 16 bytes", fn, motion_bytes, r->p.fbW, r->p.fbH);
+    return render_aovs(r, samples, aov_out, aov_bytes, info, prev_verts, motion_out);
+}
+
+static int render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info, const float* prevVerts, gmupt_motion* motion)
+{
     if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: null renderer");
     if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_aovs: no scene bound");
     if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_aovs: no camera set");
@@ -1239,6 +1272,10 @@ extern "C" int gmupt_render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov*
         HIP_TRY(hipGetLastError());
         launch_aov_resolve(p, rows * W, samples, R, r->aovRays, r->aovHits, out + (size_t)row * W, r->stream);
         HIP_TRY(hipGetLastError());
+        if (motion) {
+            launch_mv_resolve(p.scene, prevVerts, rows * W, R, r->aovHits, out + (size_t)row * W, motion + (size_t)row * W, r->stream);
+            HIP_TRY(hipGetLastError());
+        }
     }
     HIP_TRY(hipEventRecord(r->queryEv[1], r->stream));
     DevStats ds;
@@ -1388,7 +1425,11 @@ struct TpSlot {
     bool present = false;
     gmupt_camera_buffer cam{};
     uint32_t x0 = 0, y0 = 0, W = 0, H = 0;
+    // the vertex pose the records were written in (gmupt_render_denoised_temporal_motion only): a device copy of the bound vertex buffer
+    void* verts = nullptr; size_t vertsBytes = 0;
+    bool hasPose = false; uint64_t binding = 0, geomGeneration = 0; uint32_t numVerts = 0;
 };
+static_assert(sizeof(gmupt_motion) == 16 && offsetof(gmupt_motion, flags) == 12, "gmupt_motion layout");
 
 struct gmupt_temporal {
     gmupt_renderer* r = nullptr;
@@ -1436,7 +1477,7 @@ extern "C" void gmupt_temporal_destroy(gmupt_temporal* t)
     (void)hipSetDevice(t->r->dev->id);
     (void)hipStreamSynchronize(t->r->stream);
     for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
-    for (void* a : { t->frozen.rec, t->last.rec, t->integrated }) if (a) (void)hipFree(a);
+    for (void* a : { t->frozen.rec, t->last.rec, t->integrated, t->frozen.verts, t->last.verts }) if (a) (void)hipFree(a);
     delete t;
 }
 
@@ -1444,14 +1485,22 @@ extern "C" int gmupt_temporal_reset(gmupt_temporal* t)
 {
     if (!t) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_temporal_reset: null handle");
     t->frozen.present = false; t->last.present = false;
+    if (t->frozen.verts || t->last.verts) {   // the pose snapshots go with the records
+        HIP_TRY(hipSetDevice(t->r->dev->id));
+        HIP_TRY(hipStreamSynchronize(t->r->stream));
+        for (TpSlot* sl : { &t->frozen, &t->last }) {
+            if (sl->verts) HIP_TRY(hipFree(sl->verts));
+            sl->verts = nullptr; sl->vertsBytes = 0; sl->hasPose = false;
+        }
+    }
     return GMUPT_OK;
 }
 
-extern "C" int gmupt_temporal_denoise_image(gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_camera_buffer* cam,
-                                            uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
-                                            const gmupt_temporal_params* p, float* out_rgba, size_t out_bytes, float* ms)
+// gmupt_temporal_denoise_image (motion == nullptr: k_tp_integrate) and gmupt_temporal_denoise_image_motion (k_tp_integrate_mv)
+static int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
+                            const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
+                            const gmupt_temporal_params* p, float* out_rgba, size_t out_bytes, float* ms)
 {
-    const char* fn = "gmupt_temporal_denoise_image";
     if (ms) *ms = 0.0f;
     gmupt_temporal_params d;
     if (!p) { gmupt_temporal_default_params(&d); p = &d; }
@@ -1478,9 +1527,14 @@ extern "C" int gmupt_temporal_denoise_image(gmupt_temporal* t, const float* beau
     }
     float4* integrated = static_cast<float4*>(t->integrated);
     t->last.present = false;                                // until its records are written
+    t->last.hasPose = false;                                // until gmupt_render_denoised_temporal_motion says which pose they are in
     HIP_TRY(hipEventRecord(t->ev[0], r->stream));
-    launch_temporal(reinterpret_cast<const float4*>(beauty_rgba), reinterpret_cast<const float4*>(aov), (int)width, (int)height, prev, tp, integrated,
-                    static_cast<float4*>(t->last.rec), r->stream);
+    if (motion)
+        launch_temporal_motion(reinterpret_cast<const float4*>(beauty_rgba), reinterpret_cast<const float4*>(aov), reinterpret_cast<const float4*>(motion),
+                               (int)width, (int)height, prev, tp, integrated, static_cast<float4*>(t->last.rec), r->stream);
+    else
+        launch_temporal(reinterpret_cast<const float4*>(beauty_rgba), reinterpret_cast<const float4*>(aov), (int)width, (int)height, prev, tp, integrated,
+                        static_cast<float4*>(t->last.rec), r->stream);
     HIP_TRY(hipGetLastError());
     launch_denoise(integrated, reinterpret_cast<const float4*>(aov), (int)width, (int)height, dn, r->dnScratch, reinterpret_cast<float4*>(out_rgba), r->stream);
     HIP_TRY(hipGetLastError());
@@ -1493,10 +1547,41 @@ extern "C" int gmupt_temporal_denoise_image(gmupt_temporal* t, const float* beau
     return GMUPT_OK;
 }
 
+extern "C" int gmupt_temporal_denoise_image(gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_camera_buffer* cam,
+                                            uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
+                                            const gmupt_temporal_params* p, float* out_rgba, size_t out_bytes, float* ms)
+{
+    return temporal_denoise("gmupt_temporal_denoise_image", t, beauty_rgba, aov, nullptr, cam, x0, y0, width, height, new_accumulation, p, out_rgba, out_bytes, ms);
+}
+
+extern "C" int gmupt_temporal_denoise_image_motion(gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
+                                                   const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                                                   int new_accumulation, const gmupt_temporal_params* p, float* out_rgba, size_t out_bytes, float* ms)
+{
+    const char* fn = "gmupt_temporal_denoise_image_motion";
+    if ((uintptr_t)motion & 15u) { if (ms) *ms = 0.0f; return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: misaligned motion plane (16 bytes)", fn); }
+    return temporal_denoise(fn, t, beauty_rgba, aov, motion, cam, x0, y0, width, height, new_accumulation, p, out_rgba, out_bytes, ms);
+}
+
+// gmupt_render_denoised_temporal, and with `poses` gmupt_render_denoised_temporal_motion: the record sets keep their vertex pose
+static int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
+                                    float* out_rgba, size_t bytes, gmupt_trace_info* info);
+
 extern "C" int gmupt_render_denoised_temporal(gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
                                               float* out_rgba, size_t bytes, gmupt_trace_info* info)
 {
-    const char* fn = "gmupt_render_denoised_temporal";
+    return render_denoised_temporal("gmupt_render_denoised_temporal", false, r, t, aov_samples, p, out_rgba, bytes, info);
+}
+
+extern "C" int gmupt_render_denoised_temporal_motion(gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
+                                                     float* out_rgba, size_t bytes, gmupt_trace_info* info)
+{
+    return render_denoised_temporal("gmupt_render_denoised_temporal_motion", true, r, t, aov_samples, p, out_rgba, bytes, info);
+}
+
+static int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
+                                    float* out_rgba, size_t bytes, gmupt_trace_info* info)
+{
     if (info) std::memset(info, 0, sizeof(*info));
     if (!r || !t) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer or handle", fn);
     if (t->r != r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: the handle belongs to another renderer", fn);
@@ -1515,32 +1600,51 @@ extern "C" int gmupt_render_denoised_temporal(gmupt_renderer* r, gmupt_temporal*
     rc = query_supported(r, fn);
     if (rc != GMUPT_OK) return rc;
     HIP_TRY(hipSetDevice(r->dev->id));
-    rc = grow_scratch(r, &r->dnInput, &r->dnInputBytes, (size_t)W * H * (sizeof(gmupt_aov) + 16));
+    const bool fold = !t->seen || t->generation != r->accumGeneration;
+    // the record sets as they will be once the fold has swapped them: `fz` is integrated against, `nw` receives this call's records
+    TpSlot& fz = fold ? t->last : t->frozen;
+    TpSlot& nw = fold ? t->frozen : t->last;
+    const uint32_t nv = r->p.scene.numVerts;
+    const auto inPose = [&](const TpSlot& sl) { return sl.hasPose && sl.binding == r->bindingId && sl.numVerts == nv; };
+    const bool moved = poses && fz.present && inPose(fz) && fz.geomGeneration != r->geomGeneration;
+    const size_t npix = (size_t)W * H;
+    rc = grow_scratch(r, &r->dnInput, &r->dnInputBytes, npix * (sizeof(gmupt_aov) + 16 + (moved ? sizeof(gmupt_motion) : 0)));
     if (rc != GMUPT_OK) return rc;
     gmupt_aov* aov = static_cast<gmupt_aov*>(r->dnInput);
-    float* beauty = reinterpret_cast<float*>(static_cast<char*>(r->dnInput) + (size_t)W * H * sizeof(gmupt_aov));
+    float* beauty = reinterpret_cast<float*>(static_cast<char*>(r->dnInput) + npix * sizeof(gmupt_aov));
+    gmupt_motion* motion = moved ? reinterpret_cast<gmupt_motion*>(static_cast<char*>(r->dnInput) + npix * (sizeof(gmupt_aov) + 16)) : nullptr;
     gmupt_trace_info ai;
-    rc = gmupt_render_aovs(r, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai);
+    if (moved) rc = gmupt_render_aovs_motion(r, aov_samples, static_cast<const float*>(fz.verts), nv, aov, npix * sizeof(gmupt_aov), motion, npix * sizeof(gmupt_motion), &ai);
+    else rc = gmupt_render_aovs(r, aov_samples, aov, npix * sizeof(gmupt_aov), &ai);
     if (info) *info = ai;
     if (rc != GMUPT_OK) return rc;
-    rc = gmupt_copy_framebuffer_to_device(r, beauty, (size_t)W * H * 16);
+    rc = gmupt_copy_framebuffer_to_device(r, beauty, npix * 16);
     if (rc != GMUPT_OK) return rc;
-    const bool fold = !t->seen || t->generation != r->accumGeneration;
+    if (poses && !(inPose(nw) && nw.geomGeneration == r->geomGeneration)) {
+        // the pose of the records this call writes: once per refit, into the set that receives them (never the one integrated against).
+        // It is written before temporal_denoise() has checked its arguments and folded, so that one synchronisation serves both; the
+        // set is marked as having no pose first and gets it back only after that call succeeded, so a refused call leaves a set that
+        // is integrated against without a motion plane, never one with a wrong pose.
+        nw.hasPose = false;
+        rc = grow_scratch(r, &nw.verts, &nw.vertsBytes, (size_t)nv * 12);
+        if (rc != GMUPT_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(nw.verts, r->p.scene.verts, (size_t)nv * 12, hipMemcpyDeviceToDevice, r->stream));
+    }
     const uint32_t x0 = r->p.tileEnabled ? r->p.tileX0 : 0u, y0 = r->p.tileEnabled ? r->p.tileY0 : 0u;
     float ms = 0.0f;
-    rc = gmupt_temporal_denoise_image(t, beauty, aov, &r->p.cam, x0, y0, W, H, fold ? 1 : 0, p, out_rgba, bytes, &ms);
+    rc = temporal_denoise(fn, t, beauty, aov, motion, &r->p.cam, x0, y0, W, H, fold ? 1 : 0, p, out_rgba, bytes, &ms);   // synchronises the stream
     if (info) info->ms = ai.ms + ms;
     if (rc != GMUPT_OK) return rc;
     t->seen = true; t->generation = r->accumGeneration;
+    if (poses) { t->last.hasPose = true; t->last.binding = r->bindingId; t->last.geomGeneration = r->geomGeneration; t->last.numVerts = nv; }
     return GMUPT_OK;
 }
 
-extern "C" int gmupt_temporal_integrate_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height,
-                                             const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
-                                             uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
-                                             float* out_rgba, gmupt_history* out_history, uint32_t threads)
+static int temporal_integrate_host(const char* fn, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion, uint32_t width, uint32_t height,
+                                   const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
+                                   uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
+                                   float* out_rgba, gmupt_history* out_history, uint32_t threads)
 {
-    const char* fn = "gmupt_temporal_integrate_host";
     if (!beauty_rgba || !aov || !out_rgba || !out_history) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null beauty, aov or output", fn);
     if (width == 0 || height == 0 || width > 65535 || height > 65535 || (uint64_t)width * height > (1ull << 28))
         return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: image of %ux%u (1..65535 each, at most 2^28 pixels)", fn, width, height);
@@ -1553,10 +1657,11 @@ extern "C" int gmupt_temporal_integrate_host(const float* beauty_rgba, const gmu
     {   // the outputs may not overlap each other or any input
         const size_t n = (size_t)width * height;
         const uintptr_t o[2] = { (uintptr_t)out_rgba, (uintptr_t)out_history }, on[2] = { n * 16, n * sizeof(gmupt_history) };
-        const uintptr_t i[4] = { (uintptr_t)beauty_rgba, (uintptr_t)aov, (uintptr_t)prev, (uintptr_t)out_history },
-                        in[4] = { n * 16, n * sizeof(gmupt_aov), prev ? (size_t)prev_width * prev_height * sizeof(gmupt_history) : 0, n * sizeof(gmupt_history) };
+        const uintptr_t i[5] = { (uintptr_t)beauty_rgba, (uintptr_t)aov, (uintptr_t)prev, (uintptr_t)motion, (uintptr_t)out_history },
+                        in[5] = { n * 16, n * sizeof(gmupt_aov), prev ? (size_t)prev_width * prev_height * sizeof(gmupt_history) : 0,
+                                  motion ? n * sizeof(gmupt_motion) : 0, n * sizeof(gmupt_history) };
         for (int a = 0; a < 2; a++)
-            for (int b = 0; b < (a == 0 ? 4 : 3); b++)
+            for (int b = 0; b < (a == 0 ? 5 : 4); b++)
                 if (in[b] && o[a] < i[b] + in[b] && i[b] < o[a] + on[a]) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: an output overlaps another array", fn);
     }
     gmupt_temporal_params d;
@@ -1565,13 +1670,51 @@ extern "C" int gmupt_temporal_integrate_host(const float* beauty_rgba, const gmu
     int rc = temporal_params(fn, p, dn, tp);
     if (rc != GMUPT_OK) return rc;
     try {
-        temporal_host(beauty_rgba, aov, (int)width, (int)height, prev, prev_cam, (int)prev_x0, (int)prev_y0, (int)prev_width, (int)prev_height, tp,
+        temporal_host(beauty_rgba, aov, motion, (int)width, (int)height, prev, prev_cam, (int)prev_x0, (int)prev_y0, (int)prev_width, (int)prev_height, tp,
                       out_rgba, out_history, (int)std::min(std::max(threads, 1u), 16u));
     } catch (const std::bad_alloc&) {
         return fail(GMUPT_ERR_OUT_OF_MEMORY, "%s: out of host memory for %ux%u pixels", fn, width, height);
     } catch (const std::exception& e) {
         return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %s", fn, e.what());
     }
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_temporal_integrate_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height,
+                                             const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
+                                             uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
+                                             float* out_rgba, gmupt_history* out_history, uint32_t threads)
+{
+    return temporal_integrate_host("gmupt_temporal_integrate_host", beauty_rgba, aov, nullptr, width, height, prev, prev_cam, prev_x0, prev_y0, prev_width,
+                                   prev_height, p, out_rgba, out_history, threads);
+}
+
+extern "C" int gmupt_temporal_integrate_motion_host(const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion, uint32_t width, uint32_t height,
+                                                    const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
+                                                    uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
+                                                    float* out_rgba, gmupt_history* out_history, uint32_t threads)
+{
+    return temporal_integrate_host("gmupt_temporal_integrate_motion_host", beauty_rgba, aov, motion, width, height, prev, prev_cam, prev_x0, prev_y0, prev_width,
+                                   prev_height, p, out_rgba, out_history, threads);
+}
+
+extern "C" int gmupt_motion_host(const gmupt_hit* hits, const gmupt_aov* aov, size_t n, const gmupt_triangle* tris, uint32_t num_tris,
+                                 const float* verts_now, const float* verts_prev, uint32_t num_verts, gmupt_motion* out)
+{
+    const char* fn = "gmupt_motion_host";
+    if (n == 0) return GMUPT_OK;
+    if (!hits || !aov || !out || !tris || !verts_now || !verts_prev) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null array", fn);
+    for (size_t i = 0; i < n; i++) {
+        gmupt_hit h;
+        std::memcpy(&h, (const char*)hits + i * sizeof(h), sizeof(h));
+        if (h.triangle < 0 || h.light > 0u) continue;
+        if ((uint32_t)h.triangle >= num_tris) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: hit %zu names triangle record %d of %u", fn, i, h.triangle, num_tris);
+        gmupt_triangle T;
+        std::memcpy(&T, (const char*)tris + (size_t)h.triangle * sizeof(T), sizeof(T));
+        for (int k = 0; k < 3; k++)
+            if (T.v[k] < 0 || (uint32_t)T.v[k] >= num_verts) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: triangle record %d references vertex %d of %u", fn, h.triangle, T.v[k], num_verts);
+    }
+    motion_host(hits, aov, n, tris, verts_now, verts_prev, out);
     return GMUPT_OK;
 }
 

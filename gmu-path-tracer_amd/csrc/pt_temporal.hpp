@@ -51,8 +51,11 @@ GM_HD int tp_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 // pixel p: beauty texel b and AOV record a0..a3 -> integrated texel `out` and new record r0..r2.  The four tap records are loaded
 // together, at addresses clamped into the previous rectangle, before any of them is tested (a load whose tap is outside is made and
 // ignored).  A projection whose taps all lie outside the previous rectangle loads nothing: no tap could count.
-GM_HD void tp_pixel(const float4 b, const float4 a0, const float4 a1, const float4 a2, const float4 a3, const TpPrev& pv, const TpParams& prm,
-                    float4& out, float4& r0, float4& r1, float4& r2)
+// MV: m is the pixel's gmupt_motion record; with flags == 1 the point that is projected and that the taps' plane test measures from is
+// prev_position, where the surface point was when the history was written.  The new record keeps x_p, the current pose.
+template <bool MV>
+GM_HD void tp_pixel_t(const float4 b, const float4 a0, const float4 a1, const float4 a2, const float4 a3, const float4 m, const TpPrev& pv,
+                      const TpParams& prm, float4& out, float4& r0, float4& r1, float4& r2)
 {
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const int32_t tri = (int32_t)f2u(a3.x);
@@ -63,9 +66,11 @@ GM_HD void tp_pixel(const float4 b, const float4 a0, const float4 a1, const floa
         return;
     }
     const f3 np = normalize3(nraw), xp = mk3(a2.x, a2.y, a2.z);
+    f3 xh = xp;                                                   // the point in the history's pose
+    if constexpr (MV) { if (f2u(m.w) == 1u) xh = mk3(m.x, m.y, m.z); }
     float nh = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f;
     float u, v;
-    if (pv.rec && tp_project(pv.cam, xp, u, v)) {
+    if (pv.rec && tp_project(pv.cam, xh, u, v)) {
         const float ul = u - (float)pv.x0, vl = v - (float)pv.y0;
         const float fu = __builtin_floorf(ul), fv = __builtin_floorf(vl);
         if (fu >= -1.0f && fu <= (float)(pv.W - 1) && fv >= -1.0f && fv <= (float)(pv.H - 1)) {
@@ -87,7 +92,7 @@ GM_HD void tp_pixel(const float4 b, const float4 a0, const float4 a1, const floa
                 if (qx < 0 || qx >= pv.W || qy < 0 || qy >= pv.H) continue;
                 if (f2u(q2[k].w) != 1u || !(q0[k].w > 0.0f) || f2u(q1[k].w) != mat) continue;
                 if (!(dot3(np, mk3(q1[k].x, q1[k].y, q1[k].z)) >= prm.minCos)) continue;
-                if (!(dabs(dot3(np, mk3(q2[k].x, q2[k].y, q2[k].z) - xp)) <= lim)) continue;
+                if (!(dabs(dot3(np, mk3(q2[k].x, q2[k].y, q2[k].z) - xh)) <= lim)) continue;
                 sw = sw + w[k];
                 sr = sr + w[k] * q0[k].x; sg = sg + w[k] * q0[k].y; sb = sb + w[k] * q0[k].z;
                 sn = sn + w[k] * q0[k].w;
@@ -115,6 +120,12 @@ GM_HD void tp_pixel(const float4 b, const float4 a0, const float4 a1, const floa
     r0 = make_float4(out.x, out.y, out.z, count);
     r1 = make_float4(np.x, np.y, np.z, u2f(mat));
     r2 = make_float4(xp.x, xp.y, xp.z, u2f(count > 0.0f ? 1u : 0u));
+}
+
+GM_HD void tp_pixel(const float4 b, const float4 a0, const float4 a1, const float4 a2, const float4 a3, const TpPrev& pv, const TpParams& prm,
+                    float4& out, float4& r0, float4& r1, float4& r2)
+{
+    tp_pixel_t<false>(b, a0, a1, a2, a3, make_float4(0.0f, 0.0f, 0.0f, 0.0f), pv, prm, out, r0, r1, r2);
 }
 
 } // namespace gmupt

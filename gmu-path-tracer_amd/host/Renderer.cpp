@@ -149,6 +149,31 @@ gmupt_trace_info Renderer::denoiseTemporal(float* deviceOut, size_t bytes, unsig
 	return info;
 }
 
+gmupt_trace_info Renderer::denoiseTemporalMotion(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_temporal_params* params)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }
+	if (!mTemporal) { gmupt_temporal* t = nullptr; check(gmupt_temporal_create(mRenderer.get(), &t)); mTemporal.reset(t); }
+	gmupt_trace_info info{};
+	check(gmupt_render_denoised_temporal_motion(mRenderer.get(), mTemporal.get(), aovSamples, params, deviceOut, bytes, &info));
+	return info;
+}
+
+std::vector<float> Renderer::denoiseTemporalMotion(unsigned aovSamples, const gmupt_temporal_params* params)
+{
+	const Resolution t = targetSize();
+	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
+	const size_t bytes = out.size() * sizeof(float);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoiseTemporalMotion: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { denoiseTemporalMotion(static_cast<float*>(d), bytes, aovSamples, params); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error("denoiseTemporalMotion: cannot read the image back");
+	return out;
+}
+
 std::vector<float> Renderer::denoiseTemporal(unsigned aovSamples, const gmupt_temporal_params* params)
 {
 	const Resolution t = targetSize();
@@ -164,13 +189,13 @@ std::vector<float> Renderer::denoiseTemporal(unsigned aovSamples, const gmupt_te
 	return out;
 }
 
-gmupt_refit_info Renderer::refitScene()
+gmupt_refit_info Renderer::refitScene(bool keepHistory)
 {
 	gmupt_refit_info info{};
 	bindScene(); // (the scene is bound on first use: a refit before the first frame starts from the loaded tree)
 	check(gmupt_renderer_refit(mRenderer.get(), &info));
 	mScene.mCamera.getBuffer()->iterationCounter = -1; // paths in flight carry hits of the old geometry
-	resetHistory();
+	if (!keepHistory) resetHistory();
 	return info;
 }
 

@@ -61,11 +61,15 @@ public:
 	// e.g. after a light edit, which makes the old history wrong.
 	gmupt_trace_info denoiseTemporal(float* deviceOut, size_t bytes, unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
 	std::vector<float> denoiseTemporal(unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
+	// denoiseTemporal for geometry that moves (gmupt_render_denoised_temporal_motion): the handle keeps the vertex pose of its record sets,
+	// and after refitScene(true) the history is looked up where each surface point was.  Without a refit in between it is denoiseTemporal.
+	gmupt_trace_info denoiseTemporalMotion(float* deviceOut, size_t bytes, unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
+	std::vector<float> denoiseTemporalMotion(unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
 	void resetHistory();
 	// after Scene::setVertices: the tree's boxes and this renderer's traversal tables recomputed on the GPU for the moved vertices
-	// (gmupt_renderer_refit; the topology of the tree stays), the accumulation restarted, the temporal history dropped.  Throws like the
-	// other wrappers.
-	gmupt_refit_info refitScene();
+	// (gmupt_renderer_refit; the topology of the tree stays), the accumulation restarted, the temporal history dropped -- or kept
+	// (keepHistory) for denoiseTemporalMotion, which follows the moved surface.  Throws like the other wrappers.
+	gmupt_refit_info refitScene(bool keepHistory = false);
 
 private:
 	void createDevice(int hipDevice);

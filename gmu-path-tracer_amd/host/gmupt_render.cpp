@@ -83,6 +83,7 @@ int main(int argc, char** argv)
 	std::string verticesFile;
 	std::string aovPrefix; unsigned aovSamples = 1;
 	std::string denoisePrefix;
+	std::string temporalPrefix;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
 		auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -108,6 +109,7 @@ int main(int argc, char** argv)
 		else if (a == "--aov-samples") aovSamples = std::strtoul(next(), nullptr, 10);
 		else if (a == "--denoise") denoisePrefix = next();
 		else if (a == "--vertices") verticesFile = next();
+		else if (a == "--temporal") temporalPrefix = next();
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -116,6 +118,8 @@ int main(int argc, char** argv)
 			            "             [--pick X,Y]   after the frames: triangle / material / light sphere under whole-frame pixel (X, Y), one JSON line\n"
 			            "             [--aov PREFIX [--aov-samples S]]   after the frames: the AOV buffers of the camera, S = 1..8 samples per axis (default 1):\n"
 			            "                            PREFIX_albedo.pfm, PREFIX_normal.pfm (PF), PREFIX_depth.pfm (Pf), PREFIX.aov (64-byte gmupt_aov records); not with --ranks\n"
+			            "             [--temporal PREFIX] the temporal preview after the frames (PREFIX.pfm); with --vertices the frames are rendered on the loaded pose first,\n"
+			            "                                 then on the moved one, and the preview keeps its history across the refit (Renderer::denoiseTemporalMotion)\n"
 			            "             [--vertices FILE]   before the frames: moved positions of all vertices (raw float32 xyz), refitted on the GPU; not with --ranks\n"
 			            "             [--denoise PREFIX [--aov-samples S]]   after the frames: the frame through the a-trous denoiser guided by the AOV buffers\n"
 			            "                            (S samples per axis): PREFIX.pfm (PF) and PREFIX.png (8-bit, truncated like --capture); not with --ranks\n");
@@ -186,6 +190,8 @@ int main(int argc, char** argv)
 		}
 		if (!aovPrefix.empty() && ranks > 1)
 			throw std::invalid_argument("--aov renders the AOV buffers of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
+		if (!temporalPrefix.empty() && ranks > 1)
+			throw std::invalid_argument("--temporal previews the frame of a single process: it cannot be combined with --ranks N > 1");
 		if (!denoisePrefix.empty() && ranks > 1)
 			throw std::invalid_argument("--denoise filters the frame of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
 		if (!verticesFile.empty() && ranks > 1)
@@ -217,6 +223,10 @@ int main(int argc, char** argv)
 			return 0;
 		}
 		Renderer renderer(nullptr, { w, h }, scene, 0, pool, live);
+		if (!verticesFile.empty() && !temporalPrefix.empty()) {   // the history of the loaded pose, which the preview after the refit follows
+			for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
+			renderer.denoiseTemporalMotion(aovSamples);
+		}
 		if (!verticesFile.empty()) {
 			std::FILE* f = std::fopen(verticesFile.c_str(), "rb");
 			if (!f) throw std::runtime_error("cannot read " + verticesFile);
@@ -225,7 +235,7 @@ int main(int argc, char** argv)
 			for (size_t n; (n = std::fread(chunk, sizeof(float), 3072, f)) > 0;) xyz.insert(xyz.end(), chunk, chunk + n);
 			std::fclose(f);
 			renderer.scene().setVertices(xyz);
-			const gmupt_refit_info info = renderer.refitScene();
+			const gmupt_refit_info info = renderer.refitScene(!temporalPrefix.empty());
 			std::printf("{\"refit\": {\"rebuilt\": %u, \"reason\": %u, \"levels\": %u, \"opened_nodes\": %u, \"ms\": %.6g}}\n", info.rebuilt, info.reason, info.levels, info.opened_nodes, info.ms);
 		}
 		for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
@@ -263,6 +273,11 @@ int main(int argc, char** argv)
 			}
 			if (!gmupt::writePngRGBA8(denoisePrefix + ".png", png.data(), w, h)) throw std::runtime_error("Failed to write " + denoisePrefix + ".png");
 			std::printf("denoise %s: %ux%u, %u aov samples\n", denoisePrefix.c_str(), w, h, aovSamples);
+		}
+		if (!temporalPrefix.empty()) {
+			const std::vector<float> img = renderer.denoiseTemporalMotion(aovSamples);
+			writePfmFile(temporalPrefix + ".pfm", img, w, h);
+			std::printf("temporal %s: %ux%u, %u aov samples\n", temporalPrefix.c_str(), w, h, aovSamples);
 		}
 		if (!pfm.empty()) renderer.writePfm(pfm);
 		if (!dump.empty()) {

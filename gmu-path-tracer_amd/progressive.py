@@ -21,7 +21,7 @@ def to_rgba8(frame):
 
 
 class ProgressiveSession:
-    def __init__(self, renderer, camera, width, height, rank=0, world=1, dist=None, preview_every=32, on_preview=None):
+    def __init__(self, renderer, camera, width, height, rank=0, world=1, dist=None, preview_every=32, on_preview=None, motion=False):
         self.renderer, self.camera = renderer, camera
         self.width, self.height = width, height
         self.rank, self.world, self.dist = rank, world, dist
@@ -29,6 +29,7 @@ class ProgressiveSession:
         self.frames = 0
         self.previews = 0
         self.temporal = None   # the history handle of denoised_temporal, created on first use
+        self.motion = bool(motion)   # denoised_temporal goes through the motion entry point (also set by set_vertices(keep_history=True))
 
     # ---- events (applied before the next frame, like the GUI callbacks of the reference)
     def move_camera(self, mouse_dx=0.0, mouse_dy=0.0, w=False, s=False, a=False, d=False):
@@ -42,11 +43,14 @@ class ProgressiveSession:
         if self.temporal is not None:
             self.temporal.reset()                    # the history was lit by the old lights
 
-    def set_vertices(self, scene_buffers, verts, normals=None):
+    def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False):
         """The geometry moved (same vertex count, same triangles): upload the vertices, and `normals` (when given) into the property
         records, refit the tree and the renderer's traversal tables on the GPU (gmupt_renderer_refit), restart the accumulation.  The
-        temporal history shows the old surface and is dropped.  scene_buffers: the capi.SceneBuffers the renderer is bound to.
-        Returns the refit info dict."""
+        temporal history shows the old surface and is dropped; with keep_history=True it is kept, and denoised_temporal() from then on
+        looks it up where each surface point was (gmupt_render_denoised_temporal_motion).  The first such call still drops a history
+        that earlier denoised_temporal() calls wrote, because its record sets carry no vertex pose; ProgressiveSession(..., motion=True)
+        uses the motion entry point from the first preview on, so that nothing is dropped.  scene_buffers: the capi.SceneBuffers the
+        renderer is bound to.  Returns the refit info dict."""
         scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
         if normals is not None:
             from . import capi
@@ -55,7 +59,13 @@ class ProgressiveSession:
             scene_buffers.props.update(props)
         info = self.renderer.refit()
         self.camera.reset_accumulation()
-        if self.temporal is not None:
+        if keep_history and not self.motion:
+            # from here on the previews go through the motion entry point.  Record sets that the plain entry point wrote carry no
+            # pose and would be reprojected onto the moved surface as if it stood still: drop them once, as the default does
+            if self.temporal is not None:
+                self.temporal.reset()
+            self.motion = True
+        elif not keep_history and self.temporal is not None:
             self.temporal.reset()
         return info
 
@@ -98,7 +108,8 @@ class ProgressiveSession:
         if self.temporal is None:
             from . import capi
             self.temporal = capi.Temporal(self.renderer)
-        return self.renderer.denoise_temporal(self.temporal, aov_samples, **params).cpu().numpy()
+        call = self.renderer.denoise_temporal_motion if self.motion else self.renderer.denoise_temporal
+        return call(self.temporal, aov_samples, **params).cpu().numpy()
 
     # ---- frames
     def frame(self, dt=0.0):

@@ -495,6 +495,61 @@ int gmupt_bvh_refit_host(gmupt_bvh_node* nodes, uint32_t num_nodes, const gmupt_
                          const float* verts, uint32_t num_verts, uint32_t threads);
 int gmupt_renderer_refit(gmupt_renderer* r, gmupt_refit_info* info /* may be NULL */);
 
+/* ---- motion: temporal reuse across refits -- the history is looked up where the surface point WAS (the other half of SVGF's temporal
+ * stage, Schied et al. 2017, section 4.1).  Opt-in: every entry point above behaves as before. ----
+ * Motion record (gmupt_motion, 16 bytes, one per pixel of the renderer's rectangle).  For a pixel whose centre ray (k = 0 of gmupt_aov_ray)
+ * hits triangle record T with barycentrics (u, v) and no nearer light sphere, p0, p1, p2 the vertices T.v[0..2] of the bound vertex buffer
+ * and q0, q1, q2 the same indices of the caller's array of PREVIOUS vertices, binary32, no contraction, per component:
+ *     w      = (1.0f - u) - v
+ *     b_now  = (w * p0 + u * p1) + v * p2
+ *     b_prev = (w * q0 + u * q1) + v * q2
+ *     prev_position = (b_prev == b_now) ? aov.position : aov.position + (b_prev - b_now)
+ *     flags  = 1
+ *   Every other pixel (miss, light sphere): all zero.  The displacement form makes a triangle whose vertices did not move give
+ *   prev_position == aov.position bit for bit (the ?: also keeps a -0.0f component): an unmoved scene takes exactly the existing path.
+ * gmupt_render_aovs_motion: gmupt_render_aovs (k_aov_raygen, the ray cast, k_aov_resolve, all unchanged; aov_out is bit for bit that
+ *   call's output) plus k_mv_resolve per chunk on the same hits.  prev_verts: DEVICE memory, 3 floats per vertex, 4-byte aligned; num_verts
+ *   must equal the bound vertex count.  motion_out: DEVICE memory, 16-byte aligned, motion_bytes >= width * height * 16.  Errors follow
+ *   gmupt_render_aovs; a NULL or misaligned prev_verts / motion_out, too few bytes or another vertex count: GMUPT_ERR_INVALID_ARGUMENT.
+ * gmupt_motion_host: the rule on host arrays, the reference of the kernel.  hits: the n centre-ray hits (gmupt_trace_rays on the
+ *   gmupt_aov_ray rays gives the AOV's own), aov: their records.  Errors: NULL arrays, a hit triangle outside [0, num_tris), a vertex index
+ *   of a hit triangle outside [0, num_verts) (GMUPT_ERR_INVALID_ARGUMENT).
+ * Integration with a motion plane: with a record of flags == 1 the integration of gmupt_temporal_* above changes in two places and nowhere
+ *   else: the point projected into the previous camera is prev_position instead of x_p, and the plane test of a tap is
+ *   |dot3(n_p, x_q - prev_position)| <= plane_dist * z_p (the tap's record holds its position in the previous pose; the current normal
+ *   stands in for the previous one, and min_normal_cos bounds what is accepted).  The new record still stores x_p, the current pose, so
+ *   the next call's motion plane lines up with it.  With flags == 0, or without a motion plane, the pixel is the arithmetic above.
+ *   gmupt_temporal_integrate_motion_host: gmupt_temporal_integrate_host plus `motion` (width * height records; NULL = that function, bit
+ *   for bit).  gmupt_temporal_denoise_image_motion: gmupt_temporal_denoise_image plus a DEVICE `motion` pointer (16-byte aligned; NULL =
+ *   that function), for callers who bring gathered frames and their own motion plane; k_tp_integrate_mv takes the place of k_tp_integrate.
+ *   The epoch rule is unchanged; the motion plane must describe the step from the pose of the FROZEN set to the image's pose.
+ * gmupt_render_denoised_temporal_motion: gmupt_render_denoised_temporal that keeps the vertex pose of each record set.
+ *   The renderer has a geometry generation (host bookkeeping): gmupt_renderer_refit advances it, gmupt_renderer_bind_scene starts a new
+ *   binding.  FROZEN and LAST each carry the generation and a device snapshot of the bound vertex buffer (12 bytes per vertex) taken by the
+ *   call that wrote their records; the fold swaps the snapshots with the record sets.  A snapshot is a device-to-device copy on the
+ *   renderer's stream, taken only when LAST's generation differs from the renderer's: once per refit, not per call.  When FROZEN's
+ *   generation differs from the renderer's, the call runs gmupt_render_aovs_motion against FROZEN's snapshot and integrates with the
+ *   motion plane (16 more bytes per pixel of scratch); when it is equal the call is exactly gmupt_render_denoised_temporal.  A FROZEN set
+ *   without a snapshot (written by gmupt_render_denoised_temporal or gmupt_temporal_denoise_image), of another binding or of another
+ *   vertex count integrates without a motion plane.  gmupt_temporal_reset and gmupt_temporal_destroy free the snapshots.  The frame, path
+ *   state, queues, counters and gmupt_get_stats stay untouched.  Errors and info as gmupt_render_denoised_temporal. */
+typedef struct { float prev_position[3]; uint32_t flags; } gmupt_motion;   /* 16 bytes */
+int gmupt_render_aovs_motion(gmupt_renderer* r, uint32_t samples, const float* prev_verts, uint32_t num_verts, gmupt_aov* aov_out, size_t aov_bytes,
+                             gmupt_motion* motion_out, size_t motion_bytes, gmupt_trace_info* info /* may be NULL */);
+int gmupt_motion_host(const gmupt_hit* hits, const gmupt_aov* aov, size_t n, const gmupt_triangle* tris, uint32_t num_tris,
+                      const float* verts_now, const float* verts_prev, uint32_t num_verts, gmupt_motion* out);
+int gmupt_temporal_integrate_motion_host(const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion /* may be NULL */,
+                                         uint32_t width, uint32_t height,
+                                         const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
+                                         uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
+                                         float* out_rgba, gmupt_history* out_history, uint32_t threads);
+int gmupt_temporal_denoise_image_motion(gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion /* may be NULL */,
+                                        const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                                        int new_accumulation, const gmupt_temporal_params* p, float* out_rgba, size_t out_bytes,
+                                        float* ms /* may be NULL */);
+int gmupt_render_denoised_temporal_motion(gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
+                                          float* out_rgba, size_t bytes, gmupt_trace_info* info /* may be NULL */);
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);
