@@ -218,6 +218,9 @@ SYMBOLS = {
     "gmupt_debug_write_framebuffer": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_run_stage": (C.c_int, [_P, C.c_int]),
     "gmupt_debug_detmath": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_uint32]),
+    "gmupt_debug_travtables_build": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "gmupt_debug_travtables_data": (_P, [_P, C.c_int, C.POINTER(C.c_size_t)]),
+    "gmupt_debug_travtables_destroy": (None, [_P]),
     "gmupt_sbvh_default_params": (None, [C.POINTER(SbvhParams)]),
     "gmupt_sbvh_build": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(SbvhParams), C.POINTER(_P)]),
     "gmupt_sbvh_num_nodes": (C.c_uint32, [_P]),
@@ -972,6 +975,28 @@ def bvh_refit_host(nodes, tris, verts, threads=16):
     verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
     _check(lib().gmupt_bvh_refit_host(_ptr(out), out.shape[0], _ptr(tris), tris.shape[0], _ptr(verts), verts.shape[0], threads))
     return out
+
+
+TRAVTABLE_KINDS = ("node64", "tri48", "tripair", "pair_ref", "wnode", "rec64", "scalars", "level_nodes", "level_off", "node_map", "wide_map", "opened")
+
+
+def travtables(nodes, tris, verts, want_wide=True, top_order_bfs=False, node_pairing=True):
+    """gmupt_debug_travtables_*: the traversal tables and refit maps a bind would build from these host arrays, no device involved.
+    Returns {kind: uint8 array (a copy)} for TRAVTABLE_KINDS."""
+    nodes = np.ascontiguousarray(nodes); tris = np.ascontiguousarray(tris)
+    verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    h = _P()
+    _check(lib().gmupt_debug_travtables_build(_ptr(nodes), nodes.shape[0], _ptr(tris), tris.shape[0], _ptr(verts), verts.shape[0],
+                                              int(want_wide), int(top_order_bfs), int(node_pairing), C.byref(h)))
+    try:
+        out = {}
+        for which, kind in enumerate(TRAVTABLE_KINDS):
+            n = C.c_size_t(0)
+            p = lib().gmupt_debug_travtables_data(h, which, C.byref(n))
+            out[kind] = np.frombuffer(C.string_at(p, n.value), np.uint8).copy() if p and n.value else np.zeros(0, np.uint8)
+        return out
+    finally:
+        lib().gmupt_debug_travtables_destroy(h)
 
 
 def sbvh_build(verts, indices, vertex_material=None, params=None):

@@ -7,6 +7,7 @@
 #include "pt_temporal.hpp"
 #include "pt_refit.hpp"
 #include "pt_motion.hpp"
+#include "pt_travtables.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
 #include "../host/TextureLoader.hpp"
@@ -14,6 +15,7 @@
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -268,7 +270,7 @@ struct gmupt_renderer {
     uint64_t accumGeneration = 0;
     // motion (gmupt_render_denoised_temporal_motion): which binding the renderer has and how many refits it has seen (host only)
     uint64_t bindingId = 0, geomGeneration = 0;
-    // refit (gmupt_renderer_refit): the buffers of the binding with their element counts, and what build_traversal_copy knows about the
+    // refit (gmupt_renderer_refit): the buffers of the binding with their element counts, and what build_trav_tables (pt_travtables.hpp) knows about the
     // topology of its tables -- host vectors, uploaded into one allocation (rfDev) by the first refit after a bind
     const gmupt_buffer* boundNodes = nullptr; const gmupt_buffer* boundTris = nullptr; const gmupt_buffer* boundVerts = nullptr;
     size_t boundElems[3] = { 0, 0, 0 };
@@ -276,6 +278,9 @@ struct gmupt_renderer {
     void* rfDev = nullptr;
     hipEvent_t rfEv[2] = { nullptr, nullptr };
 };
+
+// the renderer's six device tables, in the order build_traversal_copy fills them
+static std::array<void**, 6> trav_tables(gmupt_renderer* r) { return { &r->travNodes, &r->travTris, &r->travRecs, &r->travWide, &r->travPairs, &r->travPairRef }; }
 
 static int dev_alloc(gmupt_renderer* r, void** ptr, size_t bytes, int fill)
 {
@@ -313,12 +318,7 @@ extern "C" void gmupt_renderer_destroy(gmupt_renderer* r)
     if (r->dnInput) (void)hipFree(r->dnInput);
     if (r->p.fb) (void)hipFree(r->p.fb);
     if (r->p.listHead) (void)hipFree(r->p.listHead);
-    if (r->travNodes) (void)hipFree(r->travNodes);
-    if (r->travTris) (void)hipFree(r->travTris);
-    if (r->travRecs) (void)hipFree(r->travRecs);
-    if (r->travWide) (void)hipFree(r->travWide);
-    if (r->travPairs) (void)hipFree(r->travPairs);
-    if (r->travPairRef) (void)hipFree(r->travPairRef);
+    for (void** t : trav_tables(r)) if (*t) (void)hipFree(*t);
     if (r->stream) (void)hipStreamDestroy(r->stream);
     delete r;
 }
@@ -410,7 +410,18 @@ extern "C" int gmupt_renderer_create(gmupt_device* dev, const gmupt_renderer_des
     return GMUPT_OK;
 }
 
-// Packs the reference-layout BVH into the traversal records of pt_device.hpp (Node64 / Tri48).  Host-side, once per bind.
+// GMUPT_TOP_ORDER=bfs and GMUPT_NODE_PAIRING=0 are A/B switches of the numbering (pt_travtables.cpp); results do not depend on them
+static TravOptions trav_options(bool wantWide)
+{
+    const char* order = std::getenv("GMUPT_TOP_ORDER");
+    const char* pairing = std::getenv("GMUPT_NODE_PAIRING");
+    TravOptions o;
+    o.wantWide = wantWide; o.topOrderBfs = order && std::strcmp(order, "bfs") == 0; o.nodePairing = !(pairing && std::atoi(pairing) == 0);
+    o.topCapacity = traversal_top_capacity; o.wideTopCapacity = traversal_wide_top_capacity();
+    return o;
+}
+
+// Downloads the bound tree, has pt_travtables.cpp build the traversal tables, uploads them.  Once per bind (and per refit that rebuilds).
 static int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, const gmupt_buffer* trisB, const gmupt_buffer* vertsB)
 {
     HIP_TRY(hipSetDevice(r->dev->id));
@@ -423,331 +434,37 @@ static int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, c
     if (R) HIP_TRY(hipMemcpy(tris.data(), trisB->dptr, R * sizeof(gmupt_triangle), hipMemcpyDeviceToHost));
     if (V) HIP_TRY(hipMemcpy(verts.data(), vertsB->dptr, V * 12, hipMemcpyDeviceToHost));
 
-    // validate what the kernels will index with (a malformed tree must not become an out-of-bounds access on the GPU)
-    std::vector<int32_t> innerIndex(N, -1);
-    int32_t numInner = 0;
-    for (size_t i = 0; i < N; i++) {
-        const gmupt_bvh_node& n = nodes[i];
-        if (n.isLeaf) {
-            if (n.left < 0 || n.right < n.left || (size_t)n.right > R) return fail(GMUPT_ERR_INVALID_ARGUMENT, "bind_scene: leaf %zu has triangle range [%d, %d) outside [0, %zu)", i, n.left, n.right, R);
-        } else {
-            if (n.left <= (int32_t)i || n.right <= (int32_t)i || (size_t)n.left >= N || (size_t)n.right >= N) return fail(GMUPT_ERR_INVALID_ARGUMENT, "bind_scene: inner node %zu has children (%d, %d) outside (%zu, %zu)", i, n.left, n.right, i, N);
-            numInner++;
-        }
-    }
-    std::vector<int32_t> depth(N, 0);
-    int32_t maxDepth = 0;
-    for (size_t i = 0; i < N; i++) if (!nodes[i].isLeaf) { depth[(size_t)nodes[i].left] = depth[i] + 1; depth[(size_t)nodes[i].right] = depth[i] + 1; }
-    for (size_t i = 0; i < N; i++) maxDepth = std::max(maxDepth, depth[i]);
-    // packed numbering: first the inner nodes that the ray-cast kernels keep in LDS (the part of the tree every ray walks), then the
-    // remaining inner nodes.  How many fit depends on the kernel instantiation this tree will run: a tree that needs the spilling stack
-    // keeps fewer stack entries and more nodes in LDS (pt_traverse_deferred.hpp: kDefLdsStack / kDefLdsTop)
-    const size_t topCapacity = traversal_top_capacity((uint32_t)maxDepth);
-    {
-        // the LDS-resident set grows from the root by always expanding the frontier node with the largest surface area (the usual
-        // visit-probability estimate); GMUPT_TOP_ORDER=bfs selects plain breadth-first order (0.5 % slower on the bench scene)
-        std::vector<int32_t> bfs; bfs.reserve(topCapacity);
-        const char* order = std::getenv("GMUPT_TOP_ORDER");
-        if (!(order && std::strcmp(order, "bfs") == 0)) {
-            auto area = [&](int32_t i) { const gmupt_bvh_node& n = nodes[(size_t)i]; const double dx = (double)n.max[0] - n.min[0], dy = (double)n.max[1] - n.min[1], dz = (double)n.max[2] - n.min[2]; return dx * dy + dy * dz + dz * dx; };
-            std::vector<std::pair<double, int32_t>> frontier;
-            if (!nodes[0].isLeaf) frontier.push_back({ area(0), 0 });
-            while (!frontier.empty() && bfs.size() < topCapacity) {
-                size_t best = 0;
-                for (size_t k = 1; k < frontier.size(); k++) if (frontier[k].first > frontier[best].first || (frontier[k].first == frontier[best].first && frontier[k].second < frontier[best].second)) best = k;
-                const int32_t v = frontier[best].second;
-                frontier.erase(frontier.begin() + (long)best);
-                bfs.push_back(v);
-                const gmupt_bvh_node& n = nodes[(size_t)v];
-                if (!nodes[(size_t)n.left].isLeaf) frontier.push_back({ area(n.left), n.left });
-                if (!nodes[(size_t)n.right].isLeaf) frontier.push_back({ area(n.right), n.right });
-            }
-        } else {
-            if (!nodes[0].isLeaf) bfs.push_back(0);
-            for (size_t h = 0; h < bfs.size() && bfs.size() < topCapacity; h++) {
-                const gmupt_bvh_node& n = nodes[(size_t)bfs[h]];
-                if (!nodes[(size_t)n.left].isLeaf && bfs.size() < topCapacity) bfs.push_back(n.left);
-                if (!nodes[(size_t)n.right].isLeaf && bfs.size() < topCapacity) bfs.push_back(n.right);
-            }
-        }
-        int32_t nextIdx = 0;
-        for (int32_t v : bfs) innerIndex[(size_t)v] = nextIdx++;
-        r->p.trav.topCountDeep = (uint32_t)bfs.size();                                        // what the spilling-stack instantiations keep in LDS
-        r->p.trav.topCount = (uint32_t)std::min(bfs.size(), (size_t)kTopTreeNodes);             // what every other kernel keeps (a prefix of the same order)
-        // The rest of the inner nodes.  Every memory-side read of the ray cast is a whole 128-byte line (TCC_EA0_RDREQ_128B is all of
-        // TCC_EA0_RDREQ: profiles/r02_micro/fetch_size_calibration.txt), i.e. TWO 64-byte records.  A node therefore shares its line with the
-        // inner child a ray is most likely to visit next (the one with the larger surface area): that visit then finds its record in the
-        // cache.  Nodes without such a partner share a line with the next one of their kind in flatten order (usually a sibling or cousin).
-        // GMUPT_NODE_PAIRING=0 keeps the plain flatten order (A/B timing; results do not depend on the numbering).
-        const char* pairing = std::getenv("GMUPT_NODE_PAIRING");
-        if (pairing && std::atoi(pairing) == 0) {
-            for (size_t i = 0; i < N; i++) if (!nodes[i].isLeaf && innerIndex[i] < 0) innerIndex[i] = nextIdx++;
-        } else {
-            auto area = [&](int32_t i) { const gmupt_bvh_node& n = nodes[(size_t)i]; const double dx = (double)n.max[0] - n.min[0], dy = (double)n.max[1] - n.min[1], dz = (double)n.max[2] - n.min[2]; return dx * dy + dy * dz + dz * dx; };
-            if (nextIdx & 1) nextIdx++;                                   // lines start at even records (an unused record keeps the parity)
-            std::vector<int32_t> partner(N, -1), singles;
-            std::vector<uint8_t> taken(N, 0);
-            for (size_t i = 0; i < N; i++) {                              // parents come before their children in the reference numbering
-                if (nodes[i].isLeaf || innerIndex[i] >= 0 || taken[i]) continue;
-                const int32_t l = nodes[i].left, rr = nodes[i].right;
-                const bool li = !nodes[(size_t)l].isLeaf && innerIndex[(size_t)l] < 0, ri = !nodes[(size_t)rr].isLeaf && innerIndex[(size_t)rr] < 0;
-                int32_t c = -1;
-                if (li && ri) c = area(l) >= area(rr) ? l : rr; else if (li) c = l; else if (ri) c = rr;
-                if (c >= 0) { partner[i] = c; taken[(size_t)c] = 1; } else singles.push_back((int32_t)i);
-            }
-            for (size_t i = 0; i < N; i++) if (partner[i] >= 0) { innerIndex[i] = nextIdx++; innerIndex[(size_t)partner[i]] = nextIdx++; }
-            for (int32_t v : singles) innerIndex[(size_t)v] = nextIdx++;
-        }
-        numInner = nextIdx;   // records of the packed array (one may be an unused filler)
-    }
-    for (size_t i = 0; i < R; i++) {
-        for (int k = 0; k < 3; k++)
-            if (tris[i].v[k] < 0 || (size_t)tris[i].v[k] >= V) return fail(GMUPT_ERR_INVALID_ARGUMENT, "bind_scene: triangle record %zu references vertex %d of %zu", i, tris[i].v[k], V);
-        if (tris[i].materialID >= (uint32_t)GMUPT_MAX_LIGHTS) return fail(GMUPT_ERR_INVALID_ARGUMENT, "bind_scene: triangle record %zu has material %u (the material table holds %d entries, logic.hlsl:8)", i, tris[i].materialID, GMUPT_MAX_LIGHTS);
-    }
+    // nothing of the renderer or on the device is touched before the tables exist
+    TravTables tt;
+    const std::string err = build_trav_tables(nodes.data(), N, tris.data(), R, verts.data(), V, trav_options(r->travMode == 70), tt);
+    if (!err.empty()) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s", err.c_str());
 
-    auto desc = [&](int32_t child) -> int32_t {
-        const gmupt_bvh_node& c = nodes[(size_t)child];
-        if (!c.isLeaf) return innerIndex[(size_t)child];
-        // an empty leaf cannot be expressed by "first record + last flag": point it at a degenerate sentinel record
-        return ~(c.right > c.left ? c.left : (int32_t)R);
-    };
-    std::vector<Node64> packed((size_t)numInner ? (size_t)numInner : 1);
-    std::memset(packed.data(), 0, packed.size() * sizeof(Node64));
-    for (size_t i = 0; i < N; i++) {
-        if (nodes[i].isLeaf) continue;
-        const gmupt_bvh_node& L = nodes[(size_t)nodes[i].left];
-        const gmupt_bvh_node& Rn = nodes[(size_t)nodes[i].right];
-        Node64& o = packed[(size_t)innerIndex[i]];
-        o.a[0] = L.min[0]; o.a[1] = L.min[1]; o.a[2] = L.min[2]; o.a[3] = L.max[0];
-        o.b[0] = L.max[1]; o.b[1] = L.max[2]; o.b[2] = Rn.min[0]; o.b[3] = Rn.min[1];
-        o.c[0] = Rn.min[2]; o.c[1] = Rn.max[0]; o.c[2] = Rn.max[1]; o.c[3] = Rn.max[2];
-        o.d[0] = desc(nodes[i].left); o.d[1] = desc(nodes[i].right); o.d[2] = depth[i]; o.d[3] = 0;
-    }
-    std::vector<Tri48> ptris(R + 1);
-    std::memset(ptris.data(), 0, ptris.size() * sizeof(Tri48));
-    for (size_t i = 0; i < R; i++) {
-        const float* v0 = &verts[3 * (size_t)tris[i].v[0]]; const float* v1 = &verts[3 * (size_t)tris[i].v[1]]; const float* v2 = &verts[3 * (size_t)tris[i].v[2]];
-        Tri48& t = ptris[i];
-        t.r0[0] = v0[0]; t.r0[1] = v0[1]; t.r0[2] = v0[2];
-        t.r0[3] = v1[0] - v0[0]; t.r1[0] = v1[1] - v0[1]; t.r1[1] = v1[2] - v0[2];   // e1 = v1 - v0 (extensionRayCast.hlsl:40)
-        t.r1[2] = v2[0] - v0[0]; t.r1[3] = v2[1] - v0[1]; t.r2[0] = v2[2] - v0[2];   // e2 = v2 - v0 (:41)
-    }
-    const uint32_t one = 1u;
-    for (size_t i = 0; i < N; i++)
-        if (nodes[i].isLeaf && nodes[i].right > nodes[i].left) std::memcpy(&ptris[(size_t)nodes[i].right - 1].r2[1], &one, 4);
-    std::memcpy(&ptris[R].r2[1], &one, 4); // sentinel: all-zero triangle (det = 0, rejected), last flag set
-
-    // word 10 of a triangle record: the number of the first reference with the same (v0, v1, v2, material) -- duplicated references of one
-    // triangle (spatial splits) produce identical hit records, so a tie in t between them is no tie (pt_traverse_wide.hip)
-    const bool wantWide = r->travMode == 70;
-    if (wantWide) {
-        struct Key { int32_t v[3]; uint32_t mat; uint32_t idx; };
-        std::vector<Key> keys(R);
-        for (size_t i = 0; i < R; i++) keys[i] = { { tris[i].v[0], tris[i].v[1], tris[i].v[2] }, tris[i].materialID, (uint32_t)i };
-        std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
-            if (a.v[0] != b.v[0]) return a.v[0] < b.v[0];
-            if (a.v[1] != b.v[1]) return a.v[1] < b.v[1];
-            if (a.v[2] != b.v[2]) return a.v[2] < b.v[2];
-            if (a.mat != b.mat) return a.mat < b.mat;
-            return a.idx < b.idx; });
-        for (size_t i = 0; i < R;) {
-            size_t j = i;
-            while (j < R && keys[j].v[0] == keys[i].v[0] && keys[j].v[1] == keys[i].v[1] && keys[j].v[2] == keys[i].v[2] && keys[j].mat == keys[i].mat) {
-                std::memcpy(&ptris[keys[j].idx].r2[2], &keys[i].idx, 4);
-                j++;
-            }
-            i = j;
-        }
-        const uint32_t none = 0xFFFFFFFFu;
-        std::memcpy(&ptris[R].r2[2], &none, 4);
-    }
-
-    // 4-wide collapse (WNode, pt_device.hpp): the two children of an inner node, the inner one with the largest surface area replaced by
-    // ITS children until four slots are taken; every inner slot becomes a wide node in turn.  Only built when every child box lies inside
-    // its parent's box (what a bounding-volume hierarchy is; the wide walk's equivalence to the binary one rests on it).
-    // the leaves as triangle pairs (TriPair, pt_device.hpp): consecutive references of a leaf two by two
-    std::vector<TriPair> pairs;
-    std::vector<uint32_t> pairRef;
-    std::vector<int32_t> leafPair(N, -1);       // first pair of every leaf node
-    if (wantWide) {
-        pairs.reserve(R / 2 + N / 2 + 2); pairRef.reserve(R + N + 4);
-        auto put = [&](TriPair& pr, int slot, size_t ref) {
-            const Tri48& t = ptris[ref];
-            const float c[9] = { t.r0[0], t.r0[1], t.r0[2], t.r0[3], t.r1[0], t.r1[1], t.r1[2], t.r1[3], t.r2[0] };   // v0.xyz, e1.xyz, e2.xyz
-            for (int k = 0; k < 9; k++) pr.w[2 * k + slot] = c[k];
-        };
-        const uint32_t one32 = 1u;
-        for (size_t i = 0; i < N; i++) {
-            if (!nodes[i].isLeaf) continue;
-            leafPair[i] = (int32_t)pairs.size();
-            const int32_t a = nodes[i].left, b = nodes[i].right;
-            for (int32_t k = a; k < b || k == a; k += 2) {          // (an empty leaf gets one all-zero pair)
-                TriPair pr; std::memset(&pr, 0, sizeof(pr));
-                uint32_t r0 = 0xFFFFFFFFu, r1 = 0xFFFFFFFFu;
-                if (k < b) { put(pr, 0, (size_t)k); r0 = (uint32_t)k; }
-                if (k + 1 < b) { put(pr, 1, (size_t)k + 1); r1 = (uint32_t)k + 1; }
-                if (k + 2 >= b) std::memcpy(&pr.w[18], &one32, 4);
-                const uint32_t nrefs = (k < b ? 1u : 0u) + (k + 1 < b ? 1u : 0u); std::memcpy(&pr.w[19], &nrefs, 4);   // (statistics)
-                pairs.push_back(pr); pairRef.push_back(r0); pairRef.push_back(r1);
-            }
-        }
-    }
-
-    std::vector<WNode> wide;
-    std::vector<uint32_t> rfOpened, rfWideMap;   // refit: the nodes the collapse opened; 4 * wide node + slot -> reference node
-    uint32_t wideTop = 0, wideBound = 0;
-    bool contained = true;
-    for (size_t i = 0; i < N && contained && wantWide; i++) {
-        if (nodes[i].isLeaf) continue;
-        for (int32_t c : { nodes[i].left, nodes[i].right })
-            for (int k = 0; k < 3; k++)
-                if (!(nodes[(size_t)c].min[k] >= nodes[i].min[k] && nodes[(size_t)c].max[k] <= nodes[i].max[k] && nodes[(size_t)c].min[k] <= nodes[(size_t)c].max[k])) contained = false;
-    }
-    if (wantWide && contained && !nodes[0].isLeaf) {
-        auto area = [&](int32_t i) { const gmupt_bvh_node& n = nodes[(size_t)i]; const double dx = (double)n.max[0] - n.min[0], dy = (double)n.max[1] - n.min[1], dz = (double)n.max[2] - n.min[2]; return dx * dy + dy * dz + dz * dx; };
-        // Opening a slot drops ITS box test for the rays that reach its children.  "Child hit implies parent hit" holds for every ray
-        // unless a child is flat on an axis on which the parent is not, in the plane of one of the parent's faces (a ray with d = 0 on that
-        // axis that starts in this plane gets NaNs from the child's two planes -- no condition -- and +-inf from the parent's: a miss;
-        // pt_traverse_wide.hip).  Such a node keeps its own slot.
-        auto opens = [&](int32_t c) {
-            const gmupt_bvh_node& pn = nodes[(size_t)c];
-            for (int32_t x : { pn.left, pn.right }) {
-                const gmupt_bvh_node& cn = nodes[(size_t)x];
-                for (int k = 0; k < 3; k++)
-                    if (cn.min[k] == cn.max[k] && pn.min[k] != pn.max[k] && (cn.min[k] == pn.min[k] || cn.max[k] == pn.max[k])) return false;
-            }
-            return true;
-        };
-        struct Slots { int32_t s[4]; int n; int32_t bin; };
-        std::vector<Slots> created;                    // creation order: parents before children
-        std::vector<int32_t> createdOf(N, -1);
-        std::vector<int32_t> todo{ 0 };
-        rfOpened.clear();
-        while (!todo.empty()) {
-            const int32_t v = todo.back(); todo.pop_back();
-            Slots w; w.bin = v; w.n = 2; w.s[0] = nodes[(size_t)v].left; w.s[1] = nodes[(size_t)v].right; w.s[2] = w.s[3] = -1;
-            while (w.n < 4) {
-                int best = -1;
-                for (int k = 0; k < w.n; k++) if (!nodes[(size_t)w.s[k]].isLeaf && opens(w.s[k]) && (best < 0 || area(w.s[k]) > area(w.s[best]))) best = k;
-                if (best < 0) break;
-                const int32_t c = w.s[best];
-                rfOpened.push_back((uint32_t)c);
-                for (int k = w.n; k > best + 1; k--) w.s[k] = w.s[k - 1];
-                w.s[best] = nodes[(size_t)c].left; w.s[best + 1] = nodes[(size_t)c].right; w.n++;
-            }
-            createdOf[(size_t)v] = (int32_t)created.size();
-            created.push_back(w);
-            for (int k = w.n - 1; k >= 0; k--) if (!nodes[(size_t)w.s[k]].isLeaf) todo.push_back(w.s[k]);
-        }
-        const size_t W = created.size();
-        // numbering: the LDS-resident top first (grown from the root, largest surface area first), then creation order (depth-first)
-        std::vector<int32_t> number(W, -1);
-        int32_t nextW = 0;
-        {
-            std::vector<std::pair<double, int32_t>> frontier{ { area(0), 0 } };
-            const size_t cap = traversal_wide_top_capacity();
-            while (!frontier.empty() && (size_t)nextW < cap) {
-                size_t best = 0;
-                for (size_t k = 1; k < frontier.size(); k++) if (frontier[k].first > frontier[best].first || (frontier[k].first == frontier[best].first && frontier[k].second < frontier[best].second)) best = k;
-                const int32_t c = frontier[best].second;
-                frontier.erase(frontier.begin() + (long)best);
-                number[(size_t)c] = nextW++;
-                const Slots& w = created[(size_t)c];
-                for (int k = 0; k < w.n; k++) if (!nodes[(size_t)w.s[k]].isLeaf) frontier.push_back({ area(w.s[k]), createdOf[(size_t)w.s[k]] });
-            }
-            wideTop = (uint32_t)nextW;
-        }
-        for (size_t c = 0; c < W; c++) if (number[c] < 0) number[c] = nextW++;
-        wide.resize(W);
-        rfWideMap.assign(4 * W, kRfNone);
-        const float qnan = std::numeric_limits<float>::quiet_NaN();
-        for (size_t c = 0; c < W; c++) {
-            const Slots& w = created[c];
-            WNode& o = wide[(size_t)number[c]];
-            for (int k = 0; k < 4; k++) {
-                if (k < w.n) {
-                    const gmupt_bvh_node& b = nodes[(size_t)w.s[k]];
-                    for (int a = 0; a < 3; a++) { o.p[a][k] = b.min[a]; o.p[5 - a][k] = b.max[a]; }   // rows: min x, y, z, max z, y, x
-                    o.link[k] = b.isLeaf ? ~leafPair[(size_t)w.s[k]] : number[(size_t)createdOf[(size_t)w.s[k]]];
-                    rfWideMap[4 * (size_t)number[c] + (size_t)k] = (uint32_t)w.s[k];
-                } else {
-                    for (int a = 0; a < 6; a++) o.p[a][k] = qnan;      // never hit
-                    o.link[k] = (int32_t)0x80000000;
-                }
-            }
-            o.aux[0] = depth[(size_t)w.bin]; o.aux[1] = w.n; o.aux[2] = o.aux[3] = 0;
-        }
-        // most entries the inner stack of a walk can hold: every inner slot hit on every level, the deepest child visited last
-        std::vector<uint32_t> occ(W, 0);
-        for (size_t c = W; c-- > 0;) {
-            const Slots& w = created[c];
-            uint32_t inner = 0, deepest = 0;
-            for (int k = 0; k < w.n; k++) if (!nodes[(size_t)w.s[k]].isLeaf) { inner++; deepest = std::max(deepest, occ[(size_t)createdOf[(size_t)w.s[k]]]); }
-            occ[c] = inner ? inner - 1 + deepest : 0;
-        }
-        wideBound = occ[0];
-    }
-    if (r->travWide) { HIP_TRY(hipFree(r->travWide)); r->travWide = nullptr; }
-    if (!wide.empty()) {
-        HIP_TRY(hipMalloc(&r->travWide, wide.size() * sizeof(WNode)));
-        HIP_TRY(hipMemcpy(r->travWide, wide.data(), wide.size() * sizeof(WNode), hipMemcpyHostToDevice));
-    }
-    if (r->travPairs) { HIP_TRY(hipFree(r->travPairs)); r->travPairs = nullptr; }
-    if (r->travPairRef) { HIP_TRY(hipFree(r->travPairRef)); r->travPairRef = nullptr; }
-    if (!wide.empty()) {
-        HIP_TRY(hipMalloc(&r->travPairs, pairs.size() * sizeof(TriPair)));
-        HIP_TRY(hipMemcpy(r->travPairs, pairs.data(), pairs.size() * sizeof(TriPair), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&r->travPairRef, pairRef.size() * 4));
-        HIP_TRY(hipMemcpy(r->travPairRef, pairRef.data(), pairRef.size() * 4, hipMemcpyHostToDevice));
-    }
-    r->p.trav.pairs = (const TriPair*)r->travPairs; r->p.trav.pairRef = (const uint32_t*)r->travPairRef; r->p.trav.numPairs = (uint32_t)pairs.size();
-    r->p.trav.wnodes = (const WNode*)r->travWide; r->p.trav.wideCount = (uint32_t)wide.size(); r->p.trav.wideTopCount = wideTop; r->p.trav.wideStackBound = wideBound;
-    r->p.trav.wideRootDesc = 0;
-
-    if (r->travNodes) { HIP_TRY(hipFree(r->travNodes)); r->travNodes = nullptr; }
-    if (r->travTris) { HIP_TRY(hipFree(r->travTris)); r->travTris = nullptr; }
-    HIP_TRY(hipMalloc(&r->travNodes, packed.size() * sizeof(Node64)));
-    HIP_TRY(hipMalloc(&r->travTris, ptris.size() * sizeof(Tri48)));
-    HIP_TRY(hipMemcpy(r->travNodes, packed.data(), packed.size() * sizeof(Node64), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(r->travTris, ptris.data(), ptris.size() * sizeof(Tri48), hipMemcpyHostToDevice));
+    const bool haveWide = !tt.wide.empty();   // without a wide copy the pairs stay on the host
+    const void* recs = nullptr; size_t recBytes = 0;
 #ifdef GMUPT_VARIANTS
-    // unified 64-byte records for the cooperative kernels (rungs of the test build only)
-    std::vector<Rec64> recs(packed.size() + ptris.size());
-    std::memset(recs.data(), 0, recs.size() * sizeof(Rec64));
-    for (size_t i = 0; i < packed.size(); i++) std::memcpy(&recs[i], &packed[i], 64);
-    for (size_t i = 0; i < ptris.size(); i++) {
-        std::memcpy(&recs[packed.size() + i], &ptris[i], 48);
-        if (i < R) std::memcpy(&recs[packed.size() + i].q[12], &tris[i], 16); // (v0, v1, v2, materialID)
-    }
-    if (r->travRecs) { HIP_TRY(hipFree(r->travRecs)); r->travRecs = nullptr; }
-    HIP_TRY(hipMalloc(&r->travRecs, recs.size() * sizeof(Rec64)));
-    HIP_TRY(hipMemcpy(r->travRecs, recs.data(), recs.size() * sizeof(Rec64), hipMemcpyHostToDevice));
+    recs = tt.recs.data(); recBytes = tt.recs.size() * sizeof(Rec64);
 #endif
+    const struct { const void* data; size_t bytes; } up[6] = {      // in the order of trav_tables()
+        { tt.nodes.data(), tt.nodes.size() * sizeof(Node64) }, { tt.tris.data(), tt.tris.size() * sizeof(Tri48) }, { recs, recBytes },
+        { tt.wide.data(), tt.wide.size() * sizeof(WNode) }, { tt.pairs.data(), haveWide ? tt.pairs.size() * sizeof(TriPair) : 0 },
+        { tt.pairRef.data(), haveWide ? tt.pairRef.size() * 4 : 0 } };
+    const std::array<void**, 6> dst = trav_tables(r);
+    for (int k = 0; k < 6; k++) {
+        if (*dst[k]) { HIP_TRY(hipFree(*dst[k])); *dst[k] = nullptr; }
+        if (!up[k].bytes) continue;
+        HIP_TRY(hipMalloc(dst[k], up[k].bytes));
+        HIP_TRY(hipMemcpy(*dst[k], up[k].data, up[k].bytes, hipMemcpyHostToDevice));
+    }
     TravScene& t = r->p.trav;
-    t.recs = (const Rec64*)r->travRecs; t.triBase = (uint32_t)packed.size();
-    t.maxDepth = (uint32_t)maxDepth;
-    t.nodes = (const Node64*)r->travNodes; t.tris = (const Tri48*)r->travTris;
-    t.rootDesc = nodes[0].isLeaf ? ~(nodes[0].right > nodes[0].left ? nodes[0].left : (int32_t)R) : innerIndex[0];
-    for (int k = 0; k < 3; k++) { t.rootMin[k] = nodes[0].min[k]; t.rootMax[k] = nodes[0].max[k]; }
+    t.recs = (const Rec64*)r->travRecs; t.nodes = (const Node64*)r->travNodes; t.tris = (const Tri48*)r->travTris;
+    t.wnodes = (const WNode*)r->travWide; t.pairs = (const TriPair*)r->travPairs; t.pairRef = (const uint32_t*)r->travPairRef;
+    t.triBase = tt.s.triBase; t.rootDesc = tt.s.rootDesc; t.topCount = tt.s.topCount; t.topCountDeep = tt.s.topCountDeep; t.maxDepth = tt.s.maxDepth;
+    for (int k = 0; k < 3; k++) { t.rootMin[k] = tt.s.rootMin[k]; t.rootMax[k] = tt.s.rootMax[k]; }
+    t.wideCount = tt.s.wideCount; t.wideTopCount = tt.s.wideTopCount; t.wideStackBound = tt.s.wideStackBound; t.wideRootDesc = 0; t.numPairs = tt.s.numPairs;
 
     // what a refit needs to rewrite these tables in place (host vectors; the first gmupt_renderer_refit uploads them)
     if (r->rfDev) { HIP_TRY(hipFree(r->rfDev)); r->rfDev = nullptr; }
-    r->rfNodeMap.assign(packed.size(), kRfNone);
-    for (size_t i = 0; i < N; i++) if (!nodes[i].isLeaf) r->rfNodeMap[(size_t)innerIndex[i]] = (uint32_t)i;
-    {   // inner nodes by height (a leaf has height 0), lowest first: every node comes after its children, whatever the shape of the tree
-        std::vector<int32_t>& height = depth;                          // (the depths are not needed any more)
-        int32_t top = 0;
-        for (size_t i = N; i-- > 0;) { height[i] = nodes[i].isLeaf ? 0 : 1 + std::max(height[(size_t)nodes[i].left], height[(size_t)nodes[i].right]); top = std::max(top, height[i]); }
-        r->rfLevelOff.assign((size_t)top + 1, 0);
-        for (size_t i = 0; i < N; i++) if (height[i] > 0) r->rfLevelOff[(size_t)height[i]]++;
-        for (size_t h = 1; h <= (size_t)top; h++) r->rfLevelOff[h] += r->rfLevelOff[h - 1];    // rfLevelOff[h] = end of height h
-        r->rfLevelNodes.resize(r->rfLevelOff[(size_t)top]);
-        std::vector<uint32_t> at(r->rfLevelOff.begin(), r->rfLevelOff.end());
-        for (size_t i = N; i-- > 0;) if (height[i] > 0) r->rfLevelNodes[--at[(size_t)height[i]]] = (uint32_t)i;
-    }
-    if (wide.empty()) { rfWideMap.clear(); rfOpened.clear(); }
-    r->rfWideMap.swap(rfWideMap); r->rfOpened.swap(rfOpened);
+    r->rfLevelNodes.swap(tt.levelNodes); r->rfLevelOff.swap(tt.levelOff); r->rfNodeMap.swap(tt.nodeMap); r->rfWideMap.swap(tt.wideMap); r->rfOpened.swap(tt.opened);
     r->boundNodes = nodesB; r->boundTris = trisB; r->boundVerts = vertsB;
     r->boundElems[0] = N; r->boundElems[1] = R; r->boundElems[2] = V;
     return GMUPT_OK;
@@ -827,21 +544,50 @@ extern "C" int gmupt_bvh_refit_host(gmupt_bvh_node* nodes, uint32_t num_nodes, c
                                     const float* verts, uint32_t num_verts, uint32_t threads)
 {
     if (!nodes || num_nodes == 0 || (!tris && num_tris) || (!verts && num_verts)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_bvh_refit_host: null or empty array");
-    const size_t N = num_nodes, R = num_tris, V = num_verts;
-    for (size_t i = 0; i < N; i++) {
-        const gmupt_bvh_node& n = nodes[i];
-        if (n.isLeaf) {
-            if (n.left < 0 || n.right < n.left || (size_t)n.right > R) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_bvh_refit_host: leaf %zu has triangle range [%d, %d) outside [0, %zu)", i, n.left, n.right, R);
-        } else if (n.left <= (int32_t)i || n.right <= (int32_t)i || (size_t)n.left >= N || (size_t)n.right >= N) {
-            return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_bvh_refit_host: inner node %zu has children (%d, %d) outside (%zu, %zu)", i, n.left, n.right, i, N);
-        }
-    }
-    for (size_t i = 0; i < R; i++)
-        for (int k = 0; k < 3; k++)
-            if (tris[i].v[k] < 0 || (size_t)tris[i].v[k] >= V) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_bvh_refit_host: triangle record %zu references vertex %d of %zu", i, tris[i].v[k], V);
-    refit_host(nodes, N, tris, verts, (int)std::min(std::max(threads, 1u), 16u));
+    const std::string err = validate_tree("gmupt_bvh_refit_host", nodes, num_nodes, tris, num_tris, num_verts, 0);
+    if (!err.empty()) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+    refit_host(nodes, num_nodes, tris, verts, (int)std::min(std::max(threads, 1u), 16u));
     return GMUPT_OK;
 }
+
+struct gmupt_travtables { TravTables t; };
+
+extern "C" int gmupt_debug_travtables_build(const gmupt_bvh_node* nodes, uint32_t num_nodes, const gmupt_triangle* tris, uint32_t num_tris,
+                                            const float* verts, uint32_t num_verts, int want_wide, int top_order_bfs, int node_pairing, gmupt_travtables** out)
+{
+    if (!out || !nodes || num_nodes == 0 || (!tris && num_tris) || (!verts && num_verts)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_debug_travtables_build: null or empty array");
+    *out = nullptr;
+    TravOptions o;
+    o.wantWide = want_wide != 0; o.topOrderBfs = top_order_bfs != 0; o.nodePairing = node_pairing != 0;
+    o.topCapacity = traversal_top_capacity; o.wideTopCapacity = traversal_wide_top_capacity();
+    gmupt_travtables* h = new (std::nothrow) gmupt_travtables();
+    if (!h) return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_debug_travtables_build: out of host memory");
+    const std::string err = build_trav_tables(nodes, num_nodes, tris, num_tris, verts, num_verts, o, h->t);
+    if (!err.empty()) { delete h; return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s", err.c_str()); }
+    *out = h;
+    return GMUPT_OK;
+}
+
+extern "C" const void* gmupt_debug_travtables_data(const gmupt_travtables* h, int which, size_t* bytes)
+{
+    if (!h || !bytes) return nullptr;
+    const TravTables& t = h->t;
+    auto of = [&](const auto& v) -> const void* { *bytes = v.size() * sizeof(v[0]); return v.data(); };
+    switch (which) {
+    case GMUPT_TT_NODE64: return of(t.nodes); case GMUPT_TT_TRI48: return of(t.tris); case GMUPT_TT_TRIPAIR: return of(t.pairs);
+    case GMUPT_TT_PAIRREF: return of(t.pairRef); case GMUPT_TT_WNODE: return of(t.wide);
+#ifdef GMUPT_VARIANTS
+    case GMUPT_TT_REC64: return of(t.recs);
+#endif
+    case GMUPT_TT_SCALARS: *bytes = sizeof(TravScalars); return &t.s;
+    case GMUPT_TT_LEVEL_NODES: return of(t.levelNodes); case GMUPT_TT_LEVEL_OFF: return of(t.levelOff); case GMUPT_TT_NODE_MAP: return of(t.nodeMap);
+    case GMUPT_TT_WIDE_MAP: return of(t.wideMap); case GMUPT_TT_OPENED: return of(t.opened);
+    }
+    *bytes = 0;
+    return nullptr;
+}
+
+extern "C" void gmupt_debug_travtables_destroy(gmupt_travtables* h) { delete h; }
 
 extern "C" int gmupt_renderer_bind_scene(gmupt_renderer* r, const gmupt_buffer* nodes, const gmupt_buffer* triangles, const gmupt_buffer* vertices,
                                          const gmupt_buffer* lights, const gmupt_buffer* tri_props, const gmupt_buffer* materials)

@@ -46,7 +46,7 @@ GM_HD void rf_tri9(const gmupt_triangle& t, const float* verts, float* c)
 }
 
 // false when child box c is flat on an axis on which parent box p is not, in the plane of one of p's faces: such a parent must keep
-// its own slot in the 4-wide collapse (gmupt_capi.hip: build_traversal_copy, opens())
+// its own slot in the 4-wide collapse (pt_travtables.cpp: collapse, which calls this; k_rf_wide repeats it on the refitted boxes)
 GM_HD bool rf_child_ok(const float* pmn, const float* pmx, const float* cmn, const float* cmx)
 {
     for (int k = 0; k < 3; k++)
@@ -54,7 +54,7 @@ GM_HD bool rf_child_ok(const float* pmn, const float* pmx, const float* cmn, con
     return true;
 }
 
-// what a refit needs from bind besides the tables themselves (host vectors of build_traversal_copy, uploaded by the first refit)
+// what a refit needs from bind besides the tables themselves (the refit maps of pt_travtables.hpp, uploaded by the first refit)
 struct RfArgs {
     DNode* nodes; const gmupt_triangle* tris; const float* verts;
     uint32_t numNodes, numTris, numVerts;

@@ -563,6 +563,20 @@ int gmupt_debug_run_stage(gmupt_renderer* r, gmupt_stage stage);
 /* evaluates the device copy of the deterministic math (fn: 0 sin, 1 cos, 2 log2, 3 exp2, 4 pow(x,y), 5 frac, 6 rng probe) */
 int gmupt_debug_detmath(gmupt_device* dev, int fn, const float* x, const float* y, float* out, uint32_t n);
 
+/* The traversal tables a bind would build from these host arrays (csrc/pt_travtables.hpp), without a device: numbering switches as
+ * arguments instead of GMUPT_TOP_ORDER / GMUPT_NODE_PAIRING, LDS capacities of this build.  gmupt_debug_travtables_data returns the bytes
+ * of one table or map (owned by the handle; NULL and 0 bytes for an empty one or for GMUPT_TT_REC64 outside a -DGMUPT_VARIANTS build).
+ * GMUPT_TT_SCALARS: 15 words -- topCount, topCountDeep, maxDepth, rootDesc, rootMin[3], rootMax[3], triBase, wideTopCount,
+ * wideStackBound, numPairs, wideCount.  A malformed tree: the message of gmupt_renderer_bind_scene, GMUPT_ERR_INVALID_ARGUMENT. */
+typedef struct gmupt_travtables gmupt_travtables;
+typedef enum { GMUPT_TT_NODE64 = 0, GMUPT_TT_TRI48 = 1, GMUPT_TT_TRIPAIR = 2, GMUPT_TT_PAIRREF = 3, GMUPT_TT_WNODE = 4, GMUPT_TT_REC64 = 5,
+               GMUPT_TT_SCALARS = 6, GMUPT_TT_LEVEL_NODES = 7, GMUPT_TT_LEVEL_OFF = 8, GMUPT_TT_NODE_MAP = 9, GMUPT_TT_WIDE_MAP = 10,
+               GMUPT_TT_OPENED = 11 } gmupt_travtable_kind;
+int gmupt_debug_travtables_build(const gmupt_bvh_node* nodes, uint32_t num_nodes, const gmupt_triangle* tris, uint32_t num_tris,
+                                 const float* verts, uint32_t num_verts, int want_wide, int top_order_bfs, int node_pairing, gmupt_travtables** out);
+const void* gmupt_debug_travtables_data(const gmupt_travtables* h, int which /* gmupt_travtable_kind */, size_t* bytes);
+void gmupt_debug_travtables_destroy(gmupt_travtables* h);
+
 /* ---- host side: SBVH build + flatten (replaces BVHWrapper::buildSBVH, Source/BVHWrapper.cpp:13-96, and the vendored Nvidia-SBVH builder) ---- */
 typedef struct {
     float split_alpha;       /* BVH::BuildParams::splitAlpha = 1e-5 (Include/Nvidia-SBVH/BVH.h:77) */
