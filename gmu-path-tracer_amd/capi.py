@@ -221,6 +221,7 @@ SYMBOLS = {
     "gmupt_debug_travtables_build": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "gmupt_debug_travtables_data": (_P, [_P, C.c_int, C.POINTER(C.c_size_t)]),
     "gmupt_debug_travtables_destroy": (None, [_P]),
+    "gmupt_debug_wide_tables_addressable": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "gmupt_sbvh_default_params": (None, [C.POINTER(SbvhParams)]),
     "gmupt_sbvh_build": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(SbvhParams), C.POINTER(_P)]),
     "gmupt_sbvh_num_nodes": (C.c_uint32, [_P]),
@@ -997,6 +998,11 @@ def travtables(nodes, tris, verts, want_wide=True, top_order_bfs=False, node_pai
         return out
     finally:
         lib().gmupt_debug_travtables_destroy(h)
+
+
+def wide_tables_addressable(wide_nodes, num_tris, num_pairs):
+    """gmupt_debug_wide_tables_addressable: do tables of these sizes stay within the wide ray cast's 32-bit byte offsets?  No device involved."""
+    return bool(lib().gmupt_debug_wide_tables_addressable(int(wide_nodes), int(num_tris), int(num_pairs)))
 
 
 def sbvh_build(verts, indices, vertex_material=None, params=None):

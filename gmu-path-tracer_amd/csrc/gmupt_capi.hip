@@ -589,6 +589,11 @@ extern "C" const void* gmupt_debug_travtables_data(const gmupt_travtables* h, in
 
 extern "C" void gmupt_debug_travtables_destroy(gmupt_travtables* h) { delete h; }
 
+extern "C" int gmupt_debug_wide_tables_addressable(uint32_t wide_nodes, uint32_t num_tris, uint32_t num_pairs)
+{
+    return wide_tables_addressable(wide_nodes, num_tris, num_pairs) ? 1 : 0;
+}
+
 extern "C" int gmupt_renderer_bind_scene(gmupt_renderer* r, const gmupt_buffer* nodes, const gmupt_buffer* triangles, const gmupt_buffer* vertices,
                                          const gmupt_buffer* lights, const gmupt_buffer* tri_props, const gmupt_buffer* materials)
 {
@@ -845,14 +850,14 @@ static_assert(sizeof(gmupt_ray) == 32 && offsetof(gmupt_ray, tmax) == 12 && offs
 static_assert(sizeof(gmupt_hit) == 32 && offsetof(gmupt_hit, triangle) == 12 && offsetof(gmupt_hit, light) == 16 && offsetof(gmupt_hit, material) == 20, "gmupt_hit layout");
 static_assert(sizeof(gmupt_trace_info) == 24 && offsetof(gmupt_trace_info, redo_rays) == 8 && offsetof(gmupt_trace_info, ms) == 16, "gmupt_trace_info layout");
 
-// the wide collapse and the limits of launch_cast_wide's 32-bit buffer offsets, here including the TriPair table (gmupt_trace_rays, gmupt_render_aovs)
+// the wide collapse and the limits of k_cast_w's 32-bit buffer offsets, the rule launch_cast_wide applies (gmupt_trace_rays, gmupt_render_aovs)
 static int query_supported(gmupt_renderer* r, const char* fn)
 {
     const RenderParams& p = r->p;
     if (!p.trav.wnodes || p.extendPrune || p.shadowPrune)
         return fail(GMUPT_ERR_UNSUPPORTED, "%s: the bound scene has no wide collapse (it needs GMUPT_TRAVERSAL=wide, no GMUPT_EXTEND_PRUNE / GMUPT_SHADOW_PRUNE, "
                     "and child boxes inside their parents)", fn);
-    if ((uint64_t)p.trav.wideCount * 128ull >= (1ull << 31) || ((uint64_t)p.scene.numTris + 1ull) * 48ull >= (1ull << 31) || (uint64_t)p.trav.numPairs * 80ull >= (1ull << 31))
+    if (!wide_tables_addressable(p.trav.wideCount, p.scene.numTris, p.trav.numPairs))
         return fail(GMUPT_ERR_UNSUPPORTED, "%s: the wide tables of the bound scene exceed 2 GiB (%u nodes, %u references, %u pairs)", fn, p.trav.wideCount, p.scene.numTris, p.trav.numPairs);
     return GMUPT_OK;
 }

@@ -29,6 +29,7 @@
 // walk has a bounds-checked global overflow).  Drain: finished lanes take the BOTTOM inner entry of busy lanes (the largest subtree
 // left) and report their best hit back; results merge by "smaller t wins, equal t is a tie".
 #include "pt_traverse_deferred.hpp"
+#include "pt_travtables.hpp"
 
 namespace gmupt {
 
@@ -773,7 +774,7 @@ uint32_t traversal_wide_overflow_entries() { return (uint32_t)kWideOvf; }
 uint32_t launch_cast_wide(const RenderParams& p, bool stats, hipStream_t s)
 {
     if (!p.trav.wnodes || p.extendPrune || p.shadowPrune) return 0u;
-    if ((uint64_t)p.trav.wideCount * 128ull >= (1ull << 31) || ((uint64_t)p.scene.numTris + 1ull) * 48ull >= (1ull << 31)) return 0u;
+    if (!wide_tables_addressable(p.trav.wideCount, p.scene.numTris, p.trav.numPairs)) return 0u;
     const uint32_t pb = p.travGridBlocks;
     // steps per iteration of a wave (between two looks at the queues): six while the records fit the 256 MB Infinity Cache, eight beyond
     // (measured: config 3 0.923 / 0.930 ms with six / eight, config 5 5.12 / 5.00 ms); GMUPT_WIDE_STEPS overrides

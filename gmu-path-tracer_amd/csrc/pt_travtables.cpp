@@ -397,4 +397,10 @@ std::string build_trav_tables(const gmupt_bvh_node* nodes, size_t N, const gmupt
     return std::string();
 }
 
+bool wide_tables_addressable(uint32_t wideCount, uint32_t numTris, uint32_t numPairs)
+{
+    constexpr uint64_t kLimit = 1ull << 31;
+    return (uint64_t)wideCount * sizeof(WNode) < kLimit && ((uint64_t)numTris + 1ull) * sizeof(Tri48) < kLimit && (uint64_t)numPairs * sizeof(TriPair) < kLimit;
+}
+
 } // namespace gmupt

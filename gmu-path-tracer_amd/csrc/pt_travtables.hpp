@@ -46,4 +46,9 @@ std::string validate_tree(const char* prefix, const gmupt_bvh_node* nodes, size_
 std::string build_trav_tables(const gmupt_bvh_node* nodes, size_t N, const gmupt_triangle* tris, size_t R, const float* verts, size_t V,
                               const TravOptions& opt, TravTables& out);
 
+// The wide ray cast (k_cast_w) addresses its three tables with signed 32-bit byte offsets: WNode records (128 bytes), Tri48 records and
+// their sentinel (48 bytes), TriPair records (80 bytes).  True when every table stays below 2 GiB; otherwise the renderer's own cast falls
+// back to the binary-tree kernels and the ray queries return GMUPT_ERR_UNSUPPORTED.
+bool wide_tables_addressable(uint32_t wideCount, uint32_t numTris, uint32_t numPairs);
+
 } // namespace gmupt

@@ -226,6 +226,18 @@ int gmupt_render_budget(gmupt_renderer* r, gmupt_camera* camera, uint32_t max_it
  *   light = material = 0.  With tmax = FLT_MAX the record is the reference's (hitDistance, baryCoord.yz, triangle, isEmitter).
  * Any hit (shadowRayCast.hlsl:41-45,89): occluded = 1 if some triangle has 1e-8 < t < 1e8 (EPSILON = 1e-8, structs.h:10) and
  *   |direction * t| < tmax -- tmax plays the reference's lightDistance; the light spheres are not tested.
+ * Degenerate rays (tests/test_degenerate_rays_gpu.py asserts each sentence): rays are NOT validated.  Every bit pattern of origin, direction
+ *   and tmax -- NaN, infinities, signed zeros, denormals (kept, never flushed), huge magnitudes -- gets the record the rules above give in
+ *   binary32, comparisons with a NaN being false; it never faults, and it does not change the record of any other ray of the batch.
+ *   A NaN or an infinity in one component of the origin or of the direction, a direction of all zeros (either sign), a direction scaled
+ *   by 1e-30 (every determinant falls below EPSILON) or an origin 1e20 away is a miss of every triangle: the miss record / occluded = 0.
+ *   A zero (either sign) or denormal direction component alone is an ordinary ray.
+ *   tmax of a closest-hit ray, from `t >= 0 && t < distance` with distance starting at tmax:
+ *     tmax <= 0 (-0.0 included) or NaN: no t passes, neither a triangle's nor a light sphere's: the miss record, with t = the bits of tmax;
+ *     tmax = +inf: every hit that tmax = FLT_MAX accepts, with the same t, u, v, triangle, light and material; a miss has t = +inf.
+ *   tmax of an any-hit ray, from `|direction * t| < tmax`:
+ *     tmax <= 0 or NaN: occluded = 0 (a length is never below it);
+ *     tmax = +inf: no distance limit -- any triangle with 1e-8 < t < 1e8 and a finite |direction * t| occludes.
  * Calling: rays and outputs are caller-owned DEVICE memory (hipMalloc, torch tensors), 16-byte aligned (occluded: 4); at most 2^26 rays per
  *   batch.  The call is enqueued on the renderer's stream behind any pending gmupt_iterate work, then synchronises and reads back its own
  *   fault flags: GMUPT_ERR_CAST_FAULT on a traversal stack overflow or an aborted wave (the outputs are then invalid).  The renderer's path
@@ -576,6 +588,10 @@ int gmupt_debug_travtables_build(const gmupt_bvh_node* nodes, uint32_t num_nodes
                                  const float* verts, uint32_t num_verts, int want_wide, int top_order_bfs, int node_pairing, gmupt_travtables** out);
 const void* gmupt_debug_travtables_data(const gmupt_travtables* h, int which /* gmupt_travtable_kind */, size_t* bytes);
 void gmupt_debug_travtables_destroy(gmupt_travtables* h);
+/* 1 when tables of these sizes are within the wide ray cast's signed 32-bit byte offsets -- wide_nodes * 128, (num_tris + 1) * 48 (the
+ * references and their sentinel record) and num_pairs * 80 all below 2^31 -- else 0.  The one rule behind the renderer's choice of the wide
+ * kernel and behind GMUPT_ERR_UNSUPPORTED of the ray queries; no device involved. */
+int gmupt_debug_wide_tables_addressable(uint32_t wide_nodes, uint32_t num_tris, uint32_t num_pairs);
 
 /* ---- host side: SBVH build + flatten (replaces BVHWrapper::buildSBVH, Source/BVHWrapper.cpp:13-96, and the vendored Nvidia-SBVH builder) ---- */
 typedef struct {

@@ -1,9 +1,7 @@
 """GPU tests of the ray-query API (gmupt_trace_rays / gmupt_pick): k_cast_w with the QueryIO policy on caller rays.
 
-Truth is the CPU oracle's own extension / shadow stages on a frozen state: the query's rays are written into rayOrigin / rayDirection /
-shadowrayOrigin / shadowrayDirection / lightDistance with identity queues, orc.stage("extension") and orc.stage("shadow") run, and the
-answers are compared bit for bit (t <-> hitDistance, u, v <-> baryCoord[1:], tris[triangle] <-> triangle, light <-> isEmitter,
-occluded <-> inShadow).
+Truth is the CPU oracle's own extension / shadow stages on a frozen state (trace_util.oracle_truth), compared bit for bit
+(trace_util.assert_matches_oracle).
 """
 import ctypes as C
 
@@ -12,79 +10,14 @@ import pytest
 import torch   # first: torch's HIP runtime is the one libgmupt binds to (the query's rays and outputs are torch tensors)
 
 import oracle_lib as O
+from trace_util import FLT_MAX, NO_TRI, assert_matches_oracle, make_rays, oracle_truth, random_rays
 
 pytestmark = pytest.mark.gpu
-
-FLT_MAX = np.finfo(np.float32).max
-NO_TRI = 0xFFFFFFFF
 
 
 @pytest.fixture()
 def wide(monkeypatch):
     monkeypatch.setenv("GMUPT_TRAVERSAL", "wide")
-
-
-def make_rays(origins, dirs, tmax):
-    r = np.zeros((len(origins), 8), np.float32)
-    r[:, 0:3] = origins; r[:, 3] = tmax; r[:, 4:7] = dirs
-    return r
-
-
-def oracle_truth(scene, closest, any_rays, light_count):
-    """The oracle's extension / shadow stages on the query's rays: dict of per-ray fields (uint32 bit patterns)."""
-    nC, nA = len(closest), len(any_rays)
-    P = max(nC, nA, 64)
-    orc = O.Renderer(scene, 32, 18, P)
-    st = orc.path_state()
-    O.state_field(st, P, "triangle")[:] = NO_TRI
-    O.state_field(st, P, "baryCoord")[:] = NO_TRI
-    if nC:
-        O.state_field(st, P, "rayOrigin").view(np.float32)[:nC] = closest[:, 0:3]
-        O.state_field(st, P, "rayDirection").view(np.float32)[:nC] = closest[:, 4:7]
-    if nA:
-        O.state_field(st, P, "shadowrayOrigin").view(np.float32)[:nA] = any_rays[:, 0:3]
-        O.state_field(st, P, "shadowrayDirection").view(np.float32)[:nA] = any_rays[:, 4:7]
-        O.state_field(st, P, "lightDistance").view(np.float32)[:nA, 0] = any_rays[:, 3]
-    q = orc.queues(); q[3][:] = np.arange(P, dtype=np.uint32); q[4][:] = np.arange(P, dtype=np.uint32)
-    qc = orc.counters(); qc[:] = 0; qc[7] = nC; qc[6] = nA
-    cam = O.Camera(32, 18); cam.set_pose(*scene["camera"]); cam.update(); cam.buffer.lightCount = light_count
-    orc.set_camera(cam.buffer)
-    orc.stage("extension"); orc.stage("shadow")
-    st = orc.path_state()
-    out = {k: O.state_field(st, P, k).copy() for k in ("hitDistance", "baryCoord", "triangle", "isEmitter", "inShadow")}
-    orc.close()
-    return out
-
-
-def assert_matches_oracle(scene, closest, any_rays, hits, occ, light_count, truth=None):
-    t = truth or oracle_truth(scene, closest, any_rays, light_count)
-    nC, nA = len(closest), len(any_rays)
-    h = hits.view(np.uint32).reshape(-1, 8)
-    hf = hits.view(np.float32).reshape(-1, 8)
-    assert np.array_equal(h[:, 0], t["hitDistance"][:nC, 0]), "t"
-    assert np.array_equal(h[:, 4], t["isEmitter"][:nC, 0]), "light"
-    tri = h[:, 3].view(np.int32)
-    hit = tri >= 0
-    assert np.array_equal(hit, t["triangle"][:nC, 0] != NO_TRI), "which rays hit a triangle"
-    recs = scene["tris"].view(np.uint32).reshape(-1, 4)
-    assert np.array_equal(recs[tri[hit]], t["triangle"][:nC][hit]), "triangle record"
-    assert np.array_equal(h[hit, 5], recs[tri[hit], 3]), "material"
-    assert np.array_equal(h[hit, 1:3], t["baryCoord"][:nC][hit, 1:3]), "u, v"
-    assert not hf[~hit, 1:3].any() and (tri[~hit] == -1).all()
-    assert np.array_equal(occ.astype(np.uint32), t["inShadow"][:nA, 0]), "occluded"
-
-
-def random_rays(scene, n, rng, tmax_any=None):
-    v = scene["verts"].reshape(-1, 3)
-    lo, hi = v.min(axis=0), v.max(axis=0)
-    ext = hi - lo
-    o = (lo + rng.uniform(-0.1, 1.1, (n, 3)) * ext).astype(np.float32)
-    d = rng.normal(size=(n, 3)).astype(np.float32)
-    d[: n // 2] /= np.linalg.norm(d[: n // 2], axis=1, keepdims=True)
-    d = d.astype(np.float32)
-    closest = make_rays(o, d, FLT_MAX)
-    any_rays = make_rays(o, d, rng.uniform(0.05, 1.5, n).astype(np.float32) * np.float32(np.linalg.norm(ext)))
-    return closest, any_rays
 
 
 def renderer(pkg, device, scene, pool=4096, **kw):
