@@ -145,6 +145,24 @@ REFIT_FLAT_CHILD, REFIT_VARIANTS_BUILD = 1, 2
 assert C.sizeof(RefitInfo) == 24
 
 
+class LbvhParams(C.Structure):
+    """gmupt_lbvh_params."""
+    _fields_ = [("max_leaf_size", C.c_uint32)]
+
+
+class LbvhInfo(C.Structure):
+    """gmupt_lbvh_info: 48 bytes."""
+    _fields_ = [("num_nodes", C.c_uint32), ("num_leaves", C.c_uint32), ("depth", C.c_uint32), ("num_tris", C.c_uint32),
+                ("root_min", C.c_float * 3), ("root_max", C.c_float * 3), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {"num_nodes": int(self.num_nodes), "num_leaves": int(self.num_leaves), "depth": int(self.depth), "num_tris": int(self.num_tris),
+                "root_min": np.array(self.root_min[:], np.float32), "root_max": np.array(self.root_max[:], np.float32), "ms": float(self.ms)}
+
+
+assert C.sizeof(LbvhInfo) == 48
+
+
 class GmuptError(RuntimeError):
     def __init__(self, msg, code=0):
         super().__init__(msg)
@@ -210,6 +228,11 @@ SYMBOLS = {
     "gmupt_temporal_denoise_image_motion": (C.c_int, [_P, _P, _P, _P, C.POINTER(CameraBuffer), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                                       C.POINTER(TemporalParams), _P, C.c_size_t, C.POINTER(C.c_float)]),
     "gmupt_render_denoised_temporal_motion": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(TemporalParams), _P, C.c_size_t, C.POINTER(TraceInfo)]),
+    "gmupt_lbvh_default_params": (None, [C.POINTER(LbvhParams)]),
+    "gmupt_lbvh_build_host": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.POINTER(LbvhParams), _P, _P, _P, C.POINTER(LbvhInfo)]),
+    "gmupt_lbvh_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "gmupt_lbvh_destroy": (None, [_P]),
+    "gmupt_lbvh_build": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.POINTER(LbvhParams), C.POINTER(_P), C.POINTER(_P), _P, C.POINTER(LbvhInfo)]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -330,6 +353,13 @@ class Buffer:
         self.h = _P()
         self.dev = dev
         _check(lib().gmupt_buffer_create(dev.h, kind, _ptr(array), array.nbytes, C.byref(self.h)))
+
+    @classmethod
+    def wrap(cls, dev, handle):
+        """A Buffer around a gmupt_buffer the library created (gmupt_lbvh_build); close() destroys it like any other."""
+        self = cls.__new__(cls)
+        self.h, self.dev = handle, dev
+        return self
 
     def update(self, array):
         array = np.ascontiguousarray(array)
@@ -1034,3 +1064,83 @@ def sbvh_build(verts, indices, vertex_material=None, params=None):
         return {"nodes": nodes, "tris": tris, "ref_triangle": ref, "sah": float(lib().gmupt_sbvh_sah(h)), "depth": int(lib().gmupt_sbvh_depth(h))}
     finally:
         lib().gmupt_sbvh_destroy(h)
+
+
+def lbvh_build_host(verts, indices, vertex_material=None, max_leaf_size=4):
+    """gmupt_lbvh_build_host: the LBVH rule of include/gmupt.h on host arrays, the reference of Lbvh.build.  Returns the dict of sbvh_build
+    (nodes, tris, ref_triangle, sah, depth) plus info (LbvhInfo.as_dict()); sah is the surface-area cost of the tree with the SBVH builder's
+    default node / triangle costs of 1 (tree_sah)."""
+    verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
+    n = indices.shape[0]
+    vm = np.ascontiguousarray(vertex_material, dtype=np.uint32) if vertex_material is not None else None
+    if vm is not None and vm.shape[0] < verts.shape[0]:
+        raise GmuptError("lbvh_build_host: %d vertex materials for %d vertices" % (vm.shape[0], verts.shape[0]), -1)
+    nodes = np.zeros(max(2 * n - 1, 1), dtype=bvh_node_dtype)
+    tris = np.zeros(max(n, 1), dtype=triangle_dtype)
+    ref = np.zeros(max(n, 1), dtype=np.int32)
+    pp, info = LbvhParams(int(max_leaf_size)), LbvhInfo()
+    _check(lib().gmupt_lbvh_build_host(_ptr(verts), verts.shape[0], _ptr(indices), n, _ptr(vm) if vm is not None else None, C.byref(pp),
+                                       _ptr(nodes), _ptr(tris), _ptr(ref), C.byref(info)))
+    nodes = nodes[:info.num_nodes].copy()
+    return {"nodes": nodes, "tris": tris[:n], "ref_triangle": ref[:n], "sah": tree_sah(nodes), "depth": int(info.depth), "info": info.as_dict()}
+
+
+def tree_sah(nodes):
+    """Surface-area cost of a reference-layout tree: A(node) / A(root) times 2 for an inner node (two box tests) and times the number of
+    references for a leaf -- the measure gmupt_sbvh_sah reports at its default costs of 1, from the flattened boxes in float64 instead of
+    the builder's running float products.  0 for a root without area."""
+    nodes = np.asarray(nodes)
+    e = np.maximum(nodes["max"].astype(np.float64) - nodes["min"].astype(np.float64), 0.0)
+    area = 2.0 * (e[:, 0] * e[:, 1] + e[:, 1] * e[:, 2] + e[:, 2] * e[:, 0])
+    if not area[0] > 0:
+        return 0.0
+    leaf = nodes["isLeaf"] != 0
+    count = np.where(leaf, nodes["right"] - nodes["left"], 2)
+    return float((area * count).sum() / area[0])
+
+
+class Lbvh:
+    """gmupt_lbvh: the GPU LBVH builder of one device -- a stream and the scratch of the largest mesh built so far, kept between builds."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.h = _P()
+        _check(lib().gmupt_lbvh_create(dev.h, C.byref(self.h)))
+
+    def build(self, vertex_buffer, indices, vertex_material=None, max_leaf_size=4, ref_triangle=False):
+        """gmupt_lbvh_build on the device-resident vertices of `vertex_buffer` (a Buffer of kind BUFFER_VERTICES).  indices / vertex_material:
+        torch device tensors (int32 / a 4-byte integer type, used in place) or numpy arrays (uploaded).  Returns (nodes Buffer, tris Buffer,
+        info dict); the caller closes the buffers.  ref_triangle=True adds info["ref_triangle"], the source triangle of every record."""
+        import torch
+        device = torch.device("cuda", self.dev.index)
+
+        def on_device(x, dtype):
+            if isinstance(x, torch.Tensor):
+                if x.device != device or x.element_size() != 4 or x.is_floating_point():
+                    raise GmuptError("Lbvh.build: a tensor must hold 4-byte integers on %s" % device, -1)
+                return x.contiguous()
+            arr = np.ascontiguousarray(x, dtype=dtype)
+            return torch.from_numpy(arr.view(np.int32)).to(device)      # (the bits; torch has no arithmetic on uint32 and needs none here)
+
+        idx = on_device(indices, np.int32).reshape(-1)
+        n = idx.numel() // 3
+        vm = on_device(vertex_material, np.uint32).reshape(-1) if vertex_material is not None else None
+        nverts = int(lib().gmupt_buffer_size(vertex_buffer.h)) // 12
+        if vm is not None and vm.numel() < nverts:
+            raise GmuptError("Lbvh.build: %d vertex materials for %d vertices" % (vm.numel(), nverts), -1)
+        ref = torch.empty(max(n, 1), dtype=torch.int32, device=device) if ref_triangle else None
+        torch.cuda.synchronize(device)    # the builder has its own stream: uploads and the caller's writes are done before it starts
+        nodes, tris, info = _P(), _P(), LbvhInfo()
+        pp = LbvhParams(int(max_leaf_size))
+        _check(lib().gmupt_lbvh_build(self.h, vertex_buffer.h, idx.data_ptr(), n, vm.data_ptr() if vm is not None else None, C.byref(pp),
+                                      C.byref(nodes), C.byref(tris), ref.data_ptr() if ref is not None else None, C.byref(info)))
+        out = info.as_dict()
+        if ref is not None:
+            out["ref_triangle"] = ref[:n].cpu().numpy()
+        return Buffer.wrap(self.dev, nodes), Buffer.wrap(self.dev, tris), out
+
+    def close(self):
+        if self.h:
+            lib().gmupt_lbvh_destroy(self.h)
+            self.h = _P()

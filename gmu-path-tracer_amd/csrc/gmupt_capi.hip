@@ -8,6 +8,7 @@
 #include "pt_refit.hpp"
 #include "pt_motion.hpp"
 #include "pt_travtables.hpp"
+#include "pt_lbvh.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
 #include "../host/TextureLoader.hpp"
@@ -77,6 +78,10 @@ void launch_refit_check(const RfArgs& a, hipStream_t s);
 uint32_t launch_refit_boxes(const RfArgs& a, const std::vector<uint32_t>& levelOff, hipStream_t s);
 void launch_refit_tables(const RfArgs& a, hipStream_t s);
 void refit_host(gmupt_bvh_node* nodes, size_t N, const gmupt_triangle* tris, const float* verts, int threads);
+hipError_t lbvh_sort_temp_bytes(uint32_t n, size_t* bytes);
+LbScratch lbvh_scratch_layout(uint32_t n, size_t sortTemp);
+hipError_t launch_lbvh(void* scratch, const LbScratch& off, size_t sortTemp, const float* verts, uint32_t numVerts, const int32_t* indices, uint32_t n,
+                       const uint32_t* vertexMaterial, uint32_t maxLeaf, hipStream_t s, LbStaging& st);
 }
 using namespace gmupt;
 
@@ -1617,6 +1622,142 @@ extern "C" int gmupt_debug_detmath(gmupt_device* dev, int fn, const float* x, co
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
     (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
+    return GMUPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ LBVH: the GPU builder (pt_lbvh.hip) and its host reference (pt_lbvh.cpp)
+static_assert(sizeof(gmupt_lbvh_info) == 48 && offsetof(gmupt_lbvh_info, ms) == 40, "gmupt_lbvh_info layout");
+
+extern "C" void gmupt_lbvh_default_params(gmupt_lbvh_params* p) { if (p) p->max_leaf_size = 4; }
+
+static void lbvh_fill_info(gmupt_lbvh_info* info, const LbResult& res, uint32_t numTris, double ms)
+{
+    if (!info) return;
+    info->num_nodes = res.numNodes; info->num_leaves = res.numLeaves; info->depth = res.depth; info->num_tris = numTris;
+    for (int k = 0; k < 3; k++) { info->root_min[k] = res.rootMin[k]; info->root_max[k] = res.rootMax[k]; }
+    info->ms = ms;
+}
+
+static int lbvh_leaf_size(const char* fn, const gmupt_lbvh_params* params, uint32_t* L)
+{
+    *L = params ? params->max_leaf_size : 4u;
+    if (*L < 1 || *L > kLbMaxLeaf) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: max_leaf_size %u outside 1..%u", fn, *L, kLbMaxLeaf);
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_lbvh_build_host(const float* verts, uint32_t num_verts, const int32_t* indices, uint32_t num_tris, const uint32_t* vertex_material,
+                                     const gmupt_lbvh_params* params, gmupt_bvh_node* nodes_out, gmupt_triangle* tris_out, int32_t* ref_triangle_out,
+                                     gmupt_lbvh_info* info)
+{
+    if (!verts || !indices || !nodes_out || !tris_out || num_verts == 0 || num_tris == 0) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build_host: null or empty array");
+    if (num_tris > kLbMaxTris) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build_host: more than 2^30 triangles");
+    uint32_t L;
+    int rc = lbvh_leaf_size("gmupt_lbvh_build_host", params, &L);
+    if (rc != GMUPT_OK) return rc;
+    LbResult res{};
+    int status = GMUPT_OK;
+    const std::string err = lbvh_build_host(verts, num_verts, indices, num_tris, vertex_material, L, nodes_out, tris_out, ref_triangle_out, res, &status);
+    if (status != GMUPT_OK) return fail(status, "gmupt_lbvh_build_host: %s", err.c_str());
+    lbvh_fill_info(info, res, num_tris, 0.0);
+    return GMUPT_OK;
+}
+
+// the builder handle: a stream, two events and the scratch of the largest mesh built so far
+struct gmupt_lbvh { gmupt_device* dev; hipStream_t stream = nullptr; hipEvent_t ev[2] = { nullptr, nullptr }; void* scratch = nullptr; uint32_t capTris = 0; size_t sortTemp = 0; };
+
+extern "C" int gmupt_lbvh_create(gmupt_device* dev, gmupt_lbvh** out)
+{
+    if (!dev || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_create: null argument");
+    *out = nullptr;
+    gmupt_lbvh* h = new (std::nothrow) gmupt_lbvh();
+    if (!h) return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_lbvh_create: out of host memory");
+    h->dev = dev;
+    hipError_t e = hipSetDevice(dev->id);
+    if (e == hipSuccess) e = hipStreamCreate(&h->stream);
+    for (hipEvent_t& ev : h->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e != hipSuccess) { gmupt_lbvh_destroy(h); return fail(GMUPT_ERR_HIP, "gmupt_lbvh_create: %s", hipGetErrorString(e)); }
+    *out = h;
+    return GMUPT_OK;
+}
+
+extern "C" void gmupt_lbvh_destroy(gmupt_lbvh* h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->dev->id);
+    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
+    for (hipEvent_t ev : h->ev) if (ev) (void)hipEventDestroy(ev);
+    if (h->scratch) (void)hipFree(h->scratch);
+    delete h;
+}
+
+// a gmupt_buffer of `elems` elements filled from device memory on stream s (the caller synchronises)
+static int lbvh_output_buffer(gmupt_device* dev, gmupt_buffer_kind kind, size_t elems, const void* src, hipStream_t s, gmupt_buffer** out)
+{
+    gmupt_buffer* b = new (std::nothrow) gmupt_buffer();
+    if (!b) return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_lbvh_build: out of host memory");
+    b->dev = dev; b->kind = kind; b->elems = elems; b->bytes = elems * kind_stride(kind); b->dptr = nullptr;
+    hipError_t e = hipMalloc(&b->dptr, b->bytes + 16);       // the slack of gmupt_buffer_create
+    if (e == hipSuccess) e = hipMemsetAsync((char*)b->dptr + b->bytes, 0, 16, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(b->dptr, src, b->bytes, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) { if (b->dptr) (void)hipFree(b->dptr); delete b; return fail(GMUPT_ERR_HIP, "gmupt_lbvh_build(%zu bytes): %s", elems * kind_stride(kind), hipGetErrorString(e)); }
+    *out = b;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_lbvh_build(gmupt_lbvh* h, const gmupt_buffer* vertices, const int32_t* device_indices, uint32_t num_tris, const uint32_t* device_vertex_material,
+                                const gmupt_lbvh_params* params, gmupt_buffer** nodes_out, gmupt_buffer** triangles_out, int32_t* device_ref_triangle,
+                                gmupt_lbvh_info* info)
+{
+    if (nodes_out) *nodes_out = nullptr;
+    if (triangles_out) *triangles_out = nullptr;
+    if (!h || !vertices || !device_indices || !nodes_out || !triangles_out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build: null argument");
+    if (vertices->kind != GMUPT_BUFFER_VERTICES || vertices->dev != h->dev) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build: not a vertex buffer of the builder's device");
+    if (vertices->elems == 0 || num_tris == 0) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build: empty mesh");
+    if (num_tris > kLbMaxTris || vertices->elems > 0x7FFFFFFFu) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build: more than 2^30 triangles or 2^31 - 1 vertices");
+    if (((uintptr_t)device_indices | (uintptr_t)device_vertex_material | (uintptr_t)device_ref_triangle) & 3) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build: misaligned pointer");
+    uint32_t L;
+    int rc = lbvh_leaf_size("gmupt_lbvh_build", params, &L);
+    if (rc != GMUPT_OK) return rc;
+    HIP_TRY(hipSetDevice(h->dev->id));
+    // the sort's temporary storage is asked for per build (a host-only call): a smaller mesh is not assumed to need less than the capacity did.
+    // (capTris, sortTemp) is "large enough for every build so far", not "what the capacity needs": a later build may grow either once more
+    size_t sortTemp = 0;
+    HIP_TRY(lbvh_sort_temp_bytes(num_tris, &sortTemp));
+    if (num_tris > h->capTris || sortTemp > h->sortTemp) {
+        if (h->scratch) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipFree(h->scratch)); h->scratch = nullptr; h->capTris = 0; h->sortTemp = 0; }
+        const uint32_t cap = std::max(num_tris, h->capTris);
+        HIP_TRY(hipMalloc(&h->scratch, lbvh_scratch_layout(cap, sortTemp).total));
+        h->capTris = cap; h->sortTemp = sortTemp;
+    }
+    const LbScratch off = lbvh_scratch_layout(h->capTris, h->sortTemp);     // the parts are placed for the capacity: a smaller mesh uses the front of each
+
+    LbStaging st{};
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    HIP_TRY(launch_lbvh(h->scratch, off, h->sortTemp, (const float*)vertices->dptr, (uint32_t)vertices->elems, device_indices, num_tris, device_vertex_material, L, h->stream, st));
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    uint32_t back[16] = { 0 };
+    HIP_TRY(hipMemcpyAsync(back, st.words, sizeof(back), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (back[0] & kLbFlagBadIndex) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build: a triangle references a vertex outside the vertex buffer (%zu vertices)", vertices->elems);
+    if (back[0] & kLbFlagNonFinite) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build: a vertex used by a triangle is not finite");
+    LbResult res{};
+    res.numNodes = back[1]; res.numLeaves = (back[1] + 1) / 2; res.depth = back[2];
+    for (int k = 0; k < 3; k++) { std::memcpy(&res.rootMin[k], &back[4 + k], 4); std::memcpy(&res.rootMax[k], &back[8 + k], 4); }
+    if (res.depth > kLbMaxDepth) return fail(GMUPT_ERR_UNSUPPORTED, "gmupt_lbvh_build: the tree is %u levels deep, the traversal stacks hold %u", res.depth, kLbMaxDepth);
+    if (res.numNodes == 0 || res.numNodes > 2 * (size_t)num_tris - 1) return fail(GMUPT_ERR_HIP, "gmupt_lbvh_build: the device reported %u nodes for %u triangles", res.numNodes, num_tris);
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+
+    gmupt_buffer* nb = nullptr; gmupt_buffer* tb = nullptr;
+    rc = lbvh_output_buffer(h->dev, GMUPT_BUFFER_BVH_NODES, res.numNodes, st.nodes, h->stream, &nb);
+    if (rc == GMUPT_OK) rc = lbvh_output_buffer(h->dev, GMUPT_BUFFER_TRIANGLES, num_tris, st.tris, h->stream, &tb);
+    hipError_t e = hipSuccess;
+    if (rc == GMUPT_OK && device_ref_triangle) e = hipMemcpyAsync(device_ref_triangle, st.ref, (size_t)num_tris * 4, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (rc == GMUPT_OK && e != hipSuccess) rc = fail(GMUPT_ERR_HIP, "gmupt_lbvh_build: %s", hipGetErrorString(e));
+    if (rc != GMUPT_OK) { gmupt_buffer_destroy(nb); gmupt_buffer_destroy(tb); return rc; }
+    *nodes_out = nb; *triangles_out = tb;
+    lbvh_fill_info(info, res, num_tris, (double)ms);
     return GMUPT_OK;
 }
 

@@ -1,13 +1,14 @@
 #include "BVHWrapper.hpp"
 #include "sbvh_builder.hpp"
 #include <cstring>
+#include <stdexcept>
 
-BVHWrapper::BVHWrapper(const MeshData& scene)
+BVHWrapper::BVHWrapper(const MeshData& scene, Builder builder, unsigned maxLeafSize)
 {
-	buildSBVH(scene);
+	if (builder == Builder::LBVH) buildLBVH(scene, maxLeafSize); else buildSBVH(scene);
 }
 
-void BVHWrapper::buildSBVH(const MeshData& scene)
+void BVHWrapper::fillProperties(const MeshData& scene)
 {
 	mVertices = scene.vertices;
 
@@ -21,6 +22,11 @@ void BVHWrapper::buildSBVH(const MeshData& scene)
 		if (!scene.texCoords.empty()) { p.uv[0] = scene.texCoords[2 * n]; p.uv[1] = scene.texCoords[2 * n + 1]; }
 		p.materialID = scene.vertexMaterial[n];
 	}
+}
+
+void BVHWrapper::buildSBVH(const MeshData& scene)
+{
+	fillProperties(scene);
 
 	gmupt_sbvh_params params;
 	gmupt_sbvh_default_params(&params); // default Platform / BuildParams of Source/BVHWrapper.cpp:52-54
@@ -32,4 +38,21 @@ void BVHWrapper::buildSBVH(const MeshData& scene)
 	mGPUTree.resize(builder.numNodes());
 	mIndices.resize(builder.numReferences());
 	builder.flatten(scene.vertexMaterial.data(), mGPUTree.data(), mIndices.data(), nullptr);
+}
+
+void BVHWrapper::buildLBVH(const MeshData& scene, unsigned maxLeafSize)
+{
+	fillProperties(scene);
+
+	gmupt_lbvh_params params;
+	gmupt_lbvh_default_params(&params);
+	params.max_leaf_size = maxLeafSize;
+	const size_t n = scene.numTriangles();
+	mGPUTree.assign(n ? 2 * n - 1 : 0, BVHNode{});
+	mIndices.assign(n, Triangle{});
+	if (gmupt_lbvh_build_host(mVertices.data(), static_cast<uint32_t>(scene.numVertices()), scene.indices.data(), static_cast<uint32_t>(n),
+	                          scene.vertexMaterial.data(), &params, mGPUTree.data(), mIndices.data(), nullptr, &mLBVHInfo) != GMUPT_OK)
+		throw std::runtime_error(gmupt_last_error());
+	mGPUTree.resize(mLBVHInfo.num_nodes);
+	mSAH = 0.f;
 }

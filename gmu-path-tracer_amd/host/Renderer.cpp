@@ -19,6 +19,7 @@ Renderer::Renderer(void* hwnd, Resolution resolution, const std::string& scene, 
 	, mPoolPaths(poolPaths)
 	, mLivePaths(livePaths)
 {
+	mHipDevice = hipDevice;
 	createDevice(hipDevice);
 	createBuffers(resolution);
 	initScene(scene);
@@ -52,6 +53,7 @@ void Renderer::createBuffers(Resolution res)
 void Renderer::initScene(const std::string& name)
 {
 	mScene = Scene(mDevice.get(), name); // old resources die with the temporary (Source/Renderer.cpp:55)
+	mScene.mHipDevice = mHipDevice;
 	mScene.mCamera.getBuffer()->lightCount = static_cast<uint32_t>(mScene.lightCount() < 2 ? 2 : mScene.lightCount()); // Camera.hpp:20: never below the default 2
 	mSceneBound = false;
 }
@@ -196,6 +198,18 @@ gmupt_refit_info Renderer::refitScene(bool keepHistory)
 	check(gmupt_renderer_refit(mRenderer.get(), &info));
 	mScene.mCamera.getBuffer()->iterationCounter = -1; // paths in flight carry hits of the old geometry
 	if (!keepHistory) resetHistory();
+	return info;
+}
+
+gmupt_lbvh_info Renderer::rebuildScene(unsigned maxLeafSize, const std::vector<int32_t>* indices)
+{
+	const gmupt_lbvh_info info = mScene.rebuildOnDevice(maxLeafSize, indices);
+	mSceneBound = false;
+	bindScene();                                       // waits for the renderer's stream before it lets go of the old tree
+	mScene.mRetiredBVHBuffer.reset();
+	mScene.mRetiredIndexBuffer.reset();
+	mScene.mCamera.getBuffer()->iterationCounter = -1; // paths in flight carry hits of the old tree's records
+	resetHistory();
 	return info;
 }
 

@@ -70,6 +70,10 @@ public:
 	// (gmupt_renderer_refit; the topology of the tree stays), the accumulation restarted, the temporal history dropped -- or kept
 	// (keepHistory) for denoiseTemporalMotion, which follows the moved surface.  Throws like the other wrappers.
 	gmupt_refit_info refitScene(bool keepHistory = false);
+	// geometry a refit does not cover (after Scene::setVertices with vertices that moved far, or with another triangle list): a new tree
+	// from the GPU LBVH builder (Scene::rebuildOnDevice) bound in place of the old one, the accumulation restarted and the temporal history
+	// dropped -- a new binding is a new geometry.  The host pass of the bind (the traversal tables) runs as for any bind.
+	gmupt_lbvh_info rebuildScene(unsigned maxLeafSize = 4, const std::vector<int32_t>* indices = nullptr);
 
 private:
 	void createDevice(int hipDevice);
@@ -90,6 +94,7 @@ private:
 	Resolution mResolution;
 	RowBand mBand;
 	unsigned mPoolPaths, mLivePaths;
+	int mHipDevice = 0;
 	bool mSceneBound = false, mCameraSet = false;
 	bool mHasResize = false, mCaptureRequested = false;
 	Resolution mPendingResize{};

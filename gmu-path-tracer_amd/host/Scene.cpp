@@ -1,10 +1,21 @@
 #include "Scene.hpp"
 #include <stdexcept>
 #include <thread>
+#include <hip/hip_runtime_api.h>
 
 namespace {
 void check(int rc) { if (rc != GMUPT_OK) throw std::runtime_error(gmupt_last_error()); }
+DeviceMemory upload(const void* src, size_t bytes, const char* what)
+{
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error(std::string("rebuildOnDevice: cannot allocate the ") + what);
+	DeviceMemory mem(d);
+	if (hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error(std::string("rebuildOnDevice: cannot upload the ") + what);
+	return mem;
 }
+}
+
+void DeviceFree::operator()(void* p) const { (void)hipFree(p); }
 
 Scene::Scene(gmupt_device* device, const std::string& path)
 	: mDevice(device)
@@ -136,6 +147,35 @@ void Scene::setVertices(const std::vector<float>& xyz, const std::vector<float>*
 		check(gmupt_buffer_update(mTriangleProperties.get(), props.data(), props.size() * sizeof(gmupt_tri_props)));
 		mScene.normals = *normals;
 	}
+}
+
+gmupt_lbvh_info Scene::rebuildOnDevice(unsigned maxLeafSize, const std::vector<int32_t>* indices)
+{
+	const std::vector<int32_t>& list = indices ? *indices : mScene.indices;
+	if (list.empty() || list.size() % 3 != 0) throw std::runtime_error("rebuildOnDevice: " + std::to_string(list.size()) + " indices are no triangle list");
+	if (mHipDevice >= 0 && hipSetDevice(mHipDevice) != hipSuccess) throw std::runtime_error("rebuildOnDevice: cannot select device " + std::to_string(mHipDevice));
+	if (!mLBVH) { gmupt_lbvh* h = nullptr; check(gmupt_lbvh_create(mDevice, &h)); mLBVH.reset(h); }
+	if (!mDeviceVertexMaterial) mDeviceVertexMaterial = upload(mScene.vertexMaterial.data(), mScene.vertexMaterial.size() * sizeof(uint32_t), "vertex materials");
+	if (list.size() > mDeviceIndexCapacity)
+	{
+		mDeviceIndices = upload(list.data(), list.size() * sizeof(int32_t), "indices");
+		mDeviceIndexCapacity = list.size();
+	}
+	else if (hipMemcpy(mDeviceIndices.get(), list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+		throw std::runtime_error("rebuildOnDevice: cannot upload the indices");
+
+	gmupt_lbvh_params params;
+	gmupt_lbvh_default_params(&params);
+	params.max_leaf_size = maxLeafSize;
+	gmupt_lbvh_info info{};
+	gmupt_buffer *nodes = nullptr, *tris = nullptr;
+	check(gmupt_lbvh_build(mLBVH.get(), mVertexBuffer.get(), static_cast<const int32_t*>(mDeviceIndices.get()), static_cast<uint32_t>(list.size() / 3),
+	                       static_cast<const uint32_t*>(mDeviceVertexMaterial.get()), &params, &nodes, &tris, nullptr, &info));
+	if (!mRetiredBVHBuffer) { mRetiredBVHBuffer = std::move(mBVHBuffer); mRetiredIndexBuffer = std::move(mIndexBuffer); }   // (else: never bound, dropped below)
+	mBVHBuffer.reset(nodes);
+	mIndexBuffer.reset(tris);
+	if (indices) mScene.indices = *indices;
+	return info;
 }
 
 void Scene::setLights(const std::vector<Light>& lights)

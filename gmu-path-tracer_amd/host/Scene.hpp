@@ -45,6 +45,9 @@ private:
 
 struct BufferDeleter { void operator()(gmupt_buffer* b) const { gmupt_buffer_destroy(b); } };
 using Buffer = std::unique_ptr<gmupt_buffer, BufferDeleter>;
+struct LbvhDeleter { void operator()(gmupt_lbvh* h) const { gmupt_lbvh_destroy(h); } };
+struct DeviceFree { void operator()(void* p) const; };   // hipFree
+using DeviceMemory = std::unique_ptr<void, DeviceFree>;
 
 class Scene
 {
@@ -66,6 +69,13 @@ public:
 	// optionally, new normals -- into the mesh data, the vertex buffer and the normals inside the property buffer.  The tree keeps its
 	// topology: call Renderer::refitScene() afterwards.  Throws std::runtime_error on a wrong count or a failed upload.
 	void setVertices(const std::vector<float>& xyz, const std::vector<float>* normals = nullptr);
+	// geometry beyond a refit (vertices that moved far, another triangle list): a new tree from the GPU LBVH builder (gmupt_lbvh_build,
+	// include/gmupt.h "LBVH") over the device-resident vertex buffer.  indices: 3 per triangle into the loaded vertices, replacing the mesh's
+	// list; nullptr keeps it.  The builder handle and the device copy of the indices / vertex materials are created on first use and kept.
+	// The node and triangle buffers are replaced; the renderer still reads the old ones until it binds again, so call this through
+	// Renderer::rebuildScene(), which does.  Throws std::runtime_error (a bad index, a non-finite used vertex, ...) and then keeps the tree, the buffers and the mesh's
+	// triangle list as they were (only the internal device copy of the index list may hold the refused one; the next call uploads again).
+	gmupt_lbvh_info rebuildOnDevice(unsigned maxLeafSize = 4, const std::vector<int32_t>* indices = nullptr);
 
 private:
 	void loadScene(const std::string& path);
@@ -87,6 +97,13 @@ private:
 	Buffer mLightBuffer;
 	Buffer mMaterialPropertyBuffer;
 	Buffer mDiffuse, mMetallicRoughness, mNormal; // Texture2DArray t5..t7 (Include/Scene.hpp:108-110); null when the scene has none
+
+	// rebuildOnDevice: the builder, its inputs on the device, and the tree the renderer is still bound to until Renderer::rebuildScene rebinds
+	std::unique_ptr<gmupt_lbvh, LbvhDeleter> mLBVH;
+	DeviceMemory mDeviceIndices, mDeviceVertexMaterial;
+	size_t mDeviceIndexCapacity = 0;
+	int mHipDevice = -1;                          // set by the Renderer that owns the scene: the device of rebuildOnDevice's own allocations
+	Buffer mRetiredBVHBuffer, mRetiredIndexBuffer;
 
 	std::array<Light, MAX_LIGHTS> mLights{};
 	size_t mLightCount = 0;

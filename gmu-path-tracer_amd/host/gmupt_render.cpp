@@ -17,6 +17,11 @@
 //                [--vertices FILE]                        before the frames: moved positions for all vertices of the scene (raw little-endian float32,
 //                                                         3 per vertex) through Scene::setVertices + Renderer::refitScene; one JSON line with the
 //                                                         refit info; not with --ranks
+//                [--builder sbvh|lbvh [--leaf L]]         lbvh: before the frames (after --vertices) the tree is rebuilt on the GPU from the resident
+//                                                         vertices (Renderer::rebuildScene: Scene::rebuildOnDevice + bind), leaves of at most L
+//                                                         triangles (default 4); one JSON line with the build info; not with --ranks.
+//                                                         With --build-only: BVHWrapper::buildLBVH, the host reference of that build
+//                [--dump-tree FILE]                       with --build-only: the flattened tree, raw: the 48-byte nodes, then the 16-byte triangle records
 //                [--help]                                 this list
 #include <chrono>
 #include <cstddef>
@@ -84,6 +89,7 @@ int main(int argc, char** argv)
 	std::string aovPrefix; unsigned aovSamples = 1;
 	std::string denoisePrefix;
 	std::string temporalPrefix;
+	std::string builder = "sbvh", dumpTree; unsigned leaf = 4;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
 		auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -110,6 +116,9 @@ int main(int argc, char** argv)
 		else if (a == "--denoise") denoisePrefix = next();
 		else if (a == "--vertices") verticesFile = next();
 		else if (a == "--temporal") temporalPrefix = next();
+		else if (a == "--builder") { builder = next(); if (builder != "sbvh" && builder != "lbvh") { std::fprintf(stderr, "--builder takes sbvh or lbvh\n"); return 2; } }
+		else if (a == "--leaf") { char* end = nullptr; const char* v = next(); leaf = std::strtoul(v, &end, 10); if (end == v || *end || leaf < 1 || leaf > 64) { std::fprintf(stderr, "--leaf takes a number in 1..64\n"); return 2; } }
+		else if (a == "--dump-tree") dumpTree = next();
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -121,6 +130,9 @@ int main(int argc, char** argv)
 			            "             [--temporal PREFIX] the temporal preview after the frames (PREFIX.pfm); with --vertices the frames are rendered on the loaded pose first,\n"
 			            "                                 then on the moved one, and the preview keeps its history across the refit (Renderer::denoiseTemporalMotion)\n"
 			            "             [--vertices FILE]   before the frames: moved positions of all vertices (raw float32 xyz), refitted on the GPU; not with --ranks\n"
+			            "             [--builder sbvh|lbvh [--leaf L]]   lbvh: the tree rebuilt on the GPU before the frames (linear BVH, leaves of at most L triangles,\n"
+			            "                                 default 4), one JSON line with the build info; not with --ranks.  With --build-only: the host reference of that build\n"
+			            "             [--dump-tree FILE]  with --build-only: the flattened tree, raw (48-byte nodes, then 16-byte triangle records)\n"
 			            "             [--denoise PREFIX [--aov-samples S]]   after the frames: the frame through the a-trous denoiser guided by the AOV buffers\n"
 			            "                            (S samples per axis): PREFIX.pfm (PF) and PREFIX.png (8-bit, truncated like --capture); not with --ranks\n");
 			return 0;
@@ -179,11 +191,17 @@ int main(int argc, char** argv)
 			for (size_t i = 0; i < mesh.materials.size(); i++) { char buf[96]; std::snprintf(buf, sizeof(buf), "%s[%d, %d, %d]", i ? ", " : "", mesh.materials[i].textureIndices[0], mesh.materials[i].textureIndices[1], mesh.materials[i].textureIndices[2]); texInfo += buf; }
 			texInfo += "]";
 			const auto t0 = std::chrono::steady_clock::now();
-			BVHWrapper bvh(mesh);
+			BVHWrapper bvh(mesh, builder == "lbvh" ? BVHWrapper::Builder::LBVH : BVHWrapper::Builder::SBVH, leaf);
 			const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 			float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
 			for (size_t i = 0; i < mesh.numVertices(); i++) for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], mesh.vertices[3 * i + k]); hi[k] = std::max(hi[k], mesh.vertices[3 * i + k]); }
 			size_t glass = 0; for (const auto& m : mesh.materials) glass += m.materialType == GMUPT_MATERIAL_GLASS;
+			if (!dumpTree.empty()) {
+				std::FILE* f = std::fopen(dumpTree.c_str(), "wb");
+				if (!f || std::fwrite(bvh.tree().data(), sizeof(gmupt_bvh_node), bvh.tree().size(), f) != bvh.tree().size() ||
+				    std::fwrite(bvh.indices().data(), sizeof(gmupt_triangle), bvh.indices().size(), f) != bvh.indices().size()) throw std::runtime_error("cannot write " + dumpTree);
+				std::fclose(f);
+			}
 			std::printf("{\"triangles\": %zu, \"vertices\": %zu, \"materials\": %zu, \"glass_materials\": %zu, \"nodes\": %zu, \"references\": %zu, \"sah\": %.6f, \"build_s\": %.4f, \"bbox\": [%.6f, %.6f, %.6f, %.6f, %.6f, %.6f], \"textures\": %s}\n",
 			            mesh.numTriangles(), mesh.numVertices(), mesh.materials.size(), glass, bvh.tree().size(), bvh.indices().size(), bvh.sah(), s, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], texInfo.c_str());
 			return 0;
@@ -196,6 +214,8 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--denoise filters the frame of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
 		if (!verticesFile.empty() && ranks > 1)
 			throw std::invalid_argument("--vertices moves the geometry of a single process: it cannot be combined with --ranks N > 1");
+		if (builder == "lbvh" && ranks > 1)
+			throw std::invalid_argument("--builder lbvh rebuilds the tree of a single process: it cannot be combined with --ranks N > 1");
 		if (ranks > 1 || !rendezvous.empty())
 		{
 			// one process per GPU: row band `rank` of `ranks`, the camera of the whole frame; the bands meet on rank 0 (RCCL send / receive)
@@ -237,6 +257,10 @@ int main(int argc, char** argv)
 			renderer.scene().setVertices(xyz);
 			const gmupt_refit_info info = renderer.refitScene(!temporalPrefix.empty());
 			std::printf("{\"refit\": {\"rebuilt\": %u, \"reason\": %u, \"levels\": %u, \"opened_nodes\": %u, \"ms\": %.6g}}\n", info.rebuilt, info.reason, info.levels, info.opened_nodes, info.ms);
+		}
+		if (builder == "lbvh") {
+			const gmupt_lbvh_info info = renderer.rebuildScene(leaf);
+			std::printf("{\"lbvh\": {\"num_nodes\": %u, \"num_leaves\": %u, \"depth\": %u, \"num_tris\": %u, \"ms\": %.6g}}\n", info.num_nodes, info.num_leaves, info.depth, info.num_tris, info.ms);
 		}
 		for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
 		if (capture) { renderer.requestCapture(); renderer.update(0.f); std::printf("capture %s\n", renderer.lastCapturePath().c_str()); }

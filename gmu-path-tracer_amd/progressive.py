@@ -30,6 +30,8 @@ class ProgressiveSession:
         self.previews = 0
         self.temporal = None   # the history handle of denoised_temporal, created on first use
         self.motion = bool(motion)   # denoised_temporal goes through the motion entry point (also set by set_vertices(keep_history=True))
+        self.lbvh = None       # the GPU tree builder of rebuild(), created on first use
+        self._indices = None   # the index list of the last rebuild()
 
     # ---- events (applied before the next frame, like the GUI callbacks of the reference)
     def move_camera(self, mouse_dx=0.0, mouse_dy=0.0, w=False, s=False, a=False, d=False):
@@ -68,6 +70,42 @@ class ProgressiveSession:
         elif not keep_history and self.temporal is not None:
             self.temporal.reset()
         return info
+
+    def rebuild(self, scene_buffers, verts=None, indices=None, vertex_material=None, max_leaf_size=4):
+        """The geometry changed beyond what a refit covers -- vertices that moved far, or another triangle list (a cut, a spawn, an LOD
+        switch): upload `verts` when given (at most the vertex count the buffer was created with), build an LBVH on the GPU from the
+        device-resident vertices (capi.Lbvh, gmupt_lbvh_build), put its node and triangle buffers into `scene_buffers` (the old ones are
+        closed), bind, restart the accumulation and drop the temporal history: a new binding is a new geometry.
+        indices: (n, 3) int32, numpy or a torch device tensor; None = the list of the last rebuild(), or, before any, the triangle
+        records the scene is bound to (an SBVH's spatial splits then appear as repeated triangles).  vertex_material: per vertex; None =
+        the materialID column of the property records.  Returns the gmupt_lbvh_info dict."""
+        from . import capi
+        if verts is not None:
+            scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
+        if indices is None:
+            indices = self._indices if self._indices is not None else scene_buffers.tris.read(capi.triangle_dtype)["v"]
+        if vertex_material is None:
+            vertex_material = np.ascontiguousarray(scene_buffers.props.read(capi.tri_props_dtype)["materialID"])
+        if self.lbvh is None:
+            self.lbvh = capi.Lbvh(self.renderer.dev)
+        nodes, tris, info = self.lbvh.build(scene_buffers.verts, indices, vertex_material, max_leaf_size=max_leaf_size)
+        old = (scene_buffers.nodes, scene_buffers.tris)
+        scene_buffers.nodes, scene_buffers.tris = nodes, tris
+        self.renderer.bind_scene(scene_buffers)      # waits for the renderer's stream before it touches anything
+        for b in old:
+            b.close()
+        self._indices = indices
+        self.camera.reset_accumulation()
+        if self.temporal is not None:
+            self.temporal.reset()
+        return info
+
+    def close(self):
+        """Releases what the session itself created: the tree builder of rebuild() and the history handle of denoised_temporal()."""
+        if self.lbvh is not None:
+            self.lbvh.close(); self.lbvh = None
+        if self.temporal is not None:
+            self.temporal.close(); self.temporal = None
 
     def resize(self, width, height, rows=None):
         """Resolution switch (Renderer.cpp:146-150,408-413): new accumulation target, camera vectors for the new aspect, restart."""

@@ -228,9 +228,15 @@ def textured_mesh(seed=5):
     return m
 
 
-def build_scene(mesh, sbvh_params=None):
-    """BVHWrapper::buildSBVH: host SBVH build + flatten -> the buffers Renderer::draw binds (t0-t4, b1)."""
-    built = capi.sbvh_build(mesh["verts"], mesh["indices"], mesh["vertex_material"], sbvh_params)
+def build_scene(mesh, sbvh_params=None, builder="sbvh", max_leaf_size=4):
+    """BVHWrapper::buildSBVH: host SBVH build + flatten -> the buffers Renderer::draw binds (t0-t4, b1).  builder="lbvh": the tree of
+    gmupt_lbvh_build_host instead (the host reference of the GPU builder; capi.Lbvh builds the same arrays on the device)."""
+    if builder == "sbvh":
+        built = capi.sbvh_build(mesh["verts"], mesh["indices"], mesh["vertex_material"], sbvh_params)
+    elif builder == "lbvh":
+        built = capi.lbvh_build_host(mesh["verts"], mesh["indices"], mesh["vertex_material"], max_leaf_size)
+    else:
+        raise ValueError("build_scene: builder %r is neither 'sbvh' nor 'lbvh'" % (builder,))
     nv = mesh["verts"].shape[0]
     props = np.zeros(nv, dtype=capi.tri_props_dtype)
     props["normal"] = mesh["normals"]

@@ -562,6 +562,65 @@ int gmupt_temporal_denoise_image_motion(gmupt_temporal* t, const float* beauty_r
 int gmupt_render_denoised_temporal_motion(gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
                                           float* out_rgba, size_t bytes, gmupt_trace_info* info /* may be NULL */);
 
+/* ---- LBVH: a tree for new geometry built on the GPU (an extension; the reference builds once on the host) ----
+ * A linear BVH (Lauterbach et al. 2009: Morton keys and a radix sort; Karras 2012: the hierarchy as a binary radix tree) over the
+ * device-resident vertex buffer, in the node / triangle layout above: gmupt_renderer_bind_scene, gmupt_renderer_refit, the ray queries, the
+ * AOVs and the CPU oracle take it like an SBVH.  Its quality is lower than the SBVH's (no surface-area heuristic, no spatial splits); it is
+ * for rebuilds between frames -- a mesh that moved far or changed its triangle list -- while gmupt_sbvh_build stays the default.
+ *
+ * The rule (binary32, no contraction, correctly rounded division; lo / hi as in the refit section; gmupt_lbvh_build_host and the kernels
+ * run the same statements, csrc/pt_lbvh.hpp).  Input: num_verts vertices, num_tris index triples (each index in [0, num_verts)), an
+ * optional vertex_material[num_verts], max_leaf_size L in 1..64 (default 4).
+ *   1. Box and centre of triangle i: bmin = bmax = v0, then v1 and v2 folded in (bmin = lo(bmin, p), bmax = hi(bmax, p));
+ *      c = (bmin + bmax) * 0.5f per component.
+ *   2. cmin / cmax = the minimum / maximum of all c by value, per component (the sign of a zero has no effect below); ext = cmax - cmin.
+ *   3. Per axis: ext > 0: x = ((c - cmin) / ext) * 2097152.0f, q = min(2097151u, (uint32_t)x); else q = 0.  (x lies in [0, 2^21] when the
+ *      centres are finite.  Huge finite vertices can overflow a centre or ext; a NaN or infinite x gives q = 2097151.)
+ *   4. key (63 bits): bit 3k+2 = bit k of q.x, bit 3k+1 = bit k of q.y, bit 3k = bit k of q.z, k = 0..20.  The triangles are sorted
+ *      ascending by (key, i).  pos = position in that order, src[pos] = the triangle at that position.
+ *   5. Hierarchy: the binary radix tree over the positions 0 .. num_tris-1 with
+ *        delta(a, b) = clz64(key_a ^ key_b) if the keys differ, 64 + clz32(a ^ b) if they are equal (a, b positions), -1 outside the range.
+ *      Every node covers a range [first, last] of positions.  A range of more than one position splits at the highest differing bit of
+ *      its two ends: its children are [first, s] and [s + 1, last], s = the last position with delta(first, s) > delta(first, last).
+ *      The tree is a function of the sorted keys alone.  Depth: root 0, a child one more than its parent.
+ *   6. Leaves: a node whose range holds <= L positions is a leaf (the root too, when num_tris <= L); the nodes below it do not exist.
+ *   7. Numbering: the nodes that exist, by ascending (depth, first); root = 0.  Siblings are adjacent (right == left + 1) and children have
+ *      larger numbers than their parent, which bind and refit require.
+ *   8. Records.  Triangle record pos: v = the index triple of triangle src[pos] in input order, materialID = vertex_material ?
+ *      vertex_material[v[0]] : 0 -- what gmupt_sbvh_flatten writes.  ref_triangle[pos] = src[pos].
+ *      Leaf: left = first, right = last + 1, isLeaf = 1, box by the refit leaf rule (the three vertices of each record in index order).
+ *      Inner node: left = the number of the child [first, s], right = left + 1, isLeaf = 0, min / max = lo / hi of the left child's
+ *      and the right child's.  pad0 / pad1 / pad2 = 0.  Hence gmupt_bvh_refit_host on a fresh LBVH changes no byte.
+ *   9. Errors, nothing written / no buffer created: NULL or empty input, an index outside [0, num_verts), L outside 1..64, more than 2^30
+ *      triangles: GMUPT_ERR_INVALID_ARGUMENT.  A non-finite vertex that a triangle uses: GMUPT_ERR_INVALID_ARGUMENT (a vertex no triangle
+ *      uses may hold anything, as in refit).  A tree deeper than 64, the size of the traversal stacks: GMUPT_ERR_UNSUPPORTED (it takes more
+ *      than 2^k triangles whose centres coincide in a cell k levels from the bottom of the key space; the depth can never pass 96).
+ * gmupt_lbvh_build_host: the rule on host arrays, the reference of the device build.  nodes_out holds 2 * num_tris - 1 nodes (info->num_nodes
+ *   are written), tris_out num_tris records, ref_triangle_out (may be NULL) num_tris words.  info (may be NULL): ms = 0.
+ * gmupt_lbvh: a builder handle of a device.  It owns a stream, two events and the scratch of a build (keys, sort storage, parent links,
+ *   ranges, numbering and the staged outputs: about 190 bytes per triangle), allocated by the first build, grown when a larger mesh comes and
+ *   kept: a per-frame rebuild of a mesh that does not grow allocates only its two output buffers.
+ * gmupt_lbvh_build: vertices = a GMUPT_BUFFER_VERTICES buffer of the builder's device; device_indices = caller-owned DEVICE memory, 3 * num_tris
+ *   int32, 4-byte aligned; device_vertex_material = DEVICE uint32 per vertex, or NULL; device_ref_triangle = DEVICE int32 per triangle, or
+ *   NULL.  The whole build is enqueued on the builder's stream (it does not wait for other streams: finish work that writes the vertex buffer
+ *   first), then ONE small readback -- error flags, node count, depth, root box -- and a synchronise.  On success *nodes_out
+ *   (GMUPT_BUFFER_BVH_NODES, gmupt_buffer_size = num_nodes * 48) and *triangles_out (GMUPT_BUFFER_TRIANGLES, num_tris * 16) are new buffers
+ *   the caller destroys; they go into gmupt_renderer_bind_scene like any other.  Bit for bit the arrays of gmupt_lbvh_build_host.
+ *   info->ms = device time of the build's launches (hipEvents).  The host pass of bind (the traversal tables) still runs afterwards. */
+typedef struct { uint32_t max_leaf_size; } gmupt_lbvh_params;
+void gmupt_lbvh_default_params(gmupt_lbvh_params* p);
+typedef struct { uint32_t num_nodes, num_leaves, depth, num_tris; float root_min[3], root_max[3]; double ms; } gmupt_lbvh_info;   /* 48 bytes */
+int gmupt_lbvh_build_host(const float* verts, uint32_t num_verts, const int32_t* indices, uint32_t num_tris, const uint32_t* vertex_material /* may be NULL */,
+                          const gmupt_lbvh_params* params /* may be NULL */, gmupt_bvh_node* nodes_out, gmupt_triangle* tris_out,
+                          int32_t* ref_triangle_out /* may be NULL */, gmupt_lbvh_info* info /* may be NULL */);
+typedef struct gmupt_lbvh gmupt_lbvh;
+int gmupt_lbvh_create(gmupt_device* dev, gmupt_lbvh** out);
+void gmupt_lbvh_destroy(gmupt_lbvh* h);
+int gmupt_lbvh_build(gmupt_lbvh* h, const gmupt_buffer* vertices, const int32_t* device_indices, uint32_t num_tris,
+                     const uint32_t* device_vertex_material /* may be NULL */, const gmupt_lbvh_params* params /* may be NULL */,
+                     gmupt_buffer** nodes_out, gmupt_buffer** triangles_out, int32_t* device_ref_triangle /* may be NULL */,
+                     gmupt_lbvh_info* info /* may be NULL */);
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);
