@@ -244,6 +244,7 @@ SYMBOLS = {
     "gmupt_debug_travtables_build": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "gmupt_debug_travtables_data": (_P, [_P, C.c_int, C.POINTER(C.c_size_t)]),
     "gmupt_debug_travtables_destroy": (None, [_P]),
+    "gmupt_debug_read_travtable": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gmupt_debug_wide_tables_addressable": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "gmupt_sbvh_default_params": (None, [C.POINTER(SbvhParams)]),
     "gmupt_sbvh_build": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(SbvhParams), C.POINTER(_P)]),
@@ -716,6 +717,19 @@ class Renderer:
     def write_framebuffer(self, fb):
         fb = np.ascontiguousarray(fb, dtype=np.float32)
         _check(lib().gmupt_debug_write_framebuffer(self.h, _ptr(fb), fb.nbytes))
+
+    def read_travtables(self):
+        """gmupt_debug_read_travtable for every kind: what this renderer holds of the traversal tables, its scalars and its refit maps, as
+        {kind: uint8 array} with the keys of TRAVTABLE_KINDS, like travtables() (an absent table is empty)."""
+        out = {}
+        for which, kind in enumerate(TRAVTABLE_KINDS):
+            n = C.c_size_t(0)
+            _check(lib().gmupt_debug_read_travtable(self.h, which, None, 0, C.byref(n)))
+            buf = np.zeros(n.value, np.uint8)
+            if n.value:
+                _check(lib().gmupt_debug_read_travtable(self.h, which, _ptr(buf), buf.nbytes, C.byref(n)))
+            out[kind] = buf
+        return out
 
     def close(self):
         if self.h:

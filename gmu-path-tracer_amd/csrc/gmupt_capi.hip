@@ -259,6 +259,7 @@ struct gmupt_renderer {
     std::vector<void*> allocs;
     // packed traversal copy of the bound scene
     void* travNodes = nullptr; void* travTris = nullptr; void* travRecs = nullptr; void* travWide = nullptr; void* travPairs = nullptr; void* travPairRef = nullptr;
+    size_t travBytes[6] = { 0, 0, 0, 0, 0, 0 }; // bytes uploaded to each, in the order of trav_tables() (gmupt_debug_read_travtable)
     int travMode = 70; // GMUPT_TRAVERSAL: "wide" (default) both ray casts in one launch over the 4-wide collapse | "cast0" the same over the binary tree | "def0" separate launches; the other rungs of the ladder exist in -DGMUPT_VARIANTS builds only
     uint32_t castFlags = 0; // GMUPT_STAT_* bits of the ray-cast kernels launched since the last reset
     // ray queries (gmupt_trace_rays): work counters + statistics of their own, allocated on first use; one ray + one hit for gmupt_pick
@@ -456,9 +457,11 @@ static int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, c
     const std::array<void**, 6> dst = trav_tables(r);
     for (int k = 0; k < 6; k++) {
         if (*dst[k]) { HIP_TRY(hipFree(*dst[k])); *dst[k] = nullptr; }
+        r->travBytes[k] = 0;
         if (!up[k].bytes) continue;
         HIP_TRY(hipMalloc(dst[k], up[k].bytes));
         HIP_TRY(hipMemcpy(*dst[k], up[k].data, up[k].bytes, hipMemcpyHostToDevice));
+        r->travBytes[k] = up[k].bytes;
     }
     TravScene& t = r->p.trav;
     t.recs = (const Rec64*)r->travRecs; t.nodes = (const Node64*)r->travNodes; t.tris = (const Tri48*)r->travTris;
@@ -593,6 +596,40 @@ extern "C" const void* gmupt_debug_travtables_data(const gmupt_travtables* h, in
 }
 
 extern "C" void gmupt_debug_travtables_destroy(gmupt_travtables* h) { delete h; }
+
+// What the renderer holds of the tables above: the device tables as bind uploaded and refit rewrote them, the scalars of its TravScene,
+// the refit maps it keeps on the host.  Reads only.
+extern "C" int gmupt_debug_read_travtable(gmupt_renderer* r, int which, void* dst, size_t bytes, size_t* needed)
+{
+    if (!r || !needed) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_debug_read_travtable: null argument");
+    *needed = 0;
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_debug_read_travtable: no scene bound");
+    HIP_TRY(hipSetDevice(r->dev->id));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    const TravScene& t = r->p.trav;
+    TravScalars s{};
+    s.topCount = t.topCount; s.topCountDeep = t.topCountDeep; s.maxDepth = t.maxDepth; s.rootDesc = t.rootDesc;
+    for (int k = 0; k < 3; k++) { s.rootMin[k] = t.rootMin[k]; s.rootMax[k] = t.rootMax[k]; }
+    s.triBase = t.triBase; s.wideTopCount = t.wideTopCount; s.wideStackBound = t.wideStackBound; s.numPairs = t.numPairs; s.wideCount = t.wideCount;
+    const void* src = nullptr; size_t need = 0; bool onDevice = false;
+    auto table = [&](int k) { src = *trav_tables(r)[(size_t)k]; need = src ? r->travBytes[k] : 0; onDevice = true; };      // k: the order of trav_tables()
+    auto map = [&](const std::vector<uint32_t>& v) { src = v.data(); need = v.size() * 4; };
+    switch (which) {
+    case GMUPT_TT_NODE64: table(0); break; case GMUPT_TT_TRI48: table(1); break; case GMUPT_TT_REC64: table(2); break;
+    case GMUPT_TT_WNODE: table(3); break; case GMUPT_TT_TRIPAIR: table(4); break; case GMUPT_TT_PAIRREF: table(5); break;
+    case GMUPT_TT_SCALARS: src = &s; need = sizeof(s); break;
+    case GMUPT_TT_LEVEL_NODES: map(r->rfLevelNodes); break; case GMUPT_TT_LEVEL_OFF: map(r->rfLevelOff); break;
+    case GMUPT_TT_NODE_MAP: map(r->rfNodeMap); break; case GMUPT_TT_WIDE_MAP: map(r->rfWideMap); break; case GMUPT_TT_OPENED: map(r->rfOpened); break;
+    default: return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_debug_read_travtable: %d is no gmupt_travtable_kind", which);
+    }
+    *needed = need;
+    if (!dst && bytes == 0) return GMUPT_OK;                         // the size query
+    if (!dst || bytes < need) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_debug_read_travtable: %zu bytes given, %zu needed", bytes, need);
+    if (!need) return GMUPT_OK;
+    if (onDevice) HIP_TRY(hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
+    else std::memcpy(dst, src, need);
+    return GMUPT_OK;
+}
 
 extern "C" int gmupt_debug_wide_tables_addressable(uint32_t wide_nodes, uint32_t num_tris, uint32_t num_pairs)
 {

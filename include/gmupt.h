@@ -647,6 +647,14 @@ int gmupt_debug_travtables_build(const gmupt_bvh_node* nodes, uint32_t num_nodes
                                  const float* verts, uint32_t num_verts, int want_wide, int top_order_bfs, int node_pairing, gmupt_travtables** out);
 const void* gmupt_debug_travtables_data(const gmupt_travtables* h, int which /* gmupt_travtable_kind */, size_t* bytes);
 void gmupt_debug_travtables_destroy(gmupt_travtables* h);
+/* The same kinds read back from a renderer with a bound scene: the device tables as bind uploaded and refit rewrote them (GMUPT_TT_TRI48:
+ * the references and their sentinel; GMUPT_TT_REC64 in a -DGMUPT_VARIANTS build only), GMUPT_TT_SCALARS from the renderer's own copy of the
+ * 15 words above, the five maps from the host vectors the renderer keeps for refit.  Waits for the renderer's stream, sets *needed to the
+ * size of that table and copies it to dst when bytes >= *needed; dst == NULL with bytes == 0 asks for the size only.  A table the renderer
+ * does not hold (no wide copy: WNODE, TRIPAIR and PAIRREF, whose pairs then stay on the host; REC64 in the shipped build) has
+ * *needed = 0 and succeeds.  Errors: NULL renderer or `needed`, a buffer smaller than *needed (nothing written), an unknown kind:
+ * GMUPT_ERR_INVALID_ARGUMENT; no scene bound: GMUPT_ERR_NOT_BOUND.  It touches no frame, path state, queue, counter, statistic or table. */
+int gmupt_debug_read_travtable(gmupt_renderer* r, int which /* gmupt_travtable_kind */, void* dst, size_t bytes, size_t* needed);
 /* 1 when tables of these sizes are within the wide ray cast's signed 32-bit byte offsets -- wide_nodes * 128, (num_tris + 1) * 48 (the
  * references and their sentinel record) and num_pairs * 80 all below 2^31 -- else 0.  The one rule behind the renderer's choice of the wide
  * kernel and behind GMUPT_ERR_UNSUPPORTED of the ray queries; no device involved. */
