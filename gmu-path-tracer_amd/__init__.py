@@ -1,7 +1,7 @@
 """MI355X-native wavefront path tracer behind the GMU-Path-Tracer Renderer/Scene/Camera API.
 
 Package layout (only what the hot path needs):
-  csrc/   HIP kernels (pt_kernels.hip), deterministic math, C-ABI implementation (gmupt_capi.hip)
+  csrc/   HIP kernels (pt_kernels.hip), deterministic math, C-ABI implementation (gmupt_capi.hip and, by feature, gmupt_capi_{accel,query,denoise}.hip, gmupt_capi_host.cpp)
   host/   C++17 host side mirroring the reference classes: Camera, SBVH builder + flatten, Renderer/Scene
   capi.py ctypes binding of include/gmupt.h (plumbing for tests / bench; no compute in Python)
   scenes.py  seeded synthetic scenes of the BASELINE configurations

@@ -1,0 +1,295 @@
+// C-ABI of libgmupt.so: the entry points that never touch a device -- images, SBVH, camera, the *_host references, default parameters.
+#include "gmupt_internal.hpp"
+#include "../host/TextureLoader.hpp"
+#include "../host/png_reader.hpp"
+
+static int clamp_threads(uint32_t threads) { return (int)std::min(std::max(threads, 1u), 16u); }   // of the *_host references
+// what an image (or the rectangle of a record set) may measure
+static bool image_size_ok(uint32_t W, uint32_t H) { return W >= 1 && H >= 1 && W <= 65535 && H <= 65535 && (uint64_t)W * H <= (1ull << 28); }
+
+extern "C" int gmupt_image_decode_png(const void* png, size_t bytes, uint32_t* width, uint32_t* height, uint8_t** rgba)
+{
+    if (!png || !width || !height || !rgba) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_image_decode_png: null argument");
+    *rgba = nullptr; *width = *height = 0;
+    try {
+        gmupt::png::Image img = gmupt::png::decode(static_cast<const uint8_t*>(png), bytes);
+        uint8_t* mem = static_cast<uint8_t*>(std::malloc(img.rgba.size()));
+        if (!mem) return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_image_decode_png: out of host memory");
+        std::memcpy(mem, img.rgba.data(), img.rgba.size());
+        *rgba = mem; *width = img.width; *height = img.height;
+    } catch (const std::exception& e) { return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_image_decode_png: %s", e.what()); }
+    return GMUPT_OK;
+}
+
+extern "C" void gmupt_image_free(uint8_t* rgba) { std::free(rgba); }
+
+extern "C" int gmupt_image_resize_square(const uint8_t* rgba, uint32_t old_size, uint32_t new_size, uint8_t* dst)
+{
+    if (!rgba || !dst || old_size == 0 || new_size == 0) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_image_resize_square: null or empty argument");
+    try {
+        const std::vector<uint8_t> out = gmupt::resizeSquare(rgba, old_size, new_size);
+        std::memcpy(dst, out.data(), out.size());
+    } catch (const std::exception& e) { return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_image_resize_square: %s", e.what()); }
+    return GMUPT_OK;
+}
+
+extern "C" uint32_t gmupt_texture_common_size(const size_t* layer_bytes, uint32_t layers)
+{
+    if (!layer_bytes || layers == 0) return 0;
+    return gmupt::commonDimension(std::vector<size_t>(layer_bytes, layer_bytes + layers));
+}
+
+extern "C" int gmupt_bvh_refit_host(gmupt_bvh_node* nodes, uint32_t num_nodes, const gmupt_triangle* tris, uint32_t num_tris,
+                                    const float* verts, uint32_t num_verts, uint32_t threads)
+{
+    if (!nodes || num_nodes == 0 || (!tris && num_tris) || (!verts && num_verts)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_bvh_refit_host: null or empty array");
+    const std::string err = validate_tree("gmupt_bvh_refit_host", nodes, num_nodes, tris, num_tris, num_verts, 0);
+    if (!err.empty()) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+    refit_host(nodes, num_nodes, tris, verts, clamp_threads(threads));
+    return GMUPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ denoiser
+static_assert(sizeof(gmupt_denoise_params) == 20 && offsetof(gmupt_denoise_params, sigma_color) == 4 && offsetof(gmupt_denoise_params, sigma_normal) == 8 &&
+              offsetof(gmupt_denoise_params, sigma_plane) == 12 && offsetof(gmupt_denoise_params, sigma_albedo) == 16, "gmupt_denoise_params layout");
+
+extern "C" void gmupt_denoise_default_params(gmupt_denoise_params* p)
+{
+    if (!p) return;
+    p->passes = 5; p->sigma_color = 4.0f; p->sigma_normal = 128.0f; p->sigma_plane = 0.02f; p->sigma_albedo = 0.1f;
+}
+
+int denoise_params(const char* fn, const gmupt_denoise_params* p, DnParams& out)
+{
+    gmupt_denoise_params d;
+    if (!p) { gmupt_denoise_default_params(&d); p = &d; }
+    if (p->passes < 1 || p->passes > GMUPT_DENOISE_MAX_PASSES) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: passes = %u (1..%d)", fn, p->passes, GMUPT_DENOISE_MAX_PASSES);
+    const float s[4] = { p->sigma_color, p->sigma_normal, p->sigma_plane, p->sigma_albedo };
+    const char* names[4] = { "sigma_color", "sigma_normal", "sigma_plane", "sigma_albedo" };
+    for (int k = 0; k < 4; k++)
+        if (!(std::isfinite(s[k]) && s[k] > 0.0f)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %s = %g (finite and > 0)", fn, names[k], (double)s[k]);
+    out.passes = (int)p->passes; out.sigmaColor = s[0]; out.sigmaNormal = s[1]; out.sigmaPlane = s[2]; out.sigmaAlbedo = s[3];
+    return GMUPT_OK;
+}
+
+// the arguments every denoiser entry checks; device pointers must be 16-byte aligned
+int denoise_args(const char* fn, const void* beauty, const void* aov, uint32_t W, uint32_t H, const gmupt_denoise_params* p, const void* out, size_t bytes,
+                 bool device, DnParams& prm)
+{
+    if (!beauty || !aov || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null beauty, aov or output", fn);
+    if (device && (((uintptr_t)beauty | (uintptr_t)aov | (uintptr_t)out) & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: misaligned pointer (16 bytes)", fn);
+    if (!image_size_ok(W, H)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: image of %ux%u (1..65535 each, at most 2^28 pixels)", fn, W, H);
+    {   // the last pass reads beauty texels of other pixels while it writes the output: the two ranges must not overlap at all
+        const uintptr_t b0 = (uintptr_t)beauty, o0 = (uintptr_t)out, n = (uintptr_t)W * H * 16;
+        if (o0 < b0 + n && b0 < o0 + n) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: the output overlaps the beauty image", fn);
+    }
+    if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu output bytes for %ux%u RGBA32F texels", fn, bytes, W, H);
+    return denoise_params(fn, p, prm);
+}
+
+extern "C" int gmupt_denoise_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height, const gmupt_denoise_params* p,
+                                  float* out_rgba, size_t out_bytes, uint32_t threads)
+{
+    DnParams prm;
+    GMUPT_TRY(denoise_args("gmupt_denoise_host", beauty_rgba, aov, width, height, p, out_rgba, out_bytes, false, prm));
+    try {
+        denoise_host(beauty_rgba, aov, (int)width, (int)height, prm, out_rgba, clamp_threads(threads));
+    } catch (const std::bad_alloc&) {
+        return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_denoise_host: out of host memory for %ux%u pixels", width, height);
+    } catch (const std::exception& e) {
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_denoise_host: %s", e.what());
+    }
+    return GMUPT_OK;
+}
+
+static_assert(sizeof(gmupt_temporal_params) == 32 && offsetof(gmupt_temporal_params, history_cap) == 20 && offsetof(gmupt_temporal_params, min_normal_cos) == 24 &&
+              offsetof(gmupt_temporal_params, plane_dist) == 28, "gmupt_temporal_params layout");
+extern "C" void gmupt_temporal_default_params(gmupt_temporal_params* p)
+{
+    if (!p) return;
+    gmupt_denoise_default_params(&p->spatial);
+    p->history_cap = 32.0f; p->min_normal_cos = 0.9f; p->plane_dist = 0.02f;
+}
+
+int temporal_params(const char* fn, const gmupt_temporal_params* p, DnParams& dn, TpParams& tp)
+{
+    gmupt_temporal_params d;
+    if (!p) { gmupt_temporal_default_params(&d); p = &d; }
+    GMUPT_TRY(denoise_params(fn, &p->spatial, dn));
+    if (!(std::isfinite(p->history_cap) && p->history_cap >= 0.0f && p->history_cap <= GMUPT_TEMPORAL_MAX_CAP))
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: history_cap = %g (0..%g)", fn, (double)p->history_cap, (double)GMUPT_TEMPORAL_MAX_CAP);
+    if (!(std::isfinite(p->min_normal_cos) && p->min_normal_cos <= 1.0f)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: min_normal_cos = %g (finite, <= 1)", fn, (double)p->min_normal_cos);
+    if (!(std::isfinite(p->plane_dist) && p->plane_dist >= 0.0f)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: plane_dist = %g (finite and >= 0)", fn, (double)p->plane_dist);
+    tp.cap = p->history_cap; tp.minCos = p->min_normal_cos; tp.planeDist = p->plane_dist;
+    return GMUPT_OK;
+}
+
+static int temporal_integrate_host(const char* fn, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion, uint32_t width, uint32_t height,
+                                   const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
+                                   uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
+                                   float* out_rgba, gmupt_history* out_history, uint32_t threads)
+{
+    if (!beauty_rgba || !aov || !out_rgba || !out_history) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null beauty, aov or output", fn);
+    if (!image_size_ok(width, height)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: image of %ux%u (1..65535 each, at most 2^28 pixels)", fn, width, height);
+    if (prev) {
+        if (!prev_cam) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: a previous record set without its camera", fn);
+        if (!image_size_ok(prev_width, prev_height) || prev_x0 > 65535 || prev_y0 > 65535)
+            return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: previous rectangle of %ux%u at (%u, %u) (1..65535 each, at most 2^28 pixels)", fn, prev_width, prev_height, prev_x0, prev_y0);
+    }
+    {   // the outputs may not overlap each other or any input
+        const size_t n = (size_t)width * height;
+        const uintptr_t o[2] = { (uintptr_t)out_rgba, (uintptr_t)out_history }, on[2] = { n * 16, n * sizeof(gmupt_history) };
+        const uintptr_t i[5] = { (uintptr_t)beauty_rgba, (uintptr_t)aov, (uintptr_t)prev, (uintptr_t)motion, (uintptr_t)out_history },
+                        in[5] = { n * 16, n * sizeof(gmupt_aov), prev ? (size_t)prev_width * prev_height * sizeof(gmupt_history) : 0,
+                                  motion ? n * sizeof(gmupt_motion) : 0, n * sizeof(gmupt_history) };
+        for (int a = 0; a < 2; a++)
+            for (int b = 0; b < (a == 0 ? 5 : 4); b++)
+                if (in[b] && o[a] < i[b] + in[b] && i[b] < o[a] + on[a]) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: an output overlaps another array", fn);
+    }
+    gmupt_temporal_params d;
+    if (!p) { gmupt_temporal_default_params(&d); p = &d; }
+    DnParams dn; TpParams tp;
+    GMUPT_TRY(temporal_params(fn, p, dn, tp));
+    try {
+        temporal_host(beauty_rgba, aov, motion, (int)width, (int)height, prev, prev_cam, (int)prev_x0, (int)prev_y0, (int)prev_width, (int)prev_height, tp,
+                      out_rgba, out_history, clamp_threads(threads));
+    } catch (const std::bad_alloc&) {
+        return fail(GMUPT_ERR_OUT_OF_MEMORY, "%s: out of host memory for %ux%u pixels", fn, width, height);
+    } catch (const std::exception& e) {
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %s", fn, e.what());
+    }
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_temporal_integrate_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height,
+                                             const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
+                                             uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
+                                             float* out_rgba, gmupt_history* out_history, uint32_t threads)
+{
+    return temporal_integrate_host("gmupt_temporal_integrate_host", beauty_rgba, aov, nullptr, width, height, prev, prev_cam, prev_x0, prev_y0, prev_width,
+                                   prev_height, p, out_rgba, out_history, threads);
+}
+
+extern "C" int gmupt_temporal_integrate_motion_host(const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion, uint32_t width, uint32_t height,
+                                                    const gmupt_history* prev, const gmupt_camera_buffer* prev_cam, uint32_t prev_x0, uint32_t prev_y0,
+                                                    uint32_t prev_width, uint32_t prev_height, const gmupt_temporal_params* p,
+                                                    float* out_rgba, gmupt_history* out_history, uint32_t threads)
+{
+    return temporal_integrate_host("gmupt_temporal_integrate_motion_host", beauty_rgba, aov, motion, width, height, prev, prev_cam, prev_x0, prev_y0, prev_width,
+                                   prev_height, p, out_rgba, out_history, threads);
+}
+
+extern "C" int gmupt_motion_host(const gmupt_hit* hits, const gmupt_aov* aov, size_t n, const gmupt_triangle* tris, uint32_t num_tris,
+                                 const float* verts_now, const float* verts_prev, uint32_t num_verts, gmupt_motion* out)
+{
+    const char* fn = "gmupt_motion_host";
+    if (n == 0) return GMUPT_OK;
+    if (!hits || !aov || !out || !tris || !verts_now || !verts_prev) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null array", fn);
+    for (size_t i = 0; i < n; i++) {
+        gmupt_hit h;
+        std::memcpy(&h, (const char*)hits + i * sizeof(h), sizeof(h));
+        if (h.triangle < 0 || h.light > 0u) continue;
+        if ((uint32_t)h.triangle >= num_tris) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: hit %zu names triangle record %d of %u", fn, i, h.triangle, num_tris);
+        gmupt_triangle T;
+        std::memcpy(&T, (const char*)tris + (size_t)h.triangle * sizeof(T), sizeof(T));
+        for (int k = 0; k < 3; k++)
+            if (T.v[k] < 0 || (uint32_t)T.v[k] >= num_verts) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: triangle record %d references vertex %d of %u", fn, h.triangle, T.v[k], num_verts);
+    }
+    motion_host(hits, aov, n, tris, verts_now, verts_prev, out);
+    return GMUPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ LBVH: the GPU builder (pt_lbvh.hip) and its host reference (pt_lbvh.cpp)
+static_assert(sizeof(gmupt_lbvh_info) == 48 && offsetof(gmupt_lbvh_info, ms) == 40, "gmupt_lbvh_info layout");
+
+extern "C" void gmupt_lbvh_default_params(gmupt_lbvh_params* p) { if (p) p->max_leaf_size = 4; }
+
+void lbvh_fill_info(gmupt_lbvh_info* info, const LbResult& res, uint32_t numTris, double ms)
+{
+    if (!info) return;
+    info->num_nodes = res.numNodes; info->num_leaves = res.numLeaves; info->depth = res.depth; info->num_tris = numTris;
+    for (int k = 0; k < 3; k++) { info->root_min[k] = res.rootMin[k]; info->root_max[k] = res.rootMax[k]; }
+    info->ms = ms;
+}
+
+int lbvh_leaf_size(const char* fn, const gmupt_lbvh_params* params, uint32_t* L)
+{
+    *L = params ? params->max_leaf_size : 4u;
+    if (*L < 1 || *L > kLbMaxLeaf) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: max_leaf_size %u outside 1..%u", fn, *L, kLbMaxLeaf);
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_lbvh_build_host(const float* verts, uint32_t num_verts, const int32_t* indices, uint32_t num_tris, const uint32_t* vertex_material,
+                                     const gmupt_lbvh_params* params, gmupt_bvh_node* nodes_out, gmupt_triangle* tris_out, int32_t* ref_triangle_out,
+                                     gmupt_lbvh_info* info)
+{
+    if (!verts || !indices || !nodes_out || !tris_out || num_verts == 0 || num_tris == 0) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build_host: null or empty array");
+    if (num_tris > kLbMaxTris) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_build_host: more than 2^30 triangles");
+    uint32_t L;
+    GMUPT_TRY(lbvh_leaf_size("gmupt_lbvh_build_host", params, &L));
+    LbResult res{};
+    int status = GMUPT_OK;
+    const std::string err = lbvh_build_host(verts, num_verts, indices, num_tris, vertex_material, L, nodes_out, tris_out, ref_triangle_out, res, &status);
+    if (status != GMUPT_OK) return fail(status, "gmupt_lbvh_build_host: %s", err.c_str());
+    lbvh_fill_info(info, res, num_tris, 0.0);
+    return GMUPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ host: SBVH
+extern "C" void gmupt_sbvh_default_params(gmupt_sbvh_params* p)
+{
+    if (!p) return;
+    p->split_alpha = 1.0e-5f; p->max_depth = 64; p->max_spatial_depth = 48; p->min_leaf_size = 1; p->max_leaf_size = 0x7FFFFFF;
+    p->node_cost = 1.0f; p->tri_cost = 1.0f;
+}
+
+extern "C" int gmupt_sbvh_build(const float* vertices, uint32_t num_vertices, const int32_t* indices, uint32_t num_triangles,
+                                const gmupt_sbvh_params* params, gmupt_sbvh** out)
+{
+    if (!out || (!vertices && num_vertices) || (!indices && num_triangles)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_sbvh_build: null argument");
+    *out = nullptr;
+    gmupt_sbvh_params prm; gmupt_sbvh_default_params(&prm);
+    if (params) prm = *params;
+    if (prm.max_depth < 1 || prm.max_depth > 64) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_sbvh_build: max_depth %d outside [1, 64]", prm.max_depth);
+    try {
+        gmupt_sbvh* h = new gmupt_sbvh();
+        h->b = new gmupt::SbvhBuilder(vertices, num_vertices, indices, num_triangles, prm);
+        h->b->build();
+        *out = h;
+    } catch (const std::exception& e) {
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_sbvh_build: %s", e.what());
+    }
+    return GMUPT_OK;
+}
+extern "C" uint32_t gmupt_sbvh_num_nodes(const gmupt_sbvh* h) { return h ? h->b->numNodes() : 0; }
+extern "C" uint32_t gmupt_sbvh_num_references(const gmupt_sbvh* h) { return h ? h->b->numReferences() : 0; }
+extern "C" float gmupt_sbvh_sah(const gmupt_sbvh* h) { return h ? h->b->sah() : 0.0f; }
+extern "C" uint32_t gmupt_sbvh_depth(const gmupt_sbvh* h) { return h ? h->b->depth() : 0; }
+extern "C" int gmupt_sbvh_flatten(const gmupt_sbvh* h, const uint32_t* vertex_material, gmupt_bvh_node* nodes, gmupt_triangle* triangles, int32_t* ref_triangle)
+{
+    if (!h || !nodes) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_sbvh_flatten: null argument");
+    h->b->flatten(vertex_material, nodes, triangles, ref_triangle);
+    return GMUPT_OK;
+}
+extern "C" void gmupt_sbvh_destroy(gmupt_sbvh* h) { if (h) { delete h->b; delete h; } }
+
+// ------------------------------------------------------------------------------------------------ host: camera
+extern "C" int gmupt_camera_create(uint32_t width, uint32_t height, gmupt_camera** out)
+{
+    if (!out || !width || !height) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_camera_create: bad argument");
+    *out = new (std::nothrow) gmupt_camera(width, height);
+    return *out ? GMUPT_OK : fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_camera_create: out of host memory");
+}
+extern "C" void gmupt_camera_destroy(gmupt_camera* c) { delete c; }
+extern "C" void gmupt_camera_update_resolution(gmupt_camera* c, uint32_t width, uint32_t height) { if (c) c->cam.updateResolution(width, height); }
+extern "C" void gmupt_camera_set_pose(gmupt_camera* c, float x, float y, float z, float pitch, float yaw) { if (c) { c->cam.setPosition(x, y, z); c->cam.setRotation(pitch, yaw); } }
+extern "C" void gmupt_camera_update(gmupt_camera* c, float dt) { if (c) c->cam.update(dt); }
+extern "C" void gmupt_camera_set_input(gmupt_camera* c, float mouse_dx, float mouse_dy, uint32_t keys_wsad)
+{
+    if (!c) return;
+    c->cam.addMouseDelta(mouse_dx, mouse_dy);
+    c->cam.setKeys((keys_wsad & 1u) != 0, (keys_wsad & 2u) != 0, (keys_wsad & 4u) != 0, (keys_wsad & 8u) != 0);
+}
+
+extern "C" void gmupt_camera_reset_accumulation(gmupt_camera* c) { if (c) c->cam.getBuffer()->iterationCounter = -1; }
+extern "C" gmupt_camera_buffer* gmupt_camera_get_buffer(gmupt_camera* c) { return c ? c->cam.getBuffer() : nullptr; }

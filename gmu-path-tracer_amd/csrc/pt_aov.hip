@@ -10,6 +10,7 @@
 #include "pt_device.hpp"
 #include "detmath.hpp"
 #include "pt_shading.hpp"
+#include "pt_launch.hpp"
 
 namespace gmupt {
 

@@ -25,6 +25,7 @@
 #include "detmath.hpp"
 #include "pt_kernel_util.hpp"
 #include "pt_shading.hpp"
+#include "pt_launch.hpp"
 
 namespace gmupt {
 

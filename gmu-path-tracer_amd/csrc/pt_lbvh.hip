@@ -17,6 +17,7 @@
 //   k_lb_level    inner boxes, one launch per depth 63 .. 0 on a fixed grid that strides over the nodes of that depth (the range comes
 //                 from device memory, an absent depth is an empty range): children are one level down, so no atomics and no waiting
 #include "pt_lbvh.hpp"
+#include "pt_launch.hpp"
 
 #include <algorithm>
 #include <cstring>

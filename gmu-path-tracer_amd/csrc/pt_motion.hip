@@ -8,6 +8,7 @@
 #include "pt_device.hpp"
 #include "detmath.hpp"
 #include "pt_motion.hpp"
+#include "pt_launch.hpp"
 
 #include <cstring>
 

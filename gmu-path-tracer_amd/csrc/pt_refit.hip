@@ -13,6 +13,7 @@
 // All arithmetic is pt_refit.hpp, which the host refit below runs too.  Indices are size_t: a table may pass 2 GiB.
 #include "pt_refit.hpp"
 #include "pt_denoise.hpp"
+#include "pt_launch.hpp"
 
 #include <algorithm>
 #include <vector>

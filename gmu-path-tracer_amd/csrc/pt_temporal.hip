@@ -12,6 +12,7 @@
 #include "detmath.hpp"
 #include "pt_denoise.hpp"
 #include "pt_temporal.hpp"
+#include "pt_launch.hpp"
 
 #include <cstring>
 #include <vector>

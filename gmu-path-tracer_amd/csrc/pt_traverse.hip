@@ -8,6 +8,7 @@
 // shadow acceptance rule t in (1e-8, 1e8), |d t| < lightDistance (shadowRayCast.hlsl:16-47,88-91).
 // What is free: memory layout, loop structure, scheduling of the triangle tests, and -- for the any-hit shadow ray -- the visit order.
 #include "pt_traverse_deferred.hpp"
+#include "pt_launch.hpp"
 
 namespace gmupt {
 

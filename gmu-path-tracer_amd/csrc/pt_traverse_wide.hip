@@ -30,6 +30,7 @@
 // left) and report their best hit back; results merge by "smaller t wins, equal t is a tie".
 #include "pt_traverse_deferred.hpp"
 #include "pt_travtables.hpp"
+#include "pt_launch.hpp"
 
 namespace gmupt {
 

@@ -5,8 +5,8 @@
         -fno-gpu-flush-denormals-to-zero -fno-fast-math --cuda-device-only -S -x hip csrc/pt_traverse_wide.hip -Iinclude -o wide.s
   python tools/isa_compare.py before.s after.s
 
-Other kernels of any source file: --kernel NAME (repeatable) pairs the kernels whose mangled name is gmupt::NAME with any parameter list,
-e.g. for csrc/pt_kernels.hip:
+Other kernels of any source file: --kernel NAME (repeatable) pairs the kernels whose mangled name is gmupt::NAME with any parameter list
+(the instantiations of a template by their mangled template arguments), e.g. for csrc/pt_kernels.hip:
 
   python tools/isa_compare.py --kernel k_clear --kernel k_logic --kernel k_material before.s after.s
 
@@ -29,7 +29,9 @@ def named(names):
     def match(line):
         m = pat.match(line)
         if m and m.group(3)[:int(m.group(2))] in names and len(m.group(3)) >= int(m.group(2)):
-            return m.group(3)[:int(m.group(2))], m.group(1)
+            n = int(m.group(2))
+            targs = m.group(1)[len("_ZN5gmupt") + len(m.group(2)) + n:]      # of a template: its mangled arguments keep the instantiations apart
+            return m.group(3)[:n] + (" " + targs if targs.startswith("I") else ""), m.group(1)
         return None
     return match
 
@@ -90,8 +92,8 @@ def main():
     match = named(set(names)) if names else cast_w
     a, b = kernels(files[0], match), kernels(files[1], match)
     ok = bool(a) or not names
-    if names and sorted(a) != sorted(names):
-        print("kernels not found in %s: %s" % (files[0], sorted(set(names) - set(a)))); ok = False
+    if names and {k.split(" ")[0] for k in a} != set(names):
+        print("kernels not found in %s: %s" % (files[0], sorted(set(names) - {k.split(" ")[0] for k in a}))); ok = False
     for key in sorted(a):
         if key not in b:
             print("%s: missing in %s" % (a[key]["name"], files[1])); ok = False; continue
