@@ -26,7 +26,6 @@ FLAGS = [
 # and a build of the wide ray cast whose stacks overflow on ordinary scenes.
 TEST_BUILDS = {"variants": ["-DGMUPT_VARIANTS"], "scan1": ["-DGMUPT_SCAN_GROUP=1"],
                "wides8": ["-DGMUPT_WIDE_STACK=8", "-DGMUPT_WIDE_TOP=64", "-DGMUPT_WIDE_PARK=4"]}   # wide ray cast with a tiny LDS share per lane: stacks run full, rays are parked for the exact walk all the time
-EXPERIMENT_BUILDS = {"wxcd": ["-DGMUPT_WIDE_XCD_EXPERIMENT=1"], "wsg0": ["-DGMUPT_WIDE_SIGNED=0"], "mrg0": ["-DGMUPT_MATERIAL_REGROUP=0"], "wq0": ["-DGMUPT_WIDE_QUADPK=0"], "wqt0": ["-DGMUPT_WIDE_QUADTRI=0"], "dnb0": ["-DGMUPT_DN_BATCH=0"]}   # name -> extra flags of A/B timing builds (tools/ only, never loaded by tests), e.g. {"wg1024": ["-DGMUPT_DEF_BLOCK=1024", "-DGMUPT_TOP_NODES=512"]}
 
 
 def lib_path(name=None):
@@ -48,7 +47,8 @@ def build(force=False, verbose=False, name=None):
     if not force and not needs_build(name):
         return lib
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    extra = os.environ.get("GMUPT_EXTRA_FLAGS", "").split() + ({**TEST_BUILDS, **EXPERIMENT_BUILDS}[name] if name else [])
+    # GMUPT_EXTRA_FLAGS: extra compiler flags of a one-off build for A/B timing, e.g. GMUPT_EXTRA_FLAGS="-DGMUPT_WIDE_REPS=4"
+    extra = os.environ.get("GMUPT_EXTRA_FLAGS", "").split() + (TEST_BUILDS[name] if name else [])
     cmd = [hipcc] + FLAGS + extra + ["-x", "hip"] + [os.path.join(HERE, s) for s in DEVICE_SOURCES + HOST_SOURCES] + ["-o", lib]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
@@ -65,11 +65,7 @@ def build_all(force=False, verbose=False):
 
 
 if __name__ == "__main__":
-    if "--experiments" in sys.argv:
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(4) as ex:
-            print("\n".join(ex.map(lambda n: build(force=True, name=n), sorted(EXPERIMENT_BUILDS))))
-    elif "--all" in sys.argv:
+    if "--all" in sys.argv:
         print("\n".join(build_all(force="--force" in sys.argv, verbose=True)))
     else:
         print(build(force="--force" in sys.argv, verbose=True))

@@ -235,7 +235,7 @@ extern "C" int gmupt_renderer_create(gmupt_device* dev, const gmupt_renderer_des
     p.travGridBlocks = (uint32_t)dev->prop.multiProcessorCount * ((env_u32("GMUPT_WAVES_PER_CU", 16u) * 64 + db - 1) / db);
     p.travGridBlocks = std::max(std::min(p.travGridBlocks, p.ovfStride / db), 1u);   // no more threads than the overflow stacks serve
     p.extendPrune = env_u32("GMUPT_EXTEND_PRUNE", 0u); p.shadowPrune = env_u32("GMUPT_SHADOW_PRUNE", 0u);
-    p.tuneWideSteps = env_u32("GMUPT_WIDE_STEPS", 0u); p.xcdBins = env_u32("GMUPT_XCD_BINS", 0u);
+    p.tuneWideSteps = env_u32("GMUPT_WIDE_STEPS", 0u);
     p.castLoopCap = env_u32("GMUPT_CAST_LOOP_CAP", 1u << 20);
     if (p.castLoopCap == 0) p.castLoopCap = 1u << 20;
     p.tuneRefill = env_u32("GMUPT_REFILL", 20u);

@@ -80,13 +80,8 @@ GM_HD float dn_initial_variance(const float4* col, const float4* nl, int W, int 
     return hmax(0.0f, m2 - m1 * m1);
 }
 
-// GMUPT_DN_BATCH (default 1): the loads of the nine variance words, and of the five taps of a row, are issued together before any of
-// them is tested, at addresses clamped into the image (a load whose tap is outside or invalid is made and ignored; invalid pixels have
-// zeroed guide planes).  0: one tap at a time, the validity test between the colour load and the guide loads (the experiment build
-// "dnb0" of build.py, for A/B timing).  Both run the same arithmetic in the same order: the result is the same bits.
-#ifndef GMUPT_DN_BATCH
-#define GMUPT_DN_BATCH 1
-#endif
+// dn_atrous issues the loads of the nine variance words, and of the five taps of a row, together before any of them is tested, at
+// addresses clamped into the image: a load whose tap is outside or invalid is made and ignored (invalid pixels have zeroed guide planes).
 
 GM_HD int dn_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
@@ -113,7 +108,6 @@ GM_HD float4 dn_atrous(const float4* col, const DnPlanes& g, int W, int H, int x
     const size_t p = (size_t)y * W + x;
     // 3x3 Gaussian of the variance over the valid neighbours, renormalised
     float gw = 0.0f, gv = 0.0f;
-#if GMUPT_DN_BATCH
     float vq[9];
 #pragma unroll
     for (int t = 0; t < 9; t++) vq[t] = col[(size_t)dn_clamp(y + t / 3 - 1, H - 1) * W + dn_clamp(x + t % 3 - 1, W - 1)].w;
@@ -124,20 +118,6 @@ GM_HD float4 dn_atrous(const float4* col, const DnPlanes& g, int W, int H, int x
         const float k = dn_h3(dx) * dn_h3(dy);
         gw = gw + k; gv = gv + k * vq[t];
     }
-#else
-    for (int dy = -1; dy <= 1; dy++) {
-        const int qy = y + dy;
-        if (qy < 0 || qy >= H) continue;
-        for (int dx = -1; dx <= 1; dx++) {
-            const int qx = x + dx;
-            if (qx < 0 || qx >= W) continue;
-            const float v = col[(size_t)qy * W + qx].w;
-            if (!dn_valid(v)) continue;
-            const float k = dn_h3(dx) * dn_h3(dy);
-            gw = gw + k; gv = gv + k * v;
-        }
-    }
-#endif
     const float gp = gv / gw;
     const float4 nlp = g.nl[p], xap = g.xa[p];
     const float2 agp = g.ag[p];
@@ -151,7 +131,6 @@ GM_HD float4 dn_atrous(const float4* col, const DnPlanes& g, int W, int H, int x
         const int qy = y + s * j;
         if (qy < 0 || qy >= H) continue;
         const size_t row = (size_t)qy * W;
-#if GMUPT_DN_BATCH
         float4 cq[5], nlq[5], xaq[5];
         float2 agq[5];
 #pragma unroll
@@ -165,16 +144,6 @@ GM_HD float4 dn_atrous(const float4* col, const DnPlanes& g, int W, int H, int x
             if (qx < 0 || qx >= W || !dn_valid(cq[t].w)) continue;
             dn_tap(a, c, cq[t], nlq[t], xaq[t], agq[t], dn_h5(t - 2) * dn_h5(j), prm);
         }
-#else
-        for (int i = -2; i <= 2; i++) {
-            const int qx = x + s * i;
-            if (qx < 0 || qx >= W) continue;
-            const size_t q = row + qx;
-            const float4 cq = col[q];
-            if (!dn_valid(cq.w)) continue;
-            dn_tap(a, c, cq, g.nl[q], g.xa[q], g.ag[q], dn_h5(i) * dn_h5(j), prm);
-        }
-#endif
     }
     if (!(a.sw > 0.0f)) return col[p];
     return make_float4(a.sr / a.sw, a.sg / a.sw, a.sb / a.sw, a.sv / (a.sw * a.sw));

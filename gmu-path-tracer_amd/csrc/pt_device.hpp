@@ -171,7 +171,7 @@ struct RenderParams {
     int* ovfStack;         // global overflow of the traversal stacks
     uint32_t ovfStride;    // threads of the traversal grid
     uint32_t raysPerWave;  // queue entries owned by one wave of the persistent ray-cast kernels
-    uint32_t* travCounters; // [0] extension, [1] shadow: next unassigned queue entry (zeroed by k_material every iteration); [4 + 8 phase + segment]: the same per queue segment (XCD experiment)
+    uint32_t* travCounters; // [0] extension, [1] shadow: next unassigned queue entry (zeroed by k_material every iteration)
     uint32_t travGridBlocks; // persistent ray-cast grid
     uint32_t extendPrune;  // 1: the extension ray skips boxes it enters beyond its current closest hit (see pt_traverse.hip)
     uint32_t shadowPrune;  // 1: the shadow ray skips boxes it enters beyond the light (cannot change its boolean result)
@@ -179,7 +179,7 @@ struct RenderParams {
     uint32_t tuneRefill, tuneTriThresh; // lane-refill / triangle-burst thresholds of the deferred-leaf kernels
     uint32_t tuneWideSteps;             // wide ray cast: steps per iteration (0: by table size; 6 or 8)
     uint32_t wideQuarterTail;           // wide ray cast (set at launch): the last half round of shadow-ray chunks in quarters
-    uint32_t xcdBins;      // experiment builds only (-DGMUPT_WIDE_XCD_EXPERIMENT): the queues are eight equal segments, a wave serves the segment of its XCD first
+    uint32_t reserved0;    // never read, always zero: holds the kernel-argument layout, and with it the compiled ray cast, where it was; removing it is a change to be timed on its own
     uint32_t castLoopCap;  // watchdog of the fused ray cast: loop iterations after which a wave gives up (GMUPT_STAT_CAST_ABORTED)
     gmupt_camera_buffer cam;
     SceneView scene;

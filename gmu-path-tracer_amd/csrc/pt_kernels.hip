@@ -390,9 +390,6 @@ __device__ __forceinline__ void stage_new_path(const RenderParams& p, uint32_t q
     p.queues[(size_t)Q_EXT_RAY * p.P + queueIndex] = index;                  // :51
 }
 
-#ifndef GMUPT_MATERIAL_REGROUP
-#define GMUPT_MATERIAL_REGROUP 1
-#endif
 __global__ __launch_bounds__(kBlock) void k_material(RenderParams p, int clearFrame)
 {
     __shared__ uint32_t s_cnt[kNumCounts][kBlock / 64];
@@ -456,7 +453,6 @@ __global__ __launch_bounds__(kBlock) void k_material(RenderParams p, int clearFr
             if (!clearFrame) { st->pathsCompleted += nEnded; st->segments += (unsigned long long)nEnded + nUE4 + nGlass; }
         }
     }
-#if GMUPT_MATERIAL_REGROUP
     // ---- the slots of the block regrouped by class before the stages run: thread j takes the j-th slot of the sequence (UE4 slots in slot order,
     // then glass, then ended).  The three stages are long and different (k_material is bound by VALU issue, not by memory): with the classes
     // mixed as the slots are, nearly every wave runs all three one after the other at 63 % of its lanes; regrouped, at most two waves of a block
@@ -491,27 +487,6 @@ __global__ __launch_bounds__(kBlock) void k_material(RenderParams p, int clearFr
         else stage_glass(p, rank, slot, extGlassOffset);
     }
 }
-#else
-    if (c > CLS_ENDED) return;
-    // rank = slots of the same class with a smaller index: block offset + earlier waves + lower lanes
-    const unsigned long long mine = (c == CLS_UE4) ? b0 : (c == CLS_GLASS) ? b1 : b2;
-    uint32_t rank = s_pre[c] + prefix_rank(mine);
-    for (uint32_t w = 0; w < wave; w++) rank += s_cnt[c][w];
-
-    if (c == CLS_ENDED) stage_new_path(p, rank, i, clearFrame);
-    else {
-        p.queues[(size_t)(c == CLS_UE4 ? Q_MAT_UE4 : Q_MAT_GLASS) * p.P + rank] = i; // logic.hlsl:282-285
-        if (c == CLS_UE4) {
-            uint32_t srank = 0;
-            if (shadow) {
-                srank = s_pre[3] + prefix_rank(b3);
-                for (uint32_t w = 0; w < wave; w++) srank += s_cnt[3][w];
-            }
-            stage_ue4(p, rank, i, srank, extUE4Offset);
-        } else stage_glass(p, rank, i, extGlassOffset);
-    }
-}
-#endif
 
 // ------------------------------------------------------------------------------------------------ detmath probe
 __global__ void k_detmath(int fn, const float* x, const float* y, float* out, uint32_t n)

@@ -46,15 +46,6 @@ namespace gmupt {
 #ifndef GMUPT_WIDE_PARK
 #define GMUPT_WIDE_PARK 16
 #endif
-#ifndef GMUPT_WIDE_QUADPK
-#define GMUPT_WIDE_QUADPK 1     // the packed slab arithmetic one plane row per asm statement (four operations per wait state)
-#endif
-#ifndef GMUPT_WIDE_QUADTRI
-#define GMUPT_WIDE_QUADTRI 1    // the same for the triangle-pair arithmetic (four statements)
-#endif
-#ifndef GMUPT_WIDE_SIGNED
-#define GMUPT_WIDE_SIGNED 1     // planes fetched in ray-sign order, ordered slab tree unless a walking ray of the wave has a special 1 / d
-#endif
 constexpr int kWideStack = GMUPT_WIDE_STACK;   // LDS words per lane shared by the two stacks
 constexpr int kWideTop = GMUPT_WIDE_TOP;       // WNodes of the tree top kept in LDS
 constexpr int kWideRoom = 4;                   // a node step pushes at most four entries
@@ -64,24 +55,7 @@ constexpr int kWideOvf = kMaxStack + 2 > kWideStack ? kMaxStack + 2 - kWideStack
 
 typedef int vec4i __attribute__((ext_vector_type(4)));
 
-// One WNode into registers: from the LDS copy of the tree top (the top walk), or from global memory (everything below the top)
-__device__ __forceinline__ void load_wnode_lds(const float4* s_top, int cur, vec4f& q0, vec4f& q1, vec4f& q2, vec4f& q3, vec4f& q4, vec4f& q5, vec4i& lk)
-{
-    const GMUPT_AS_LDS vec4f* n = (const GMUPT_AS_LDS vec4f*)(s_top) + cur * 8;
-    q0 = n[0]; q1 = n[1]; q2 = n[2]; q3 = n[5]; q4 = n[4]; q5 = n[3]; lk = *(const GMUPT_AS_LDS vec4i*)(n + 6);   // rows: min x, y, z, max z, y, x
-}
-__device__ __forceinline__ void load_wnode_glb(__amdgpu_buffer_rsrc_t nodes, int cur, vec4f& q0, vec4f& q1, vec4f& q2, vec4f& q3, vec4f& q4, vec4f& q5, vec4i& lk)
-{
-    const int off = cur * 128;
-    q0 = __builtin_bit_cast(vec4f, __builtin_amdgcn_raw_buffer_load_b128(nodes, off, 0, 0));
-    q1 = __builtin_bit_cast(vec4f, __builtin_amdgcn_raw_buffer_load_b128(nodes, off + 16, 0, 0));
-    q2 = __builtin_bit_cast(vec4f, __builtin_amdgcn_raw_buffer_load_b128(nodes, off + 32, 0, 0));
-    q3 = __builtin_bit_cast(vec4f, __builtin_amdgcn_raw_buffer_load_b128(nodes, off + 80, 0, 0));
-    q4 = __builtin_bit_cast(vec4f, __builtin_amdgcn_raw_buffer_load_b128(nodes, off + 64, 0, 0));
-    q5 = __builtin_bit_cast(vec4f, __builtin_amdgcn_raw_buffer_load_b128(nodes, off + 48, 0, 0));
-    lk = __builtin_bit_cast(vec4i, __builtin_amdgcn_raw_buffer_load_b128(nodes, off + 96, 0, 0));
-}
-
+// One WNode into registers: from the LDS copy of the tree top (the top walk), or from global memory (everything below the top).
 // The planes of a WNode in RAY-SIGN order: q0 .. q2 = the plane of each axis the ray meets first (row `axis` for a positive, row 5 - axis for a
 // negative 1 / d), q3 .. q5 = the other one.  Which row is a per-lane byte offset (RayPk's packed `sg`: bytes 0..2 = 0|80, 16|64, 32|48), added to
 // the lane's record address with one SDWA add per axis; the far row of every axis is at (2 * record + 80) - near address.
@@ -115,17 +89,6 @@ __device__ __forceinline__ void load_wnode_glb_signed(__amdgpu_buffer_rsrc_t nod
     lk = __builtin_bit_cast(vec4i, __builtin_amdgcn_raw_buffer_load_b128(nodes, (int)a.rec + 96, 0, 0));
 }
 
-// the slab test of ray_box (extensionRayCast.hlsl:79-94) on one slot; "hit" is `result > 0`, i.e. t1 >= t0 and (t0 > 0 ? t0 : t1) > 0,
-// which is t1 >= t0 && t1 > 0 (t1 >= t0 > 0 implies t1 > 0; a NaN fails both forms)
-__device__ __forceinline__ bool slab_hit(float mnx, float mny, float mnz, float mxx, float mxy, float mxz, f3 o, f3 invdir)
-{
-    const float fx = (mxx - o.x) * invdir.x, fy = (mxy - o.y) * invdir.y, fz = (mxz - o.z) * invdir.z;
-    const float nx = (mnx - o.x) * invdir.x, ny = (mny - o.y) * invdir.y, nz = (mnz - o.z) * invdir.z;
-    const float t1 = __builtin_fminf(__builtin_fmaxf(fx, nx), __builtin_fminf(__builtin_fmaxf(fy, ny), __builtin_fmaxf(fz, nz)));
-    const float t0 = __builtin_fmaxf(__builtin_fminf(fx, nx), __builtin_fmaxf(__builtin_fminf(fy, ny), __builtin_fminf(fz, nz)));
-    return (t1 >= t0) & (t1 > 0.0f);
-}
-
 // source-triangle number of a reference (word 10 of its Tri48 record): equal for the duplicated references of one triangle
 __device__ __forceinline__ uint32_t tri_canon(__amdgpu_buffer_rsrc_t tris, int i)
 {
@@ -137,24 +100,11 @@ __device__ __forceinline__ uint32_t tri_canon(__amdgpu_buffer_rsrc_t tris, int i
 // fminf / fmaxf that consumes a packed product; (2) a scalar operand that both halves must see (a ray component) it either copies into
 // a register pair of its own -- 18 registers this kernel does not have -- or re-aligns through SCRATCH memory in every step; the
 // instruction itself can take either half of an aligned pair for both results (op_sel).  So the ray lives in five aligned pairs (RayPk)
-// and each helper names the half it broadcasts.  Every packed instruction is followed by `s_nop 0`: on gfx950 its result may not be read
-// by the very next instruction (the compiler pads its own packed code the same way; it cannot see into an asm statement).
+// and each instruction names the half it broadcasts (op_sel).  Every statement of packed instructions ends with `s_nop 0`: on gfx950 a
+// packed result may not be read by the very next instruction (the compiler pads its own packed code the same way; it cannot see into an
+// asm statement), and inside a statement no instruction reads the result of the one before it.
 // v_min / v_max / v_min3 / v_max3 return the non-NaN operand like the HLSL min / max, and no operand here can be a signalling NaN
 // (products, and the quiet NaNs of empty slots).
-#ifndef GMUPT_WIDE_PK
-#define GMUPT_WIDE_PK 1
-#endif
-#define GMUPT_PK2(NAME, TEXT) __device__ __forceinline__ vec2f NAME(vec2f a, vec2f b) { vec2f r; asm(TEXT "\n\ts_nop 0" : "=v"(r) : "v"(a), "v"(b)); return r; }
-GMUPT_PK2(pk_mul, "v_pk_mul_f32 %0, %1, %2")                                                        // a * b
-GMUPT_PK2(pk_add, "v_pk_add_f32 %0, %1, %2")                                                        // a + b
-GMUPT_PK2(pk_sub, "v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]")                              // a - b
-GMUPT_PK2(pk_mul_lo, "v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]")                                     // a * (b.x, b.x)
-GMUPT_PK2(pk_mul_hi, "v_pk_mul_f32 %0, %1, %2 op_sel:[0,1]")                                        // a * (b.y, b.y)
-GMUPT_PK2(pk_sub_lo, "v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]")           // a - (b.x, b.x)
-GMUPT_PK2(pk_sub_hi, "v_pk_add_f32 %0, %1, %2 op_sel:[0,1] neg_lo:[0,1] neg_hi:[0,1]")              // a - (b.y, b.y)
-GMUPT_PK2(pk_lo_sub, "v_pk_add_f32 %0, %2, %1 op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]")           // (b.x, b.x) - a
-GMUPT_PK2(pk_hi_sub, "v_pk_add_f32 %0, %2, %1 op_sel:[1,0] neg_lo:[0,1] neg_hi:[0,1]")              // (b.y, b.y) - a
-#undef GMUPT_PK2
 __device__ __forceinline__ float v_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float v_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float v_min3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
@@ -182,6 +132,8 @@ __device__ __forceinline__ void ray_set(RayPk& r, f3 o, f3 d)
 
 #define GMUPT_LO(Q) __builtin_shufflevector(Q, Q, 0, 1)
 #define GMUPT_HI(Q) __builtin_shufflevector(Q, Q, 2, 3)
+// the min / max tree of ray_box (extensionRayCast.hlsl:79-94) on one slot; "hit" is `result > 0`, i.e. t1 >= t0 and (t0 > 0 ? t0 : t1) > 0,
+// which is t1 >= t0 && t1 > 0 (t1 >= t0 > 0 implies t1 > 0; a NaN fails both forms)
 __device__ __forceinline__ bool slab_hit_pk(float nx, float ny, float nz, float fx, float fy, float fz)
 {
     const float t1 = v_min3(v_max(fx, nx), v_max(fy, ny), v_max(fz, nz));
@@ -201,9 +153,8 @@ __device__ __forceinline__ bool slab_hit_ordered(float nx, float ny, float nz, f
 __device__ __forceinline__ void slab_hits4(const vec4f q0, const vec4f q1, const vec4f q2, const vec4f q3, const vec4f q4, const vec4f q5, const RayPk& ray,
                                            bool& h0, bool& h1, bool& h2, bool& h3, const bool general = true)
 {
-#if GMUPT_WIDE_PK && GMUPT_WIDE_QUADPK
-    // one plane row (four slots) per statement: two subtractions, two multiplications -- a product is read two instructions after its
-    // difference was written, so one wait state at the end covers the statement (4 instead of 1 packed operations per `s_nop`)
+    // (plane - o) * (1 / d), one plane row (four slots) per statement: two subtractions, two multiplications -- a product is read two
+    // instructions after its difference was written, so one wait state at the end covers the statement
     vec2f nxa, nxb, nya, nyb, nza, nzb, fxa, fxb, fya, fyb, fza, fzb;
 #define GMUPT_ROW(A, B, Q, O, OSEL, INV, ISEL) \
     asm("v_pk_add_f32 %0, %2, %4 " OSEL " neg_lo:[0,1] neg_hi:[0,1]\n\tv_pk_add_f32 %1, %3, %4 " OSEL " neg_lo:[0,1] neg_hi:[0,1]\n\t" \
@@ -216,15 +167,6 @@ __device__ __forceinline__ void slab_hits4(const vec4f q0, const vec4f q1, const
     GMUPT_ROW(fya, fyb, q4, ray.oxy, "op_sel:[0,1]", ray.ixy, "op_sel:[0,1]");
     GMUPT_ROW(fza, fzb, q5, ray.ozi, "op_sel_hi:[1,0]", ray.ozi, "op_sel:[0,1]");
 #undef GMUPT_ROW
-#elif GMUPT_WIDE_PK
-    const vec2f nxa = pk_mul_lo(pk_sub_lo(GMUPT_LO(q0), ray.oxy), ray.ixy), nxb = pk_mul_lo(pk_sub_lo(GMUPT_HI(q0), ray.oxy), ray.ixy);
-    const vec2f nya = pk_mul_hi(pk_sub_hi(GMUPT_LO(q1), ray.oxy), ray.ixy), nyb = pk_mul_hi(pk_sub_hi(GMUPT_HI(q1), ray.oxy), ray.ixy);
-    const vec2f nza = pk_mul_hi(pk_sub_lo(GMUPT_LO(q2), ray.ozi), ray.ozi), nzb = pk_mul_hi(pk_sub_lo(GMUPT_HI(q2), ray.ozi), ray.ozi);
-    const vec2f fxa = pk_mul_lo(pk_sub_lo(GMUPT_LO(q3), ray.oxy), ray.ixy), fxb = pk_mul_lo(pk_sub_lo(GMUPT_HI(q3), ray.oxy), ray.ixy);
-    const vec2f fya = pk_mul_hi(pk_sub_hi(GMUPT_LO(q4), ray.oxy), ray.ixy), fyb = pk_mul_hi(pk_sub_hi(GMUPT_HI(q4), ray.oxy), ray.ixy);
-    const vec2f fza = pk_mul_hi(pk_sub_lo(GMUPT_LO(q5), ray.ozi), ray.ozi), fzb = pk_mul_hi(pk_sub_lo(GMUPT_HI(q5), ray.ozi), ray.ozi);
-#endif
-#if GMUPT_WIDE_PK
     if (general) {
         h0 = slab_hit_pk(nxa.x, nya.x, nza.x, fxa.x, fya.x, fza.x); h1 = slab_hit_pk(nxa.y, nya.y, nza.y, fxa.y, fya.y, fza.y);
         h2 = slab_hit_pk(nxb.x, nyb.x, nzb.x, fxb.x, fyb.x, fzb.x); h3 = slab_hit_pk(nxb.y, nyb.y, nzb.y, fxb.y, fyb.y, fzb.y);
@@ -232,11 +174,6 @@ __device__ __forceinline__ void slab_hits4(const vec4f q0, const vec4f q1, const
         h0 = slab_hit_ordered(nxa.x, nya.x, nza.x, fxa.x, fya.x, fza.x); h1 = slab_hit_ordered(nxa.y, nya.y, nza.y, fxa.y, fya.y, fza.y);
         h2 = slab_hit_ordered(nxb.x, nyb.x, nzb.x, fxb.x, fyb.x, fzb.x); h3 = slab_hit_ordered(nxb.y, nyb.y, nzb.y, fxb.y, fyb.y, fzb.y);
     }
-#else
-    const f3 o = ray_o(ray), invdir = ray_inv(ray);
-    h0 = slab_hit(q0.x, q1.x, q2.x, q3.x, q4.x, q5.x, o, invdir); h1 = slab_hit(q0.y, q1.y, q2.y, q3.y, q4.y, q5.y, o, invdir);
-    h2 = slab_hit(q0.z, q1.z, q2.z, q3.z, q4.z, q5.z, o, invdir); h3 = slab_hit(q0.w, q1.w, q2.w, q3.w, q4.w, q5.w, o, invdir);
-#endif
 }
 
 // Moeller-Trumbore (extensionRayCast.hlsl:38-62 == shadowRayCast.hlsl:16-40) on the TWO triangles of a TriPair at once: every operation of
@@ -248,9 +185,8 @@ __device__ __forceinline__ PairHit tri_pair_compute(const vec4f a0, const vec4f 
     const vec2f v0x = GMUPT_LO(a0), v0y = GMUPT_HI(a0), v0z = GMUPT_LO(a1), e1x = GMUPT_HI(a1), e1y = GMUPT_LO(a2), e1z = GMUPT_HI(a2);
     const vec2f e2x = GMUPT_LO(a3), e2y = GMUPT_HI(a3), e2z = GMUPT_LO(a4);
     PairHit h;
-#if GMUPT_WIDE_PK && GMUPT_WIDE_QUADPK && GMUPT_WIDE_QUADTRI
-    // the same operations as the branch below, in four statements of independent instructions (one wait state per statement instead of
-    // one per packed instruction: no result is read by the instruction that follows the one that wrote it)
+    // the operations of tri_compute_flat (pt_traverse_common.hpp), in its order, in four statements of independent instructions (one
+    // wait state per statement: no result is read by the instruction that follows the one that wrote it)
     vec2f px, py, pz, tx, ty, tz, m1, m2, m3;
     asm("v_pk_mul_f32 %0, %11, %15 op_sel:[0,1]\n\t"                                    // pvec = cross3(d, e2): e2z d.y
         "v_pk_mul_f32 %6, %10, %16 op_sel_hi:[1,0]\n\t"                                 //   e2y d.z
@@ -288,28 +224,6 @@ __device__ __forceinline__ PairHit tri_pair_compute(const vec4f a0, const vec4f 
         : "+v"(uu), "=&v"(vv), "=&v"(tt), "=&v"(c1), "=&v"(c2), "=&v"(c3), "=&v"(c4)
         : "v"(qx), "v"(qy), "v"(qz), "v"(ray.dxy), "v"(ray.dzz), "v"(e2x), "v"(e2y), "v"(e2z), "v"(invDet));
     h.u = uu; h.v = vv; h.t = tt;
-#elif GMUPT_WIDE_PK
-    // pvec = cross3(d, e2) = (d.y e2.z - d.z e2.y, d.z e2.x - d.x e2.z, d.x e2.y - d.y e2.x)
-    const vec2f px = pk_sub(pk_mul_hi(e2z, ray.dxy), pk_mul_lo(e2y, ray.dzz)), py = pk_sub(pk_mul_lo(e2x, ray.dzz), pk_mul_lo(e2z, ray.dxy)), pz = pk_sub(pk_mul_lo(e2y, ray.dxy), pk_mul_hi(e2x, ray.dxy));
-    const vec2f det = pk_add(pk_add(pk_mul(e1x, px), pk_mul(e1y, py)), pk_mul(e1z, pz));                     // dot3(e1, pvec)
-    vec2f invDet; invDet.x = 1.0f / det.x; invDet.y = 1.0f / det.y;
-    const vec2f tx = pk_lo_sub(v0x, ray.oxy), ty = pk_hi_sub(v0y, ray.oxy), tz = pk_lo_sub(v0z, ray.ozi);   // tvec = o - v0
-    h.u = pk_mul(pk_add(pk_add(pk_mul(tx, px), pk_mul(ty, py)), pk_mul(tz, pz)), invDet);                     // dot3(tvec, pvec) * invDet
-    const vec2f qx = pk_sub(pk_mul(ty, e1z), pk_mul(tz, e1y)), qy = pk_sub(pk_mul(tz, e1x), pk_mul(tx, e1z)), qz = pk_sub(pk_mul(tx, e1y), pk_mul(ty, e1x));   // qvec = cross3(tvec, e1)
-    h.v = pk_mul(pk_add(pk_add(pk_mul_lo(qx, ray.dxy), pk_mul_hi(qy, ray.dxy)), pk_mul_lo(qz, ray.dzz)), invDet);   // dot3(d, qvec) * invDet
-    h.t = pk_mul(pk_add(pk_add(pk_mul(e2x, qx), pk_mul(e2y, qy)), pk_mul(e2z, qz)), invDet);                  // dot3(e2, qvec) * invDet
-#else
-    const f3 o = ray_o(ray), d = ray_d(ray);
-    const vec2f dx = { d.x, d.x }, dy = { d.y, d.y }, dz = { d.z, d.z }, ox = { o.x, o.x }, oy = { o.y, o.y }, oz = { o.z, o.z };
-    const vec2f px = dy * e2z - dz * e2y, py = dz * e2x - dx * e2z, pz = dx * e2y - dy * e2x;
-    const vec2f det = (e1x * px + e1y * py) + e1z * pz;
-    vec2f invDet; invDet.x = 1.0f / det.x; invDet.y = 1.0f / det.y;
-    const vec2f tx = ox - v0x, ty = oy - v0y, tz = oz - v0z;
-    h.u = ((tx * px + ty * py) + tz * pz) * invDet;
-    const vec2f qx = ty * e1z - tz * e1y, qy = tz * e1x - tx * e1z, qz = tx * e1y - ty * e1x;
-    h.v = ((dx * qx + dy * qy) + dz * qz) * invDet;
-    h.t = ((e2x * qx + e2y * qy) + e2z * qz) * invDet;
-#endif
     h.okA = !((det.x > -kEpsilon && det.x < kEpsilon) | (h.u.x < 0.0f) | (h.u.x > 1.0f) | (h.v.x < 0.0f) | (h.u.x + h.v.x > 1.0f));
     h.okB = !((det.y > -kEpsilon && det.y < kEpsilon) | (h.u.y < 0.0f) | (h.u.y > 1.0f) | (h.v.y < 0.0f) | (h.u.y + h.v.y > 1.0f));
     h.last = __builtin_bit_cast(vec4u, a4).z != 0u;   // (whole-vector bit cast: __builtin_bit_cast of a vector ELEMENT reads element 0 with this compiler)
@@ -578,31 +492,6 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
             }
         }
         if (nIdle == 64 || (nIdle >= (int)p.tuneRefill && phase < 2)) { // wave-uniform
-#ifndef GMUPT_WIDE_XCD_EXPERIMENT
-#define GMUPT_WIDE_XCD_EXPERIMENT 0   // 1 (tools/xcd_experiment.py only): queues pre-binned into eight equal segments, one per XCD (does an L2 per subtree pay?)
-#endif
-#if GMUPT_WIDE_XCD_EXPERIMENT
-            while (p.xcdBins && next >= end && phase < 2) {
-                const uint32_t count = phase == 0 ? countExt : countSh, segLen = count >> 3;
-                const uint32_t xcc = (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;     // HW_REG_XCC_ID: the XCD this workgroup runs on
-                bool got = false;
-                for (uint32_t t = 0; t < 8u && !got; t++) {
-                    const uint32_t sgm = (xcc + t) & 7u;
-                    uint32_t base = 0;
-                    if (lane == 0u) base = atomicAdd(&p.travCounters[4u + 8u * (uint32_t)phase + sgm], p.raysPerWave);
-                    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                    if (base < segLen) {
-                        got = true;
-                        const uint32_t gb = sgm * segLen + base, ge = (base + p.raysPerWave < segLen ? gb + p.raysPerWave : (sgm + 1u) * segLen);
-                        next = gb; end = ge; chunkBase = gb;
-                        const uint32_t* q = phase == 0 ? qExt : qSh;
-                        qe0 = (gb + lane < ge) ? IO::entry(q, gb + lane) : kQueueHole;
-                        qe1 = (gb + 64u + lane < ge) ? IO::entry(q, gb + 64u + lane) : kQueueHole;
-                    }
-                }
-                if (!got) { phase++; next = end = 0; }
-            }
-#endif
             while (next >= end && phase < 2) { // next chunk of the current queue, or the first one of the next queue
                 uint32_t base = 0;
                 const uint32_t count = phase == 0 ? countExt : countSh;
@@ -629,7 +518,7 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
                 // the next ray first: its loads are in flight while the finished ray is written back
                 const bool take = my < end;
                 const uint32_t newIndex = take ? (entry < 64u ? entryLo : entryHi) : kQueueHole;   // extensionRayCast.hlsl:210 / shadowRayCast.hlsl:159
-                const bool newRay = take && ((phase != 0 && !GMUPT_WIDE_XCD_EXPERIMENT) || newIndex != kQueueHole); // holes only exist in the extension queue (and in the experiment's padded bins)
+                const bool newRay = take && (phase != 0 || newIndex != kQueueHole); // holes only exist in the extension queue
                 f3 newO = mk3(0, 0, 0), newD = mk3(0, 0, 1); float newDist = kFltMax;
                 if (newRay) {
                     if (phase == 0) { newO = IO::ray3(p, F_RAY_OX, newIndex); newD = IO::ray3(p, F_RAY_DX, newIndex); newDist = IO::closest_limit(p, newIndex); }  // :213-214
@@ -666,17 +555,10 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
             census2 += __popcll(__ballot(cur >= 0 && !roomNow)); census3 += __popcll(__ballot(cur == kDone && pendingNow));
         }
         // (wave-uniform, once per iteration: rays only change in the refill above) the ordered slab tree needs every walking ray's 1 / d finite
-        const bool generalSlabs = !GMUPT_WIDE_SIGNED || __ballot(cur >= 0 && (ray_sg(ray) >> 24) != 0u) != 0ull;
+        const bool generalSlabs = __ballot(cur >= 0 && (ray_sg(ray) >> 24) != 0u) != 0ull;
         if (STATS && lane == 0u) { itersAll++; if (generalSlabs) itersGeneral++; }
 #pragma unroll
         for (int rep = 0; rep < REPS; rep++) {
-#if GMUPT_WIDE_SIGNED
-#define GMUPT_WIDE_LOAD_LDS() load_wnode_lds_signed(s_top, pla, q0, q1, q2, q3, q4, q5, lk)
-#define GMUPT_WIDE_LOAD_GLB() load_wnode_glb_signed(rNodes, pla, q0, q1, q2, q3, q4, q5, lk)
-#else
-#define GMUPT_WIDE_LOAD_LDS() load_wnode_lds(s_top, cur, q0, q1, q2, q3, q4, q5, lk)
-#define GMUPT_WIDE_LOAD_GLB() load_wnode_glb(rNodes, cur, q0, q1, q2, q3, q4, q5, lk)
-#endif
             // the four slab tests of the node in q0 .. lk, then: the first hit inner slot is the next node, the other hits are pushed (inner nodes from the
             // bottom, leaves from the top) -- ranks by prefix counts, one predicated LDS store per slot and stack (nested regions per slot: the same time)
 #define GMUPT_WIDE_NODE_COMPUTE(INTOP) \
@@ -704,10 +586,10 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
             // fetch phase
             const bool doNode = cur >= 0 && pb >= pa && pb - pa >= (uint32_t)(kWideRoom - 1);
             const bool inTop = (uint32_t)cur < topCount;
-            const PlaneAddr pla = plane_addresses(cur, ray_sg(ray)); (void)pla;    // (for every lane: the node-less ones load nothing)
-            if (doNode && inTop) GMUPT_WIDE_LOAD_LDS();
+            const PlaneAddr pla = plane_addresses(cur, ray_sg(ray));    // (for every lane: the node-less ones load nothing)
+            if (doNode && inTop) load_wnode_lds_signed(s_top, pla, q0, q1, q2, q3, q4, q5, lk);
             asm volatile("" ::: "memory");   // LDS lanes first, see load_node
-            if (doNode && !inTop) GMUPT_WIDE_LOAD_GLB();
+            if (doNode && !inTop) load_wnode_glb_signed(rNodes, pla, q0, q1, q2, q3, q4, q5, lk);
             if (burst && ti < 0 && pb != (uint32_t)(S - 1)) { pb++; ti = ~sl[pb * kDefBlock]; }
             const bool doTri = burst && ti >= 0;
             vec4f a0, a1, a2, a3, a4;                        // defined for the doTri lanes only: the TriPair of this step
@@ -748,8 +630,6 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
 #undef GMUPT_WIDE_MERGE_OWN
 #undef GMUPT_WIDE_FINISH
 #undef GMUPT_WIDE_NODE_COMPUTE
-#undef GMUPT_WIDE_LOAD_LDS
-#undef GMUPT_WIDE_LOAD_GLB
     if (STATS) { flush_counts(p.stats, tcE, raysE, true); flush_wave_iters(p.stats, wInE, wTrE, true);
                  flush_counts(p.stats, tcS, raysS, false); flush_wave_iters(p.stats, wInS, wTrS, false);
                  flush_sum(&p.stats->extTopInner, topE); flush_sum(&p.stats->shTopInner, topS); flush_sum(&p.stats->castHelperSubtrees, helped);
@@ -771,17 +651,26 @@ uint32_t traversal_wide_top_capacity() { return (uint32_t)kWideTop; }
 uint32_t traversal_wide_stack_entries() { return (uint32_t)kWideStack; }
 uint32_t traversal_wide_overflow_entries() { return (uint32_t)kWideOvf; }
 
+// Steps per iteration of a wave (between two looks at the queues): six while the records fit the 256 MB Infinity Cache, eight beyond
+// (measured: config 3 0.923 / 0.930 ms with six / eight, config 5 5.12 / 5.00 ms); GMUPT_WIDE_STEPS overrides.  With eight steps the last
+// half round of shadow-ray chunks is handed out in quarters (measured with it: config 5 4.87-4.95 vs 4.95-4.99 ms, config 3 0.926-0.928
+// vs 0.920-0.923).  Sets q.wideQuarterTail; returns whether the eight-step kernel is the one to launch.
+static bool wide_eight_steps(RenderParams& q)
+{
+    const uint64_t recordBytes = (uint64_t)q.trav.wideCount * 128ull + (uint64_t)q.trav.numPairs * 80ull;
+    const bool eight = q.tuneWideSteps ? q.tuneWideSteps >= 8u : recordBytes > (256ull << 20);
+    q.wideQuarterTail = eight ? 1u : 0u;
+    return eight;
+}
+
 // Both ray casts in one wide launch.  Returns 0 when this configuration is not taken (the caller runs another kernel).
 uint32_t launch_cast_wide(const RenderParams& p, bool stats, hipStream_t s)
 {
     if (!p.trav.wnodes || p.extendPrune || p.shadowPrune) return 0u;
     if (!wide_tables_addressable(p.trav.wideCount, p.scene.numTris, p.trav.numPairs)) return 0u;
     const uint32_t pb = p.travGridBlocks;
-    // steps per iteration of a wave (between two looks at the queues): six while the records fit the 256 MB Infinity Cache, eight beyond
-    // (measured: config 3 0.923 / 0.930 ms with six / eight, config 5 5.12 / 5.00 ms); GMUPT_WIDE_STEPS overrides
-    const uint64_t recordBytes = (uint64_t)p.trav.wideCount * 128ull + (uint64_t)p.trav.numPairs * 80ull;
-    const bool eight = p.tuneWideSteps ? p.tuneWideSteps >= 8u : recordBytes > (256ull << 20);
-    RenderParams q = p; q.wideQuarterTail = eight ? 1u : 0u;   // (measured with it: config 5 4.87-4.95 vs 4.95-4.99 ms, config 3 0.926-0.928 vs 0.920-0.923)
+    RenderParams q = p;
+    const bool eight = wide_eight_steps(q);
     if (stats) { if (eight) hipLaunchKernelGGL((k_cast_w<true, GMUPT_WIDE_REPS + 2, StateIO>), dim3(pb), dim3(kDefBlock), 0, s, q); else hipLaunchKernelGGL((k_cast_w<true, GMUPT_WIDE_REPS, StateIO>), dim3(pb), dim3(kDefBlock), 0, s, q); }
     else { if (eight) hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS + 2, StateIO>), dim3(pb), dim3(kDefBlock), 0, s, q); else hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS, StateIO>), dim3(pb), dim3(kDefBlock), 0, s, q); }
     return GMUPT_STAT_FUSED_CAST | GMUPT_STAT_CAST_WIDE;
@@ -789,7 +678,7 @@ uint32_t launch_cast_wide(const RenderParams& p, bool stats, hipStream_t s)
 
 // gmupt_trace_rays: the same walk over caller rays (QueryIO).  p is the renderer's parameter block with p.stats and p.travCounters
 // already pointing at the query's own zeroed buffers (gmupt_capi.hip checks that the scene has a wide collapse within the 2 GiB limits).
-// The rest of the launch is launch_cast_wide's: grid, overflow stacks, steps per iteration, tail rule.
+// The rest of the launch is launch_cast_wide's: grid, overflow stacks, steps per iteration and tail rule (wide_eight_steps).
 void launch_trace_wide(const RenderParams& p, const gmupt_ray* closest, uint32_t nClosest, gmupt_hit* hits, const gmupt_ray* any, uint32_t nAny,
                        uint32_t* occluded, uint32_t lightCount, hipStream_t s)
 {
@@ -797,10 +686,7 @@ void launch_trace_wide(const RenderParams& p, const gmupt_ray* closest, uint32_t
     static_cast<RenderParams&>(q) = p;
     q.rays[0] = closest; q.rays[1] = any; q.count[0] = nClosest; q.count[1] = nAny;
     q.hits = hits; q.occluded = occluded; q.lightCount = lightCount;
-    const uint64_t recordBytes = (uint64_t)p.trav.wideCount * 128ull + (uint64_t)p.trav.numPairs * 80ull;
-    const bool eight = p.tuneWideSteps ? p.tuneWideSteps >= 8u : recordBytes > (256ull << 20);
-    q.wideQuarterTail = eight ? 1u : 0u;
-    if (eight) hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS + 2, QueryIO>), dim3(p.travGridBlocks), dim3(kDefBlock), 0, s, q);
+    if (wide_eight_steps(q)) hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS + 2, QueryIO>), dim3(p.travGridBlocks), dim3(kDefBlock), 0, s, q);
     else hipLaunchKernelGGL((k_cast_w<false, GMUPT_WIDE_REPS, QueryIO>), dim3(p.travGridBlocks), dim3(kDefBlock), 0, s, q);
 }
 

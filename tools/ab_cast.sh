@@ -1,18 +1,15 @@
 #!/bin/bash
 # A/B of ray-cast kernels on one box: runs bench.py --full (steady state, stage times, roofline) once per GMUPT_TRAVERSAL value given,
 # writes $AB_OUT/ab_<mode>.json (default: ab_out/)
-# usage: tools/ab_cast.sh cast0 wide wide@wpk0 [-- extra bench args]
+# usage: tools/ab_cast.sh cast0 wide [-- extra bench args]
 set -e
 OUT=${AB_OUT:-ab_out}
 mkdir -p "$OUT"
 modes=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do modes+=("$1"); shift; done
 [ "$1" == "--" ] && shift
-for spec in "${modes[@]}"; do
-  m=${spec%@*}; b=""; [ "$spec" != "$m" ] && b=${spec#*@}     # mode[@experiment-build]: libgmupt_<build>.so (gmu-path-tracer_amd/build.py EXPERIMENT_BUILDS)
-  lib=""; [ -n "$b" ] && lib=$PWD/gmu-path-tracer_amd/libgmupt_$b.so
-  m2=$m; m=$(echo $spec | tr '@' '_')
-  GMUPT_LIB=$lib GMUPT_TRAVERSAL=$m2 python bench.py --full --no-cpu-baseline --no-full-frame --no-config5 "$@" > "$OUT/ab_$m.json" 2> "$OUT/ab_$m.err" || { echo "bench failed for $m"; tail -5 "$OUT/ab_$m.err"; exit 1; }
+for m in "${modes[@]}"; do
+  GMUPT_TRAVERSAL=$m python bench.py --full --no-cpu-baseline --no-full-frame --no-config5 "$@" > "$OUT/ab_$m.json" 2> "$OUT/ab_$m.err" || { echo "bench failed for $m"; tail -5 "$OUT/ab_$m.err"; exit 1; }
   python - "$m" "$OUT" <<'PY'
 import json, sys
 m, out = sys.argv[1], sys.argv[2]
