@@ -3,7 +3,9 @@
 // One wavefront iteration = the six dispatches of the reference's Renderer::draw()
 // (Source/Renderer.cpp:195-211), regrouped for CDNA4:
 //
-//   k_logic      logic.hlsl:200-302 per slot: terminate / accumulate decision, material fetch, NEE set-up.
+//   k_logic      logic.hlsl:200-302 per slot: terminate / accumulate decision, material fetch, NEE set-up -- and, for the slots that
+//                will push a shadow ray, the direct light of materialUE4.hlsl:184-188 (its operands are all here; k_material is the
+//                kernel short of vector issue slots, this one waits for memory).
 //                Writes a 1-byte class per slot and per-block class counts instead of pushing to queues
 //                with per-warp atomics (the reference's NvBallot + InterlockedAdd idiom, logic.hlsl:36-44,
 //                263-285): queue positions are then RANKS, independent of scheduling order.
@@ -61,129 +63,7 @@ __device__ __forceinline__ float powerHeuristic(float rayPdf, float lightPdf) //
     return t / (lightPdf * lightPdf + t);
 }
 
-// ------------------------------------------------------------------------------------------------ block class counts
-// every thread of the block calls this once; writes blockCounts[k * nBlocks + blockIdx.x] for k = 0..3
-// (k = 3: UE4 slots whose light lies in the upper hemisphere, i.e. the entries of the shadow queue)
-__device__ __forceinline__ void publish_block_counts(const RenderParams& p, int c)
-{
-    __shared__ uint32_t s_cnt[kNumCounts][kBlock / 64];
-    const uint32_t wave = threadIdx.x >> 6;
-    unsigned long long b0 = __ballot((c & CLS_MASK) == CLS_UE4), b1 = __ballot(c == CLS_GLASS), b2 = __ballot(c == CLS_ENDED), b3 = __ballot(c == (CLS_UE4 | CLS_SHADOW_BIT));
-    if ((threadIdx.x & 63) == 0) { s_cnt[0][wave] = __popcll(b0); s_cnt[1][wave] = __popcll(b1); s_cnt[2][wave] = __popcll(b2); s_cnt[3][wave] = __popcll(b3); }
-    __syncthreads();
-    if (threadIdx.x < kNumCounts) {
-        uint32_t s = 0;
-        for (int w = 0; w < kBlock / 64; w++) s += s_cnt[threadIdx.x][w];
-        p.blockCounts[threadIdx.x * p.nBlocks + blockIdx.x] = s;
-        // second level: totals per group of kScanGroup blocks (integer sums: the order of the atomics does not matter)
-        if (s) atomicAdd(&p.groupTotals[((size_t)p.groupParity * kNumCounts + threadIdx.x) * p.nGroups + blockIdx.x / kScanGroup], s);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ k_clear (logic.hlsl:165-190)
-__global__ __launch_bounds__(kBlock) void k_clear(RenderParams p)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    // zero the sample count of every pixel, keep the colour (logic.hlsl:180-181)
-    uint32_t w = p.tileEnabled ? p.fbW : cam_width(p.cam), h = p.tileEnabled ? p.fbH : cam_height(p.cam);
-    uint32_t npix = w * h; if (npix > p.fbW * p.fbH) npix = p.fbW * p.fbH;
-    for (uint32_t k = i; k < npix; k += gridDim.x * kBlock) { p.fb[k].w = __builtin_bit_cast(float, 0u); p.listHead[k] = kListEnd; }
-    // newPath[i] = i for the whole pool (logic.hlsl:187-188): every live slot becomes an ended path of rank i
-    int c = CLS_NONE;
-    if (i < p.L) { c = CLS_ENDED; p.cls[i] = CLS_ENDED; }
-    publish_block_counts(p, c);
-}
-
-// ------------------------------------------------------------------------------------------------ k_logic (logic.hlsl:200-302)
-__global__ __launch_bounds__(kBlock) void k_logic(RenderParams p)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    int c = CLS_NONE;
-    if (i < p.L) {
-        c = p.cls[i];
-        if (c != CLS_RETIRED) {
-            Rng g; g.seed(i, p.cam.randomSeed[0], p.cam.randomSeed[1]);     // :216
-            bool pathEliminated = false;                                   // :217
-            f3 throughput = ld3(p, F_THR_R, i);                             // :219
-            f3 radiance = ld3(p, F_RAD_R, i);                               // :220
-            const uint32_t isEmitter = ldu(p, F_IS_EMITTER, i);
-            uint32_t pl = 0;
-            if (isEmitter > 0) {                                            // :222-226, sampleLight :192-197
-                const f3 e = sample_light_color(p.scene.lights, isEmitter);
-                radiance = radiance + e * throughput;
-                pathEliminated = true;
-            } else {
-                if (!ldu(p, F_IN_SHADOW, i)) radiance = radiance + ld3(p, F_DL_R, i) * throughput; // :230-231
-                throughput = throughput * ld3(p, F_LTHR_R, i);              // :234
-                if (throughput.x <= 0.0f && throughput.y <= 0.0f && throughput.z <= 0.0f) pathEliminated = true; // :237
-                if (ldf(p, F_HIT_DIST, i) == kFltMax) {                     // :241-245
-                    radiance = radiance + throughput * mk3(p.cam.envColor[0], p.cam.envColor[1], p.cam.envColor[2]);
-                    pathEliminated = true;
-                }
-                pl = ldu(p, F_PATH_LEN, i);
-                if (pl > 200) {                                             // :248-255
-                    float pr = hmax(throughput.x, hmax(throughput.y, throughput.z));
-                    if (g.next() > pr * 0.004f) pathEliminated = true;
-                    throughput = throughput * (1.0f / pr);
-                }
-                if (p.maxDepth && pl >= p.maxDepth) pathEliminated = true;  // extension
-            }
-
-            if (pathEliminated) {
-                // endPath :49-53: per-sample tonemap; the running-mean update is applied in canonical order by k_material
-                c = CLS_ENDED;
-                f3 r = mk3(hsaturate(radiance.x), hsaturate(radiance.y), hsaturate(radiance.z));
-                r = r / (r + mk3(1.0f, 1.0f, 1.0f));
-                const float gm = 1.0f / 2.2f;
-                r = mk3(dpow(r.x, gm), dpow(r.y, gm), dpow(r.z, gm));
-                p.sample[i] = r.x; p.sample[(size_t)p.P + i] = r.y; p.sample[(size_t)2 * p.P + i] = r.z;
-                const uint32_t pix = pixel_index(p, ldu(p, F_SCR_X, i), ldu(p, F_SCR_Y, i));
-                uint32_t prev = kListEnd;
-                if (pix != kListEnd) prev = atomicExch(&p.listHead[pix], i);
-                p.listNext[i] = prev;
-            } else {
-                // setMaterialHitProperties :79-133
-                const HitProps hp = material_hit_properties(p.scene, ldu(p, F_TRI_0, i), ldu(p, F_TRI_1, i), ldu(p, F_TRI_2, i), ldu(p, F_TRI_MAT, i),
-                                                            ld3(p, F_BARY_X, i), [&]() { return ld3(p, F_RAY_DX, i); });
-                const f3 normal = hp.normal;
-                st3(p, F_MAT_R, i, hp.color);                               // :128
-                stf(p, F_MAT_METALLIC, i, hp.metallic); stf(p, F_MAT_ROUGHNESS, i, hp.roughness); // :129
-                st3(p, F_NRM_X, i, normal);                                 // :130
-                c = (hp.materialType == GMUPT_MATERIAL_UE4) ? CLS_UE4 : CLS_GLASS; // :262-285 (types other than 0/1 are not produced by Scene)
-
-                // createShadowRay :135-163
-                uint32_t lightIndex = (uint32_t)(g.next() * (float)p.cam.lightCount);
-                float z = 1.0f - 2.0f * g.next();
-                float rr = dsqrt(hmax(0.0f, 1.0f - z * z));
-                float phi = 2.0f * kPi * g.next();
-                float x = rr * dcos(phi);
-                float y = rr * dsin(phi);
-                const gmupt_light L = p.scene.lights[lightIndex < GMUPT_MAX_LIGHTS ? lightIndex : GMUPT_MAX_LIGHTS - 1];
-                f3 lightPosition = mk3(L.position[0], L.position[1], L.position[2]) + mk3(x, y, z) * L.radius;
-                f3 surfacePos = ld3(p, F_SP_X, i) + normal * kEpsilonOffset;
-                f3 lightDir = lightPosition - surfacePos;
-                float distance = length3(lightDir);
-                lightDir = normalize3(lightDir);
-                stu(p, F_LIGHT_IDX, i, lightIndex);
-                st3(p, F_SH_OX, i, surfacePos);
-                st3(p, F_SH_DX, i, lightDir);
-                stf(p, F_LIGHT_DIST, i, distance - kEpsilonOffset);
-                // materialUE4.hlsl:167: a UE4 slot pushes a shadow ray iff the light direction lies in the normal's hemisphere;
-                // both operands are final here, so the shadow queue can be ranked by the same scan as the material queues
-                if (c == CLS_UE4 && dot3(lightDir, normal) > 0.0f) c |= CLS_SHADOW_BIT;
-
-                st3(p, F_RAD_R, i, radiance);                               // :295
-                st3(p, F_THR_R, i, throughput);                             // :296
-                stu(p, F_PATH_LEN, i, pl + 1u);                              // :293,297
-                stu(p, F_IN_SHADOW, i, 1u);                                 // :298
-            }
-            p.cls[i] = (uint8_t)c;
-        }
-    }
-    publish_block_counts(p, c);
-}
-
-// ------------------------------------------------------------------------------------------------ material stages
+// ------------------------------------------------------------------------------------------------ materialUE4.hlsl:24-115 (k_logic evaluates the direct light, k_material the sampled lobe)
 struct Ue4State { f3 rayDir; f3 baseColor; float metallic, roughness; f3 normal; };
 
 __device__ __forceinline__ f3 ue4Sample(const Ue4State& st, Rng& g) // materialUE4.hlsl:24-68
@@ -253,7 +133,146 @@ __device__ __forceinline__ f3 ue4Evaluate(const Ue4State& st, f3 direction) // m
                (st.baseColor.z / kPi) * om + (D * F.z * G) / den);           // :114
 }
 
-__device__ __forceinline__ void stage_ue4(const RenderParams& p, uint32_t queueIndex, uint32_t index, uint32_t shadowRank, uint32_t extOffset) // materialUE4.hlsl:118-192
+// ------------------------------------------------------------------------------------------------ block class counts
+// every thread of the block calls this once; writes blockCounts[k * nBlocks + blockIdx.x] for k = 0..3
+// (k = 3: UE4 slots whose light lies in the upper hemisphere, i.e. the entries of the shadow queue)
+__device__ __forceinline__ void publish_block_counts(const RenderParams& p, int c)
+{
+    __shared__ uint32_t s_cnt[kNumCounts][kBlock / 64];
+    const uint32_t wave = threadIdx.x >> 6;
+    unsigned long long b0 = __ballot((c & CLS_MASK) == CLS_UE4), b1 = __ballot(c == CLS_GLASS), b2 = __ballot(c == CLS_ENDED), b3 = __ballot(c == (CLS_UE4 | CLS_SHADOW_BIT));
+    if ((threadIdx.x & 63) == 0) { s_cnt[0][wave] = __popcll(b0); s_cnt[1][wave] = __popcll(b1); s_cnt[2][wave] = __popcll(b2); s_cnt[3][wave] = __popcll(b3); }
+    __syncthreads();
+    if (threadIdx.x < kNumCounts) {
+        uint32_t s = 0;
+        for (int w = 0; w < kBlock / 64; w++) s += s_cnt[threadIdx.x][w];
+        p.blockCounts[threadIdx.x * p.nBlocks + blockIdx.x] = s;
+        // second level: totals per group of kScanGroup blocks (integer sums: the order of the atomics does not matter)
+        if (s) atomicAdd(&p.groupTotals[((size_t)p.groupParity * kNumCounts + threadIdx.x) * p.nGroups + blockIdx.x / kScanGroup], s);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ k_clear (logic.hlsl:165-190)
+__global__ __launch_bounds__(kBlock) void k_clear(RenderParams p)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    // zero the sample count of every pixel, keep the colour (logic.hlsl:180-181)
+    uint32_t w = p.tileEnabled ? p.fbW : cam_width(p.cam), h = p.tileEnabled ? p.fbH : cam_height(p.cam);
+    uint32_t npix = w * h; if (npix > p.fbW * p.fbH) npix = p.fbW * p.fbH;
+    for (uint32_t k = i; k < npix; k += gridDim.x * kBlock) { p.fb[k].w = __builtin_bit_cast(float, 0u); p.listHead[k] = kListEnd; }
+    // newPath[i] = i for the whole pool (logic.hlsl:187-188): every live slot becomes an ended path of rank i
+    int c = CLS_NONE;
+    if (i < p.L) { c = CLS_ENDED; p.cls[i] = CLS_ENDED; }
+    publish_block_counts(p, c);
+}
+
+// ------------------------------------------------------------------------------------------------ k_logic (logic.hlsl:200-302)
+// 8 waves per SIMD asked for: with the direct light in, the allocator would otherwise take 67 VGPRs (7 waves); at 64 it spills nothing,
+// and the kernel streams the path state, so the waves in flight are what its rate hangs on
+__global__ __launch_bounds__(kBlock, 8) void k_logic(RenderParams p)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    int c = CLS_NONE;
+    if (i < p.L) {
+        c = p.cls[i];
+        if (c != CLS_RETIRED) {
+            Rng g; g.seed(i, p.cam.randomSeed[0], p.cam.randomSeed[1]);     // :216
+            bool pathEliminated = false;                                   // :217
+            f3 throughput = ld3(p, F_THR_R, i);                             // :219
+            f3 radiance = ld3(p, F_RAD_R, i);                               // :220
+            const uint32_t isEmitter = ldu(p, F_IS_EMITTER, i);
+            uint32_t pl = 0;
+            if (isEmitter > 0) {                                            // :222-226, sampleLight :192-197
+                const f3 e = sample_light_color(p.scene.lights, isEmitter);
+                radiance = radiance + e * throughput;
+                pathEliminated = true;
+            } else {
+                if (!ldu(p, F_IN_SHADOW, i)) radiance = radiance + ld3(p, F_DL_R, i) * throughput; // :230-231
+                throughput = throughput * ld3(p, F_LTHR_R, i);              // :234
+                if (throughput.x <= 0.0f && throughput.y <= 0.0f && throughput.z <= 0.0f) pathEliminated = true; // :237
+                if (ldf(p, F_HIT_DIST, i) == kFltMax) {                     // :241-245
+                    radiance = radiance + throughput * mk3(p.cam.envColor[0], p.cam.envColor[1], p.cam.envColor[2]);
+                    pathEliminated = true;
+                }
+                pl = ldu(p, F_PATH_LEN, i);
+                if (pl > 200) {                                             // :248-255
+                    float pr = hmax(throughput.x, hmax(throughput.y, throughput.z));
+                    if (g.next() > pr * 0.004f) pathEliminated = true;
+                    throughput = throughput * (1.0f / pr);
+                }
+                if (p.maxDepth && pl >= p.maxDepth) pathEliminated = true;  // extension
+            }
+
+            if (pathEliminated) {
+                // endPath :49-53: per-sample tonemap; the running-mean update is applied in canonical order by k_material
+                c = CLS_ENDED;
+                f3 r = mk3(hsaturate(radiance.x), hsaturate(radiance.y), hsaturate(radiance.z));
+                r = r / (r + mk3(1.0f, 1.0f, 1.0f));
+                const float gm = 1.0f / 2.2f;
+                r = mk3(dpow(r.x, gm), dpow(r.y, gm), dpow(r.z, gm));
+                p.sample[i] = r.x; p.sample[(size_t)p.P + i] = r.y; p.sample[(size_t)2 * p.P + i] = r.z;
+                const uint32_t pix = pixel_index(p, ldu(p, F_SCR_X, i), ldu(p, F_SCR_Y, i));
+                uint32_t prev = kListEnd;
+                if (pix != kListEnd) prev = atomicExch(&p.listHead[pix], i);
+                p.listNext[i] = prev;
+            } else {
+                // setMaterialHitProperties :79-133
+                const f3 rayDir = ld3(p, F_RAY_DX, i);                      // the incoming direction: the normal map and the direct light below share it
+                const HitProps hp = material_hit_properties(p.scene, ldu(p, F_TRI_0, i), ldu(p, F_TRI_1, i), ldu(p, F_TRI_2, i), ldu(p, F_TRI_MAT, i),
+                                                            ld3(p, F_BARY_X, i), [&]() { return rayDir; });
+                const f3 normal = hp.normal;
+                st3(p, F_MAT_R, i, hp.color);                               // :128
+                stf(p, F_MAT_METALLIC, i, hp.metallic); stf(p, F_MAT_ROUGHNESS, i, hp.roughness); // :129
+                st3(p, F_NRM_X, i, normal);                                 // :130
+                c = (hp.materialType == GMUPT_MATERIAL_UE4) ? CLS_UE4 : CLS_GLASS; // :262-285 (types other than 0/1 are not produced by Scene)
+
+                // createShadowRay :135-163
+                uint32_t lightIndex = (uint32_t)(g.next() * (float)p.cam.lightCount);
+                float z = 1.0f - 2.0f * g.next();
+                float rr = dsqrt(hmax(0.0f, 1.0f - z * z));
+                float phi = 2.0f * kPi * g.next();
+                float x = rr * dcos(phi);
+                float y = rr * dsin(phi);
+                const gmupt_light L = p.scene.lights[lightIndex < GMUPT_MAX_LIGHTS ? lightIndex : GMUPT_MAX_LIGHTS - 1];
+                f3 lightPosition = mk3(L.position[0], L.position[1], L.position[2]) + mk3(x, y, z) * L.radius;
+                f3 surfacePos = ld3(p, F_SP_X, i) + normal * kEpsilonOffset;
+                f3 lightDir = lightPosition - surfacePos;
+                float distance = length3(lightDir);
+                lightDir = normalize3(lightDir);
+                stu(p, F_LIGHT_IDX, i, lightIndex);
+                st3(p, F_SH_OX, i, surfacePos);
+                st3(p, F_SH_DX, i, lightDir);
+                const float lightDist = distance - kEpsilonOffset;
+                stf(p, F_LIGHT_DIST, i, lightDist);
+                st3(p, F_RAD_R, i, radiance);                               // :295
+                st3(p, F_THR_R, i, throughput);                             // :296
+                stu(p, F_PATH_LEN, i, pl + 1u);                              // :293,297
+                stu(p, F_IN_SHADOW, i, 1u);                                 // :298
+                // (stored before the direct light, not after it: radiance, throughput and pl need not stay in registers across it)
+                // materialUE4.hlsl:167: a UE4 slot pushes a shadow ray iff the light direction lies in the normal's hemisphere;
+                // both operands are final here, so the shadow queue can be ranked by the same scan as the material queues
+                if (c == CLS_UE4 && dot3(lightDir, normal) > 0.0f) {
+                    c |= CLS_SHADOW_BIT;
+                    // materialUE4.hlsl:184-188: the direct light of that shadow ray.  It needs neither the queue rank nor the rank-seeded RNG, and
+                    // every operand is in registers here: the values just stored to the slot (k_material used to read them back) and the light record.
+                    const Ue4State st = { rayDir, hp.color, hp.metallic, hp.roughness, normal };
+                    const float lightPdf = lightDist * lightDist / (4.0f * kPi * L.radius * L.radius); // :184
+                    const float bsdfPdf = ue4Pdf(st, lightDir);              // :185
+                    const float ph = powerHeuristic(lightPdf, bsdfPdf);
+                    const f3 e = ue4Evaluate(st, lightDir);
+                    const float lc = (float)p.cam.lightCount;
+                    const float fo = lightFalloff(lightDist, L.falloff);
+                    st3(p, F_DL_R, i, mk3(ph * e.x * L.emission[0] * lc * fo, ph * e.y * L.emission[1] * lc * fo, ph * e.z * L.emission[2] * lc * fo)); // :187-188
+                }
+            }
+            p.cls[i] = (uint8_t)c;
+        }
+    }
+    publish_block_counts(p, c);
+}
+
+// ------------------------------------------------------------------------------------------------ material stages
+__device__ __forceinline__ void stage_ue4(const RenderParams& p, uint32_t queueIndex, uint32_t index, bool pushShadow, uint32_t shadowRank, uint32_t extOffset) // materialUE4.hlsl:118-192
 {
     Rng g; g.seed(queueIndex, p.cam.randomSeed[0], p.cam.randomSeed[1]);   // :131
     Ue4State st;
@@ -277,22 +296,9 @@ __device__ __forceinline__ void stage_ue4(const RenderParams& p, uint32_t queueI
     st3(p, F_RAY_DX, index, bsdfDir);                                        // :161
     p.queues[(size_t)Q_EXT_RAY * p.P + extOffset + queueIndex] = index;       // :162 (extOffset = QC[4])
 
-    const f3 lightDir = ld3(p, F_SH_DX, index);                              // :165
-    if (dot3(lightDir, st.normal) > 0.0f) {                                  // :167,178
-        const uint32_t lightIndex = ldu(p, F_LIGHT_IDX, index);
-        const float distance = ldf(p, F_LIGHT_DIST, index);
-        const gmupt_light L = p.scene.lights[lightIndex < GMUPT_MAX_LIGHTS ? lightIndex : GMUPT_MAX_LIGHTS - 1];
-        const float lightPdf = distance * distance / (4.0f * kPi * L.radius * L.radius); // :184
-        const float bsdfPdf = ue4Pdf(st, lightDir);                          // :185
-        const float ph = powerHeuristic(lightPdf, bsdfPdf);
-        const f3 e = ue4Evaluate(st, lightDir);
-        const float lc = (float)p.cam.lightCount;
-        const float fo = lightFalloff(distance, L.falloff);
-        st3(p, F_DL_R, index, mk3(ph * e.x * L.emission[0] * lc * fo, ph * e.y * L.emission[1] * lc * fo, ph * e.z * L.emission[2] * lc * fo)); // :187-188
-        // :168-176,189: shadow queue slot = rank among the UE4 slots that push one (canonical order, no atomics)
-        const uint32_t pos = shadowRank;
-        p.queues[(size_t)Q_SHADOW_RAY * p.P + pos] = index;                  // :189
-    }
+    // :167,178: k_logic decided dot3(lightDir, normal) > 0 (the item's shadow flag) and stored the direct light (:184-188) with it
+    // :168-176,189: shadow queue slot = rank among the UE4 slots that push one (canonical order, no atomics)
+    if (pushShadow) p.queues[(size_t)Q_SHADOW_RAY * p.P + shadowRank] = index; // :189
 }
 
 __device__ __forceinline__ void stage_glass(const RenderParams& p, uint32_t queueIndex, uint32_t index, uint32_t extOffset) // materialGlass.hlsl:23-85
@@ -483,7 +489,7 @@ __global__ __launch_bounds__(kBlock) void k_material(RenderParams p, int clearFr
     if (cj == CLS_ENDED) stage_new_path(p, rank, slot, clearFrame);
     else {
         p.queues[(size_t)(cj == CLS_UE4 ? Q_MAT_UE4 : Q_MAT_GLASS) * p.P + rank] = slot; // logic.hlsl:282-285
-        if (cj == CLS_UE4) stage_ue4(p, rank, slot, (item & 0x8000u) ? s_pre[3] + s_srank[threadIdx.x] : 0u, extUE4Offset);
+        if (cj == CLS_UE4) stage_ue4(p, rank, slot, (item & 0x8000u) != 0u, s_pre[3] + s_srank[threadIdx.x], extUE4Offset);
         else stage_glass(p, rank, slot, extGlassOffset);
     }
 }
