@@ -163,6 +163,14 @@ class LbvhInfo(C.Structure):
 assert C.sizeof(LbvhInfo) == 48
 
 
+class NormalsInfo(C.Structure):
+    """gmupt_normals_info: 24 bytes."""
+    _fields_ = [("num_verts", C.c_uint32), ("num_tris", C.c_uint32), ("max_valence", C.c_uint32), ("pad", C.c_uint32), ("ms", C.c_double)]
+
+
+assert C.sizeof(NormalsInfo) == 24
+
+
 class GmuptError(RuntimeError):
     def __init__(self, msg, code=0):
         super().__init__(msg)
@@ -233,6 +241,11 @@ SYMBOLS = {
     "gmupt_lbvh_create": (C.c_int, [_P, C.POINTER(_P)]),
     "gmupt_lbvh_destroy": (None, [_P]),
     "gmupt_lbvh_build": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.POINTER(LbvhParams), C.POINTER(_P), C.POINTER(_P), _P, C.POINTER(LbvhInfo)]),
+    "gmupt_vertex_normals_host": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
+    "gmupt_normals_create": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)]),
+    "gmupt_normals_update": (C.c_int, [_P, C.POINTER(NormalsInfo)]),
+    "gmupt_normals_destroy": (None, [_P]),
+    "gmupt_buffer_update_device": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -365,6 +378,19 @@ class Buffer:
     def update(self, array):
         array = np.ascontiguousarray(array)
         _check(lib().gmupt_buffer_update(self.h, _ptr(array), array.nbytes))
+
+    def update_from_device(self, tensor):
+        """gmupt_buffer_update_device: the buffer's first bytes from a torch tensor on this buffer's GPU (e.g. a pose computed there),
+        without a trip through the host.  torch's current stream is synchronised first."""
+        import torch
+        device = torch.device("cuda", getattr(self.dev, "index", 0))
+        if not isinstance(tensor, torch.Tensor) or tensor.device != device or not tensor.is_contiguous():
+            raise GmuptError("update_from_device: a contiguous tensor on %s" % device, ERR_INVALID_ARGUMENT)
+        nbytes = tensor.numel() * tensor.element_size()
+        if nbytes > int(lib().gmupt_buffer_size(self.h)):
+            raise GmuptError("update_from_device: %d bytes into a %d-byte buffer" % (nbytes, int(lib().gmupt_buffer_size(self.h))), ERR_INVALID_ARGUMENT)
+        torch.cuda.current_stream(device).synchronize()
+        _check(lib().gmupt_buffer_update_device(self.h, C.c_void_p(tensor.data_ptr()), nbytes))
 
     def read(self, dtype=np.uint8):
         """The buffer's bytes as a new array of `dtype` (gmupt_buffer_read: synchronous)."""
@@ -506,6 +532,7 @@ class Renderer:
         self.pool = pool_paths or PATHCOUNT
         self._scene = None
         self._temporals = []   # history handles of this renderer: closed before it
+        self._normals = []     # Normals handles of this renderer: closed before it
 
     def bind_scene(self, sb):
         self._scene = sb  # keep the buffers alive
@@ -733,7 +760,7 @@ class Renderer:
 
     def close(self):
         if self.h:
-            for t in self._temporals:
+            for t in self._temporals + self._normals:
                 t.close()
             lib().gmupt_renderer_destroy(self.h)
             self.h = _P()
@@ -757,6 +784,53 @@ class Temporal:
         if self.h:
             lib().gmupt_temporal_destroy(self.h)
             self.h = _P()
+
+
+class Normals:
+    """gmupt_normals: smooth vertex normals of one index list, recomputed on the GPU from the vertex buffer the renderer is bound to and
+    written into the `normal` field of its property records (include/gmupt.h "normals" states the rule).  indices: (n, 3) int32, a numpy
+    array (uploaded) or a torch device tensor (used in place; the handle keeps its own copy).  It uses the renderer's device and stream
+    and is closed with it at the latest."""
+
+    def __init__(self, renderer, indices):
+        import torch
+        device = torch.device("cuda", getattr(renderer.dev, "index", 0))
+        if isinstance(indices, torch.Tensor):
+            if indices.device != device or indices.dtype != torch.int32:
+                raise GmuptError("Normals: an index tensor must be int32 on %s" % device, ERR_INVALID_ARGUMENT)
+            idx = indices.contiguous().reshape(-1)
+        else:
+            idx = torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)).to(device)
+        self.renderer = renderer
+        self.h = _P()
+        torch.cuda.current_stream(device).synchronize()
+        _check(lib().gmupt_normals_create(renderer.h, C.c_void_p(idx.data_ptr()) if idx.numel() else None, idx.numel() // 3, C.byref(self.h)))
+        renderer._normals.append(self)
+
+    def update(self, info=False):
+        """gmupt_normals_update on the renderer's stream.  info=False: no host synchronisation, returns None.  info=True: synchronises
+        and returns the gmupt_normals_info fields as a dict (ms = device time of the two launches)."""
+        if not info:
+            _check(lib().gmupt_normals_update(self.h, None))
+            return None
+        ni = NormalsInfo()
+        _check(lib().gmupt_normals_update(self.h, C.byref(ni)))
+        return {"num_verts": int(ni.num_verts), "num_tris": int(ni.num_tris), "max_valence": int(ni.max_valence), "ms": float(ni.ms)}
+
+    def close(self):
+        if self.h:
+            lib().gmupt_normals_destroy(self.h)
+            self.h = _P()
+
+
+def vertex_normals_host(verts, indices, threads=16):
+    """gmupt_vertex_normals_host: the smooth-normal rule of include/gmupt.h on the CPU in binary32, bit for bit what Normals.update()
+    writes.  verts (V, 3) float32, indices (n, 3) int32.  Returns (V, 3) float32."""
+    verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
+    out = np.empty_like(verts)
+    _check(lib().gmupt_vertex_normals_host(_ptr(verts), verts.shape[0], _ptr(indices), indices.shape[0], _ptr(out), int(threads)))
+    return out
 
 
 def camera_pick_ray(cam_buffer, px, py):

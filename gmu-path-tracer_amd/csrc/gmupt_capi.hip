@@ -284,6 +284,7 @@ extern "C" int gmupt_renderer_bind_scene(gmupt_renderer* r, const gmupt_buffer* 
     s.lights = (const gmupt_light*)lights->dptr; s.props = (const gmupt_tri_props*)tri_props->dptr; s.materials = (const gmupt_material*)materials->dptr;
     s.numNodes = (uint32_t)nodes->elems; s.numTris = (uint32_t)triangles->elems; s.numVerts = (uint32_t)vertices->elems; s.numMaterials = (uint32_t)materials->elems;
     GMUPT_TRY(build_traversal_copy(r, nodes, triangles, vertices));
+    r->boundProps = tri_props;
     r->sceneBound = true;
     r->bindingId++;
     return GMUPT_OK;

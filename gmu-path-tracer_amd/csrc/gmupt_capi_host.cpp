@@ -235,6 +235,21 @@ extern "C" int gmupt_lbvh_build_host(const float* verts, uint32_t num_verts, con
     return GMUPT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ normals: the host reference (pt_normals.cpp) of gmupt_normals_update
+extern "C" int gmupt_vertex_normals_host(const float* verts, uint32_t num_verts, const int32_t* indices, uint32_t num_tris, float* normals_out, uint32_t threads)
+{
+    if (!verts || !indices || !normals_out || num_verts == 0 || num_tris == 0) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_vertex_normals_host: null or empty array");
+    if (num_tris > kNmMaxTris) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_vertex_normals_host: more than 2^30 triangles");
+    for (size_t c = 0; c < 3 * (size_t)num_tris; c++)
+        if ((uint32_t)indices[c] >= num_verts) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_vertex_normals_host: triangle %zu references vertex %d of %u", c / 3, indices[c], num_verts);
+    try {
+        normals_host(verts, num_verts, indices, num_tris, normals_out, clamp_threads(threads));
+    } catch (const std::bad_alloc&) {
+        return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_vertex_normals_host: out of host memory for %u triangles", num_tris);
+    }
+    return GMUPT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ host: SBVH
 extern "C" void gmupt_sbvh_default_params(gmupt_sbvh_params* p)
 {

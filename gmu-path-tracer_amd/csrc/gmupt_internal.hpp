@@ -7,6 +7,7 @@
 #include "pt_motion.hpp"
 #include "pt_travtables.hpp"
 #include "pt_lbvh.hpp"                // and with it pt_refit.hpp, pt_device.hpp, detmath.hpp
+#include "pt_normals.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
@@ -116,6 +117,7 @@ struct gmupt_renderer {
     // refit (gmupt_renderer_refit): the buffers of the binding with their element counts, and what build_trav_tables (pt_travtables.hpp) knows about the
     // topology of its tables -- host vectors, uploaded into one allocation (rfDev) by the first refit after a bind
     const gmupt_buffer* boundNodes = nullptr; const gmupt_buffer* boundTris = nullptr; const gmupt_buffer* boundVerts = nullptr;
+    const gmupt_buffer* boundProps = nullptr;   // normals (gmupt_normals_update): the property buffer of the binding
     size_t boundElems[3] = { 0, 0, 0 };
     std::vector<uint32_t> rfLevelNodes, rfLevelOff, rfNodeMap, rfWideMap, rfOpened;
     DevMem rfDev;
@@ -148,6 +150,14 @@ struct gmupt_temporal {
 struct gmupt_lbvh {
     gmupt_device* dev; hipStream_t stream = nullptr; EventPair ev; DevMem scratch; uint32_t capTris = 0; size_t sortTemp = 0;
     ~gmupt_lbvh() { if (stream) (void)hipStreamDestroy(stream); }        // gmupt_lbvh_destroy has synchronised it
+};
+
+// the adjacency of one index list for a renderer's vertices (gmupt_normals_*): device memory laid out by normals_layout (pt_normals.hip)
+struct gmupt_normals {
+    gmupt_renderer* r = nullptr;
+    uint32_t numVerts = 0, numTris = 0, maxValence = 0;
+    DevMem mem; NmLayout off{};
+    EventPair ev;
 };
 
 // ------------------------------------------------------------------------------------------------ shared between units

@@ -1,13 +1,13 @@
 // Host-side entry points of the kernel files and of the host workers next to them, as the C-API units (gmupt_capi*.hip) call them.
 // Every file that defines one of these includes this header, so that the compiler checks the definition against the declaration
-// (lbvh_build_host of pt_lbvh.cpp is declared in pt_lbvh.hpp).
+// (lbvh_build_host of pt_lbvh.cpp is declared in pt_lbvh.hpp, normals_host of pt_normals.cpp in pt_normals.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "../../include/gmupt.h"
 
 namespace gmupt {
-struct RenderParams; struct SceneView; struct DnParams; struct TpParams; struct TpPrev; struct RfArgs; struct LbScratch; struct LbStaging;   // pt_*.hpp
+struct RenderParams; struct SceneView; struct DnParams; struct TpParams; struct TpPrev; struct RfArgs; struct LbScratch; struct LbStaging; struct NmLayout; struct NmArgs;   // pt_*.hpp
 
 void launch_clear(const RenderParams& p, hipStream_t s);
 void launch_logic(const RenderParams& p, hipStream_t s);
@@ -48,4 +48,8 @@ hipError_t lbvh_sort_temp_bytes(uint32_t n, size_t* bytes);
 LbScratch lbvh_scratch_layout(uint32_t n, size_t sortTemp);
 hipError_t launch_lbvh(void* scratch, const LbScratch& off, size_t sortTemp, const float* verts, uint32_t numVerts, const int32_t* indices, uint32_t n,
                        const uint32_t* vertexMaterial, uint32_t maxLeaf, hipStream_t s, LbStaging& st);
+hipError_t normals_sort_temp_bytes(uint32_t numTris, uint32_t numVerts, size_t* bytes);
+NmLayout normals_layout(uint32_t numTris, uint32_t numVerts, size_t sortTemp);
+hipError_t launch_normals_create(const NmArgs& a, void* sortTemp, size_t sortTempBytes, hipStream_t s);
+void launch_normals_update(const NmArgs& a, hipStream_t s);
 }

@@ -52,6 +52,7 @@ void Renderer::createBuffers(Resolution res)
 
 void Renderer::initScene(const std::string& name)
 {
+	mNormals.reset();
 	mScene = Scene(mDevice.get(), name); // old resources die with the temporary (Source/Renderer.cpp:55)
 	mScene.mHipDevice = mHipDevice;
 	mScene.mCamera.getBuffer()->lightCount = static_cast<uint32_t>(mScene.lightCount() < 2 ? 2 : mScene.lightCount()); // Camera.hpp:20: never below the default 2
@@ -191,10 +192,25 @@ std::vector<float> Renderer::denoiseTemporal(unsigned aovSamples, const gmupt_te
 	return out;
 }
 
-gmupt_refit_info Renderer::refitScene(bool keepHistory)
+gmupt_refit_info Renderer::refitScene(bool keepHistory, bool smoothNormals)
 {
 	gmupt_refit_info info{};
 	bindScene(); // (the scene is bound on first use: a refit before the first frame starts from the loaded tree)
+	if (smoothNormals)
+	{
+		if (!mNormals)
+		{
+			const std::vector<int32_t>& list = mScene.mScene.indices;
+			void* d = nullptr;
+			if (hipSetDevice(mHipDevice) != hipSuccess || hipMalloc(&d, list.size() * sizeof(int32_t)) != hipSuccess) throw std::runtime_error("refitScene: cannot allocate the index list on the device");
+			DeviceMemory indices(d);
+			if (hipMemcpy(d, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("refitScene: cannot upload the index list");
+			gmupt_normals* n = nullptr;
+			check(gmupt_normals_create(mRenderer.get(), static_cast<const int32_t*>(d), static_cast<uint32_t>(list.size() / 3), &n));
+			mNormals.reset(n);
+		}
+		check(gmupt_normals_update(mNormals.get(), nullptr));
+	}
 	check(gmupt_renderer_refit(mRenderer.get(), &info));
 	mScene.mCamera.getBuffer()->iterationCounter = -1; // paths in flight carry hits of the old geometry
 	if (!keepHistory) resetHistory();
@@ -204,6 +220,7 @@ gmupt_refit_info Renderer::refitScene(bool keepHistory)
 gmupt_lbvh_info Renderer::rebuildScene(unsigned maxLeafSize, const std::vector<int32_t>* indices)
 {
 	const gmupt_lbvh_info info = mScene.rebuildOnDevice(maxLeafSize, indices);
+	mNormals.reset();                                  // another triangle list needs another adjacency
 	mSceneBound = false;
 	bindScene();                                       // waits for the renderer's stream before it lets go of the old tree
 	mScene.mRetiredBVHBuffer.reset();

@@ -68,8 +68,11 @@ public:
 	void resetHistory();
 	// after Scene::setVertices: the tree's boxes and this renderer's traversal tables recomputed on the GPU for the moved vertices
 	// (gmupt_renderer_refit; the topology of the tree stays), the accumulation restarted, the temporal history dropped -- or kept
-	// (keepHistory) for denoiseTemporalMotion, which follows the moved surface.  Throws like the other wrappers.
-	gmupt_refit_info refitScene(bool keepHistory = false);
+	// (keepHistory) for denoiseTemporalMotion, which follows the moved surface.  smoothNormals: before the refit, area-weighted vertex normals
+	// are recomputed on the GPU from the moved vertices and written into the property buffer (gmupt_normals_update, include/gmupt.h
+	// "normals") through this renderer's own handle, built on first use from the scene's index list and dropped by rebuildScene / initScene.
+	// Throws like the other wrappers.
+	gmupt_refit_info refitScene(bool keepHistory = false, bool smoothNormals = false);
 	// geometry a refit does not cover (after Scene::setVertices with vertices that moved far, or with another triangle list): a new tree
 	// from the GPU LBVH builder (Scene::rebuildOnDevice) bound in place of the old one, the accumulation restarted and the temporal history
 	// dropped -- a new binding is a new geometry.  The host pass of the bind (the traversal tables) runs as for any bind.
@@ -85,11 +88,13 @@ private:
 	struct DeviceDeleter { void operator()(gmupt_device* d) const { gmupt_device_destroy(d); } };
 	struct RendererDeleter { void operator()(gmupt_renderer* r) const { gmupt_renderer_destroy(r); } };
 	struct TemporalDeleter { void operator()(gmupt_temporal* t) const { gmupt_temporal_destroy(t); } };
+	struct NormalsDeleter { void operator()(gmupt_normals* n) const { gmupt_normals_destroy(n); } };
 
 	void* mHwnd;
 	std::unique_ptr<gmupt_device, DeviceDeleter> mDevice;
 	std::unique_ptr<gmupt_renderer, RendererDeleter> mRenderer; // path state, queues, counters, accumulation target
 	std::unique_ptr<gmupt_temporal, TemporalDeleter> mTemporal; // history of denoiseTemporal (declared after mRenderer: destroyed before it)
+	std::unique_ptr<gmupt_normals, NormalsDeleter> mNormals;    // adjacency of refitScene(.., smoothNormals) (declared after mRenderer: destroyed before it)
 	Scene mScene;
 	Resolution mResolution;
 	RowBand mBand;

@@ -68,6 +68,8 @@ public:
 	// moved geometry (an extension; the reference has none): new positions for ALL vertices (3 floats each, the count of the loaded mesh) and,
 	// optionally, new normals -- into the mesh data, the vertex buffer and the normals inside the property buffer.  The tree keeps its
 	// topology: call Renderer::refitScene() afterwards.  Throws std::runtime_error on a wrong count or a failed upload.
+	// With Renderer::refitScene(.., smoothNormals = true) the normals are recomputed on the device and never read back: MeshData::normals
+	// then holds the last host-given normals (those of the loader, or of the last call with `normals`), not the device's.
 	void setVertices(const std::vector<float>& xyz, const std::vector<float>* normals = nullptr);
 	// geometry beyond a refit (vertices that moved far, another triangle list): a new tree from the GPU LBVH builder (gmupt_lbvh_build,
 	// include/gmupt.h "LBVH") over the device-resident vertex buffer.  indices: 3 per triangle into the loaded vertices, replacing the mesh's

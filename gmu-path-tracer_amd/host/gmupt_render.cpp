@@ -17,6 +17,8 @@
 //                [--vertices FILE]                        before the frames: moved positions for all vertices of the scene (raw little-endian float32,
 //                                                         3 per vertex) through Scene::setVertices + Renderer::refitScene; one JSON line with the
 //                                                         refit info; not with --ranks
+//                [--smooth-normals]                       with --vertices: smooth vertex normals recomputed on the GPU from the moved vertices before
+//                                                         the refit (Renderer::refitScene(.., smoothNormals = true))
 //                [--builder sbvh|lbvh [--leaf L]]         lbvh: before the frames (after --vertices) the tree is rebuilt on the GPU from the resident
 //                                                         vertices (Renderer::rebuildScene: Scene::rebuildOnDevice + bind), leaves of at most L
 //                                                         triangles (default 4); one JSON line with the build info; not with --ranks.
@@ -85,7 +87,7 @@ int main(int argc, char** argv)
 	unsigned ranks = 1, rank = 0; int device = -1;
 	std::string paramsOnly, rendezvous;
 	bool doPick = false; float pickX = 0.f, pickY = 0.f;
-	std::string verticesFile;
+	std::string verticesFile; bool smoothNormals = false;
 	std::string aovPrefix; unsigned aovSamples = 1;
 	std::string denoisePrefix;
 	std::string temporalPrefix;
@@ -115,6 +117,7 @@ int main(int argc, char** argv)
 		else if (a == "--aov-samples") aovSamples = std::strtoul(next(), nullptr, 10);
 		else if (a == "--denoise") denoisePrefix = next();
 		else if (a == "--vertices") verticesFile = next();
+		else if (a == "--smooth-normals") smoothNormals = true;
 		else if (a == "--temporal") temporalPrefix = next();
 		else if (a == "--builder") { builder = next(); if (builder != "sbvh" && builder != "lbvh") { std::fprintf(stderr, "--builder takes sbvh or lbvh\n"); return 2; } }
 		else if (a == "--leaf") { char* end = nullptr; const char* v = next(); leaf = std::strtoul(v, &end, 10); if (end == v || *end || leaf < 1 || leaf > 64) { std::fprintf(stderr, "--leaf takes a number in 1..64\n"); return 2; } }
@@ -130,6 +133,7 @@ int main(int argc, char** argv)
 			            "             [--temporal PREFIX] the temporal preview after the frames (PREFIX.pfm); with --vertices the frames are rendered on the loaded pose first,\n"
 			            "                                 then on the moved one, and the preview keeps its history across the refit (Renderer::denoiseTemporalMotion)\n"
 			            "             [--vertices FILE]   before the frames: moved positions of all vertices (raw float32 xyz), refitted on the GPU; not with --ranks\n"
+			            "             [--smooth-normals]  with --vertices: smooth vertex normals recomputed on the GPU from the moved vertices before the refit\n"
 			            "             [--builder sbvh|lbvh [--leaf L]]   lbvh: the tree rebuilt on the GPU before the frames (linear BVH, leaves of at most L triangles,\n"
 			            "                                 default 4), one JSON line with the build info; not with --ranks.  With --build-only: the host reference of that build\n"
 			            "             [--dump-tree FILE]  with --build-only: the flattened tree, raw (48-byte nodes, then 16-byte triangle records)\n"
@@ -214,6 +218,8 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--denoise filters the frame of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
 		if (!verticesFile.empty() && ranks > 1)
 			throw std::invalid_argument("--vertices moves the geometry of a single process: it cannot be combined with --ranks N > 1");
+		if (smoothNormals && verticesFile.empty())
+			throw std::invalid_argument("--smooth-normals recomputes the normals of moved vertices: it needs --vertices FILE");
 		if (builder == "lbvh" && ranks > 1)
 			throw std::invalid_argument("--builder lbvh rebuilds the tree of a single process: it cannot be combined with --ranks N > 1");
 		if (ranks > 1 || !rendezvous.empty())
@@ -255,7 +261,7 @@ int main(int argc, char** argv)
 			for (size_t n; (n = std::fread(chunk, sizeof(float), 3072, f)) > 0;) xyz.insert(xyz.end(), chunk, chunk + n);
 			std::fclose(f);
 			renderer.scene().setVertices(xyz);
-			const gmupt_refit_info info = renderer.refitScene(!temporalPrefix.empty());
+			const gmupt_refit_info info = renderer.refitScene(!temporalPrefix.empty(), smoothNormals);
 			std::printf("{\"refit\": {\"rebuilt\": %u, \"reason\": %u, \"levels\": %u, \"opened_nodes\": %u, \"ms\": %.6g}}\n", info.rebuilt, info.reason, info.levels, info.opened_nodes, info.ms);
 		}
 		if (builder == "lbvh") {

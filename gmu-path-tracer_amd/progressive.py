@@ -32,6 +32,7 @@ class ProgressiveSession:
         self.motion = bool(motion)   # denoised_temporal goes through the motion entry point (also set by set_vertices(keep_history=True))
         self.lbvh = None       # the GPU tree builder of rebuild(), created on first use
         self._indices = None   # the index list of the last rebuild()
+        self.normals = None    # the capi.Normals of set_vertices(normals="smooth"), created on first use, dropped by rebuild()
 
     # ---- events (applied before the next frame, like the GUI callbacks of the reference)
     def move_camera(self, mouse_dx=0.0, mouse_dy=0.0, w=False, s=False, a=False, d=False):
@@ -45,16 +46,38 @@ class ProgressiveSession:
         if self.temporal is not None:
             self.temporal.reset()                    # the history was lit by the old lights
 
-    def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False):
+    def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False, indices=None):
         """The geometry moved (same vertex count, same triangles): upload the vertices, and `normals` (when given) into the property
         records, refit the tree and the renderer's traversal tables on the GPU (gmupt_renderer_refit), restart the accumulation.  The
         temporal history shows the old surface and is dropped; with keep_history=True it is kept, and denoised_temporal() from then on
         looks it up where each surface point was (gmupt_render_denoised_temporal_motion).  The first such call still drops a history
         that earlier denoised_temporal() calls wrote, because its record sets carry no vertex pose; ProgressiveSession(..., motion=True)
         uses the motion entry point from the first preview on, so that nothing is dropped.  scene_buffers: the capi.SceneBuffers the
-        renderer is bound to.  Returns the refit info dict."""
-        scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
-        if normals is not None:
+        renderer is bound to.  Returns the refit info dict.
+        verts: a numpy array, or a torch tensor on the renderer's GPU (float32, contiguous), which goes from device memory to the vertex
+        buffer without a trip through the host (Buffer.update_from_device).
+        normals: None leaves the property records alone; an array is patched in through the host; "smooth" recomputes area-weighted
+        vertex normals on the GPU before the refit (capi.Normals, created on first use and kept until rebuild() or close()), no host
+        round trip.  Its index list is `indices` ((n, 3) int32, numpy or a torch device tensor; given only with the first "smooth"
+        call, or to replace the list), else the list of the last rebuild(), else the triangle records the scene is bound to -- in which
+        a triangle that the SBVH's spatial splits put into several leaves appears, and counts, several times."""
+        smooth = isinstance(normals, str)
+        if smooth and normals != "smooth":
+            raise ValueError("set_vertices: normals=%r (None, an array or \"smooth\")" % (normals,))
+        if hasattr(verts, "is_cuda"):
+            scene_buffers.verts.update_from_device(verts)
+        else:
+            scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
+        if smooth:
+            from . import capi
+            if indices is not None and self.normals is not None:
+                self.normals.close(); self.normals = None
+            if self.normals is None:
+                if indices is None:
+                    indices = self._indices if self._indices is not None else scene_buffers.tris.read(capi.triangle_dtype)["v"]
+                self.normals = capi.Normals(self.renderer, indices)
+            self.normals.update()
+        elif normals is not None:
             from . import capi
             props = scene_buffers.props.read(capi.tri_props_dtype)
             props["normal"] = np.asarray(normals, np.float32).reshape(-1, 3)
@@ -95,13 +118,18 @@ class ProgressiveSession:
         for b in old:
             b.close()
         self._indices = indices
+        if self.normals is not None:                 # a new triangle list needs a new adjacency
+            self.normals.close(); self.normals = None
         self.camera.reset_accumulation()
         if self.temporal is not None:
             self.temporal.reset()
         return info
 
     def close(self):
-        """Releases what the session itself created: the tree builder of rebuild() and the history handle of denoised_temporal()."""
+        """Releases what the session itself created: the tree builder of rebuild(), the Normals of set_vertices(normals="smooth") and the
+        history handle of denoised_temporal()."""
+        if self.normals is not None:
+            self.normals.close(); self.normals = None
         if self.lbvh is not None:
             self.lbvh.close(); self.lbvh = None
         if self.temporal is not None:

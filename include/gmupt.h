@@ -495,7 +495,7 @@ int gmupt_temporal_integrate_host(const float* beauty_rgba, const gmupt_aov* aov
  *   6. ms = device time of step 3 (hipEvents on the stream); opened_nodes = size of the checked list.
  * Refit does not touch the frame, path state, queues or statistics.  Paths in flight carry hits of the old geometry: restart the
  * accumulation (iterationCounter = 0) as after a light edit.  Shading normals live in the GMUPT_BUFFER_TRI_PROPS buffer, whose pointer is
- * bound: update it with gmupt_buffer_update, no refit involved.  Several renderers bound to the same buffers each call refit; the node
+ * bound: update it with gmupt_buffer_update, or recompute smooth normals on the device with gmupt_normals_update; no refit involved.  Several renderers bound to the same buffers each call refit; the node
  * boxes are recomputed to the same bytes each time.
  * What stays as bind left it: which nodes live in LDS, the line pairing of Node64 and the collapse choices were made by surface area of
  * the OLD boxes.  They affect speed only.  A caller whose mesh has moved far rebuilds the SBVH and rebinds; refit is for the frames in
@@ -620,6 +620,51 @@ int gmupt_lbvh_build(gmupt_lbvh* h, const gmupt_buffer* vertices, const int32_t*
                      const uint32_t* device_vertex_material /* may be NULL */, const gmupt_lbvh_params* params /* may be NULL */,
                      gmupt_buffer** nodes_out, gmupt_buffer** triangles_out, int32_t* device_ref_triangle /* may be NULL */,
                      gmupt_lbvh_info* info /* may be NULL */);
+
+/* ---- normals: smooth vertex normals recomputed on the GPU for a mesh that deforms (an extension; the reference loads its normals once) ----
+ * The shading normals are the `normal` field of the GMUPT_BUFFER_TRI_PROPS records, one record per vertex, read by the kernels from the
+ * caller's buffer.  gmupt_normals_update rewrites that field from the vertex buffer the renderer is bound to, on the renderer's stream.
+ *
+ * The rule (binary32, nothing contracted, division and square root correctly rounded; gmupt_vertex_normals_host and the kernels run the
+ * same statements, csrc/pt_normals.hpp).  Input: num_verts vertices, num_tris index triples, each index in [0, num_verts).  Corner
+ * c = 3*t + k is corner k of triangle t.
+ *   1. Face vector of triangle t with vertices p0, p1, p2: e1 = p1 - p0, e2 = p2 - p0 (per component),
+ *      f = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x).  Its length is twice the area: the sum below is
+ *      area-weighted.  A triangle that is listed twice counts twice.
+ *   2. Vertex sum: s = (0, 0, 0); then, for the corners that reference the vertex IN ASCENDING CORNER NUMBER, s = s + f(triangle of the
+ *      corner), per component.  The order is part of the rule: float atomics or a tree reduction give another result.
+ *   3. l = sqrt((s.x*s.x + s.y*s.y) + s.z*s.z).  If l > 0 and l is finite: n = s * (1.0f / l) per component.  Otherwise n = (0, 1, 0):
+ *      a vertex no triangle uses, a sum that vanished, underflowed or overflowed, and a NaN or an infinity anywhere in the vertex's fan.
+ *   4. Non-finite vertices are no error and need no readback: rule 3 absorbs them, and a vertex whose fan holds none is unaffected.
+ *   5. Only the three `normal` floats of the property records 0 .. num_verts-1 are written.  pad0, uv, materialID, pad1 and any records
+ *      beyond num_verts keep their bits.
+ * gmupt_vertex_normals_host: the rule on host arrays, no device; normals_out holds 3 floats per vertex.  Up to `threads` std::threads
+ *   (0 -> 1, at most 16); the result does not depend on the count.  NULL or empty input, an index outside [0, num_verts), more than 2^30
+ *   triangles: GMUPT_ERR_INVALID_ARGUMENT, nothing written.
+ * gmupt_normals: a handle of a renderer for one index list: it uses the renderer's device and stream and must not outlive the renderer.
+ *   gmupt_normals_create: device_indices = caller-owned DEVICE memory, 3 * num_tris int32, 4-byte aligned, finished by the caller; the
+ *   handle keeps its own copy.  It needs a bound scene (GMUPT_ERR_NOT_BOUND); num_verts = the element count of the bound vertex buffer.
+ *   On the renderer's stream it builds the vertex -> corner adjacency -- the corner numbers sorted by (vertex, corner) with a stable radix
+ *   sort, and where each vertex's corners start -- then reads ONE flag word pair back and synchronises once.  An index outside the vertex
+ *   buffer: GMUPT_ERR_INVALID_ARGUMENT and no handle.  Device memory: 40 bytes per triangle and 4 per vertex are kept (index copy, corner
+ *   list, face vectors; offsets); 36 more per triangle plus the sort's temporary storage exist during create only.
+ * gmupt_normals_update: works on the vertex and property buffers the renderer is bound to NOW (a rebind to buffers of the same vertex
+ *   count needs no new handle).  GMUPT_ERR_NOT_BOUND without a scene; a bound vertex count other than at create, or fewer property records
+ *   than vertices: GMUPT_ERR_INVALID_ARGUMENT, nothing written.  Two launches on the renderer's stream, ordered with gmupt_renderer_refit
+ *   and gmupt_iterate: the face vectors, then one thread per vertex (a vertex of very high valence serialises its thread).  info == NULL:
+ *   no host synchronisation.  With info: synchronises; ms = device time of the two launches (hipEvents), max_valence = the most corners
+ *   on one vertex.  Paths in flight have shaded with the old normals: restart the accumulation as after a refit.
+ * gmupt_buffer_update_device: gmupt_buffer_update with the source in device memory of the buffer's device (e.g. a pose computed by
+ *   another library on the GPU): the same ordering (the device is idle before and after the copy) and the same size check.  The caller
+ *   has finished the work that produced device_src.  A source that is not device memory of that device: GMUPT_ERR_INVALID_ARGUMENT. */
+typedef struct { uint32_t num_verts, num_tris, max_valence, pad; double ms; } gmupt_normals_info;   /* 24 bytes */
+int gmupt_vertex_normals_host(const float* verts, uint32_t num_verts, const int32_t* indices, uint32_t num_tris, float* normals_out /* 3 per vertex */,
+                              uint32_t threads);
+typedef struct gmupt_normals gmupt_normals;
+int gmupt_normals_create(gmupt_renderer* r, const int32_t* device_indices, uint32_t num_tris, gmupt_normals** out);
+int gmupt_normals_update(gmupt_normals* n, gmupt_normals_info* info /* may be NULL */);
+void gmupt_normals_destroy(gmupt_normals* n);
+int gmupt_buffer_update_device(gmupt_buffer* buf, const void* device_src, size_t bytes);
 
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
