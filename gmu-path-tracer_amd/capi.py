@@ -171,6 +171,21 @@ class NormalsInfo(C.Structure):
 assert C.sizeof(NormalsInfo) == 24
 
 
+class TreeCostInfo(C.Structure):
+    """gmupt_tree_cost_info: 64 bytes."""
+    _fields_ = [("sum_inner", C.c_double), ("sum_leaf", C.c_double), ("num_inner", C.c_uint32), ("num_leaves", C.c_uint32),
+                ("num_refs", C.c_uint64), ("max_leaf_refs", C.c_uint32), ("pad", C.c_uint32), ("root_half_area", C.c_double),
+                ("sah", C.c_double), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {"sum_inner": float(self.sum_inner), "sum_leaf": float(self.sum_leaf), "num_inner": int(self.num_inner),
+                "num_leaves": int(self.num_leaves), "num_refs": int(self.num_refs), "max_leaf_refs": int(self.max_leaf_refs),
+                "root_half_area": float(self.root_half_area), "sah": float(self.sah), "ms": float(self.ms)}
+
+
+assert C.sizeof(TreeCostInfo) == 64
+
+
 class GmuptError(RuntimeError):
     def __init__(self, msg, code=0):
         super().__init__(msg)
@@ -246,6 +261,8 @@ SYMBOLS = {
     "gmupt_normals_update": (C.c_int, [_P, C.POINTER(NormalsInfo)]),
     "gmupt_normals_destroy": (None, [_P]),
     "gmupt_buffer_update_device": (C.c_int, [_P, _P, C.c_size_t]),
+    "gmupt_tree_cost_host": (C.c_int, [_P, C.c_uint32, C.POINTER(TreeCostInfo), C.c_uint32]),
+    "gmupt_renderer_tree_cost": (C.c_int, [_P, _P, C.POINTER(TreeCostInfo)]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -544,6 +561,15 @@ class Renderer:
         info = RefitInfo()
         _check(lib().gmupt_renderer_refit(self.h, C.byref(info)))
         return {k: getattr(info, k) for k, _ in RefitInfo._fields_}
+
+    def tree_cost(self, nodes=None):
+        """gmupt_renderer_tree_cost: the surface-area cost of a node buffer, computed where it lives (include/gmupt.h "Tree cost"), on the
+        renderer's stream behind a preceding refit().  nodes=None: the node buffer the renderer is bound to; else any Buffer of kind
+        BUFFER_BVH_NODES of this device, e.g. the one Lbvh.build just returned.  Returns the gmupt_tree_cost_info fields as a dict: sah,
+        sum_inner, sum_leaf, root_half_area, num_inner, num_leaves, num_refs, max_leaf_refs and ms, the device time of the launches."""
+        ti = TreeCostInfo()
+        _check(lib().gmupt_renderer_tree_cost(self.h, nodes.h if nodes is not None else None, C.byref(ti)))
+        return ti.as_dict()
 
     def set_camera(self, cam_buffer):
         _check(lib().gmupt_set_camera(self.h, C.byref(cam_buffer)))
@@ -1186,6 +1212,15 @@ def tree_sah(nodes):
     leaf = nodes["isLeaf"] != 0
     count = np.where(leaf, nodes["right"] - nodes["left"], 2)
     return float((area * count).sum() / area[0])
+
+
+def tree_cost_host(nodes, threads=16):
+    """gmupt_tree_cost_host: the tree-cost rule of include/gmupt.h on the CPU, bit for bit what Renderer.tree_cost() returns for the same
+    records (ms = 0).  nodes: an array of bvh_node_dtype; any records do, no link is followed.  The thread count changes no bit."""
+    nodes = np.ascontiguousarray(nodes, dtype=bvh_node_dtype)
+    ti = TreeCostInfo()
+    _check(lib().gmupt_tree_cost_host(_ptr(nodes), nodes.shape[0], C.byref(ti), int(threads)))
+    return ti.as_dict()
 
 
 class Lbvh:

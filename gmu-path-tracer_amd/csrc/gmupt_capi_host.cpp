@@ -250,6 +250,21 @@ extern "C" int gmupt_vertex_normals_host(const float* verts, uint32_t num_verts,
     return GMUPT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ tree cost: the host reference (pt_treecost.cpp) of gmupt_renderer_tree_cost
+extern "C" int gmupt_tree_cost_host(const gmupt_bvh_node* nodes, uint32_t n, gmupt_tree_cost_info* info, uint32_t threads)
+{
+    if (!nodes || !info || n == 0) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_tree_cost_host: null or empty array");
+    TcPartial total;
+    try {
+        total = tree_cost_host(nodes, n, clamp_threads(threads));
+    } catch (const std::bad_alloc&) {
+        return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_tree_cost_host: out of host memory for %u nodes", n);
+    }
+    tc_fill_info(total, info);
+    info->ms = 0.0;
+    return GMUPT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ host: SBVH
 extern "C" void gmupt_sbvh_default_params(gmupt_sbvh_params* p)
 {

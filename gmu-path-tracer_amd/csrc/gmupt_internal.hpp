@@ -8,6 +8,7 @@
 #include "pt_travtables.hpp"
 #include "pt_lbvh.hpp"                // and with it pt_refit.hpp, pt_device.hpp, detmath.hpp
 #include "pt_normals.hpp"
+#include "pt_treecost.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
@@ -122,6 +123,9 @@ struct gmupt_renderer {
     std::vector<uint32_t> rfLevelNodes, rfLevelOff, rfNodeMap, rfWideMap, rfOpened;
     DevMem rfDev;
     EventPair rfEv;
+    // tree cost (gmupt_renderer_tree_cost): the partial results of every level, 48 bytes per 256 records; allocated on first use, grown on demand
+    DevMem tcScratch;
+    EventPair tcEv;
 
     __attribute__((visibility("default"))) ~gmupt_renderer() { if (stream) (void)hipStreamDestroy(stream); }   // gmupt_renderer_destroy has synchronised it; the library has always exported this symbol
     uint32_t tile_x0() const { return p.tileEnabled ? p.tileX0 : 0u; } uint32_t tile_y0() const { return p.tileEnabled ? p.tileY0 : 0u; }   // the origin of the rendered rectangle

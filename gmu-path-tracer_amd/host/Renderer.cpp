@@ -217,6 +217,14 @@ gmupt_refit_info Renderer::refitScene(bool keepHistory, bool smoothNormals)
 	return info;
 }
 
+gmupt_tree_cost_info Renderer::treeCost()
+{
+	gmupt_tree_cost_info info{};
+	bindScene(); // (the scene is bound on first use, as in refitScene)
+	check(gmupt_renderer_tree_cost(mRenderer.get(), nullptr, &info));
+	return info;
+}
+
 gmupt_lbvh_info Renderer::rebuildScene(unsigned maxLeafSize, const std::vector<int32_t>* indices)
 {
 	const gmupt_lbvh_info info = mScene.rebuildOnDevice(maxLeafSize, indices);

@@ -73,6 +73,10 @@ public:
 	// "normals") through this renderer's own handle, built on first use from the scene's index list and dropped by rebuildScene / initScene.
 	// Throws like the other wrappers.
 	gmupt_refit_info refitScene(bool keepHistory = false, bool smoothNormals = false);
+	// the surface-area cost of the bound tree, measured on the GPU on the renderer's stream (gmupt_renderer_tree_cost, include/gmupt.h
+	// "Tree cost"): after a refitScene it tells how far the refitted tree has degraded against its value at bind time, i.e. when
+	// rebuildScene pays.  Binds the scene on first use; touches neither the frame nor the accumulation.
+	gmupt_tree_cost_info treeCost();
 	// geometry a refit does not cover (after Scene::setVertices with vertices that moved far, or with another triangle list): a new tree
 	// from the GPU LBVH builder (Scene::rebuildOnDevice) bound in place of the old one, the accumulation restarted and the temporal history
 	// dropped -- a new binding is a new geometry.  The host pass of the bind (the traversal tables) runs as for any bind.

@@ -19,6 +19,9 @@
 //                                                         refit info; not with --ranks
 //                [--smooth-normals]                       with --vertices: smooth vertex normals recomputed on the GPU from the moved vertices before
 //                                                         the refit (Renderer::refitScene(.., smoothNormals = true))
+//                [--tree-cost]                            the surface-area cost of the bound tree (Renderer::treeCost), once after bind and once more
+//                                                         after --vertices is applied: one JSON line each with the gmupt_tree_cost_info fields, the
+//                                                         doubles as hex bit patterns; not with --ranks
 //                [--builder sbvh|lbvh [--leaf L]]         lbvh: before the frames (after --vertices) the tree is rebuilt on the GPU from the resident
 //                                                         vertices (Renderer::rebuildScene: Scene::rebuildOnDevice + bind), leaves of at most L
 //                                                         triangles (default 4); one JSON line with the build info; not with --ranks.
@@ -76,6 +79,15 @@ void writeAovPfm(const std::string& path, const std::vector<gmupt_aov>& aov, uns
 	}
 	std::fclose(f);
 }
+// the gmupt_tree_cost_info fields as one JSON line; the doubles as the hex bit patterns of their binary64 values (ms as a decimal: it is a time)
+void printTreeCost(const char* when, const gmupt_tree_cost_info& c)
+{
+	auto bits = [](double d) { unsigned long long u; std::memcpy(&u, &d, sizeof(u)); return u; };
+	std::printf("{\"tree_cost\": {\"when\": \"%s\", \"sah\": \"%016llx\", \"sum_inner\": \"%016llx\", \"sum_leaf\": \"%016llx\", \"root_half_area\": \"%016llx\", "
+	            "\"num_inner\": %u, \"num_leaves\": %u, \"num_refs\": %llu, \"max_leaf_refs\": %u, \"ms\": %.6g}}\n",
+	            when, bits(c.sah), bits(c.sum_inner), bits(c.sum_leaf), bits(c.root_half_area), c.num_inner, c.num_leaves,
+	            static_cast<unsigned long long>(c.num_refs), c.max_leaf_refs, c.ms);
+}
 }
 
 int main(int argc, char** argv)
@@ -92,6 +104,7 @@ int main(int argc, char** argv)
 	std::string denoisePrefix;
 	std::string temporalPrefix;
 	std::string builder = "sbvh", dumpTree; unsigned leaf = 4;
+	bool treeCost = false;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
 		auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -122,6 +135,7 @@ int main(int argc, char** argv)
 		else if (a == "--builder") { builder = next(); if (builder != "sbvh" && builder != "lbvh") { std::fprintf(stderr, "--builder takes sbvh or lbvh\n"); return 2; } }
 		else if (a == "--leaf") { char* end = nullptr; const char* v = next(); leaf = std::strtoul(v, &end, 10); if (end == v || *end || leaf < 1 || leaf > 64) { std::fprintf(stderr, "--leaf takes a number in 1..64\n"); return 2; } }
 		else if (a == "--dump-tree") dumpTree = next();
+		else if (a == "--tree-cost") treeCost = true;
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -134,6 +148,8 @@ int main(int argc, char** argv)
 			            "                                 then on the moved one, and the preview keeps its history across the refit (Renderer::denoiseTemporalMotion)\n"
 			            "             [--vertices FILE]   before the frames: moved positions of all vertices (raw float32 xyz), refitted on the GPU; not with --ranks\n"
 			            "             [--smooth-normals]  with --vertices: smooth vertex normals recomputed on the GPU from the moved vertices before the refit\n"
+			            "             [--tree-cost]       the surface-area cost of the bound tree, measured on the GPU, after bind and again after --vertices is applied:\n"
+			            "                                 one JSON line each, the doubles as hex bit patterns; not with --ranks\n"
 			            "             [--builder sbvh|lbvh [--leaf L]]   lbvh: the tree rebuilt on the GPU before the frames (linear BVH, leaves of at most L triangles,\n"
 			            "                                 default 4), one JSON line with the build info; not with --ranks.  With --build-only: the host reference of that build\n"
 			            "             [--dump-tree FILE]  with --build-only: the flattened tree, raw (48-byte nodes, then 16-byte triangle records)\n"
@@ -220,6 +236,8 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--vertices moves the geometry of a single process: it cannot be combined with --ranks N > 1");
 		if (smoothNormals && verticesFile.empty())
 			throw std::invalid_argument("--smooth-normals recomputes the normals of moved vertices: it needs --vertices FILE");
+		if (treeCost && ranks > 1)
+			throw std::invalid_argument("--tree-cost measures the tree of a single process: it cannot be combined with --ranks N > 1");
 		if (builder == "lbvh" && ranks > 1)
 			throw std::invalid_argument("--builder lbvh rebuilds the tree of a single process: it cannot be combined with --ranks N > 1");
 		if (ranks > 1 || !rendezvous.empty())
@@ -249,6 +267,7 @@ int main(int argc, char** argv)
 			return 0;
 		}
 		Renderer renderer(nullptr, { w, h }, scene, 0, pool, live);
+		if (treeCost) printTreeCost("bind", renderer.treeCost());
 		if (!verticesFile.empty() && !temporalPrefix.empty()) {   // the history of the loaded pose, which the preview after the refit follows
 			for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
 			renderer.denoiseTemporalMotion(aovSamples);
@@ -263,6 +282,7 @@ int main(int argc, char** argv)
 			renderer.scene().setVertices(xyz);
 			const gmupt_refit_info info = renderer.refitScene(!temporalPrefix.empty(), smoothNormals);
 			std::printf("{\"refit\": {\"rebuilt\": %u, \"reason\": %u, \"levels\": %u, \"opened_nodes\": %u, \"ms\": %.6g}}\n", info.rebuilt, info.reason, info.levels, info.opened_nodes, info.ms);
+			if (treeCost) printTreeCost("vertices", renderer.treeCost());
 		}
 		if (builder == "lbvh") {
 			const gmupt_lbvh_info info = renderer.rebuildScene(leaf);

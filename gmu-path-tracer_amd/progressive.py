@@ -33,6 +33,7 @@ class ProgressiveSession:
         self.lbvh = None       # the GPU tree builder of rebuild(), created on first use
         self._indices = None   # the index list of the last rebuild()
         self.normals = None    # the capi.Normals of set_vertices(normals="smooth"), created on first use, dropped by rebuild()
+        self.baseline = None   # the tree cost (sah) that set_vertices(rebuild_above=...) compares a refitted tree with; rebuild() forgets it
 
     # ---- events (applied before the next frame, like the GUI callbacks of the reference)
     def move_camera(self, mouse_dx=0.0, mouse_dy=0.0, w=False, s=False, a=False, d=False):
@@ -46,7 +47,7 @@ class ProgressiveSession:
         if self.temporal is not None:
             self.temporal.reset()                    # the history was lit by the old lights
 
-    def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False, indices=None):
+    def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False, indices=None, rebuild_above=None):
         """The geometry moved (same vertex count, same triangles): upload the vertices, and `normals` (when given) into the property
         records, refit the tree and the renderer's traversal tables on the GPU (gmupt_renderer_refit), restart the accumulation.  The
         temporal history shows the old surface and is dropped; with keep_history=True it is kept, and denoised_temporal() from then on
@@ -60,10 +61,26 @@ class ProgressiveSession:
         vertex normals on the GPU before the refit (capi.Normals, created on first use and kept until rebuild() or close()), no host
         round trip.  Its index list is `indices` ((n, 3) int32, numpy or a torch device tensor; given only with the first "smooth"
         call, or to replace the list), else the list of the last rebuild(), else the triangle records the scene is bound to -- in which
-        a triangle that the SBVH's spatial splits put into several leaves appears, and counts, several times."""
+        a triangle that the SBVH's spatial splits put into several leaves appears, and counts, several times.
+        rebuild_above: None (the default) refits and never rebuilds.  A float > 1 is the refit-or-rebuild policy on the tree cost
+        (capi.Renderer.tree_cost, measured on the GPU): the session's baseline is the sah of the tree as bound, taken before the upload
+        when there is none yet.  After the refit, cost = the sah of the refitted tree.  When cost > rebuild_above * baseline, an LBVH
+        candidate is built from the device-resident vertices (the indices and materials rebuild() would pick, its default leaf size)
+        and its sah measured before anything is bound.  A cheaper candidate is adopted exactly as by rebuild() -- buffers swapped, bound,
+        the Normals handle and the temporal history dropped -- and its cost is the new baseline; a candidate that is no cheaper is
+        closed, the refitted tree stays and its cost becomes the baseline, so that a losing candidate is not built again every frame.
+        A baseline of 0 (a root without area) never triggers.  The returned dict then also holds cost, baseline (the value the
+        decision was made against), candidate_cost (None when none was built) and tree_rebuilt.  There is no default threshold:
+        DESIGN.md "Tree cost" has the measurements."""
         smooth = isinstance(normals, str)
         if smooth and normals != "smooth":
             raise ValueError("set_vertices: normals=%r (None, an array or \"smooth\")" % (normals,))
+        if rebuild_above is not None:
+            rebuild_above = float(rebuild_above)
+            if not rebuild_above > 1.0:
+                raise ValueError("set_vertices: rebuild_above=%r (None or a float > 1)" % (rebuild_above,))
+            if self.baseline is None:
+                self.baseline = self.renderer.tree_cost()["sah"]
         if hasattr(verts, "is_cuda"):
             scene_buffers.verts.update_from_device(verts)
         else:
@@ -92,19 +109,25 @@ class ProgressiveSession:
             self.motion = True
         elif not keep_history and self.temporal is not None:
             self.temporal.reset()
+        if rebuild_above is None:
+            return info
+        cost = self.renderer.tree_cost()["sah"]                  # on the renderer's stream, behind the refit
+        info = dict(info, cost=cost, baseline=self.baseline, candidate_cost=None, tree_rebuilt=False)
+        if self.baseline > 0 and cost > rebuild_above * self.baseline:
+            nodes, tris, _, picked = self._build_candidate(scene_buffers, None, None, 4)
+            info["candidate_cost"] = self.renderer.tree_cost(nodes=nodes)["sah"]
+            if info["candidate_cost"] < cost:
+                self._adopt(scene_buffers, nodes, tris, picked)
+                info["tree_rebuilt"] = True
+                self.baseline = info["candidate_cost"]
+            else:
+                nodes.close(); tris.close()
+                self.baseline = cost
         return info
 
-    def rebuild(self, scene_buffers, verts=None, indices=None, vertex_material=None, max_leaf_size=4):
-        """The geometry changed beyond what a refit covers -- vertices that moved far, or another triangle list (a cut, a spawn, an LOD
-        switch): upload `verts` when given (at most the vertex count the buffer was created with), build an LBVH on the GPU from the
-        device-resident vertices (capi.Lbvh, gmupt_lbvh_build), put its node and triangle buffers into `scene_buffers` (the old ones are
-        closed), bind, restart the accumulation and drop the temporal history: a new binding is a new geometry.
-        indices: (n, 3) int32, numpy or a torch device tensor; None = the list of the last rebuild(), or, before any, the triangle
-        records the scene is bound to (an SBVH's spatial splits then appear as repeated triangles).  vertex_material: per vertex; None =
-        the materialID column of the property records.  Returns the gmupt_lbvh_info dict."""
+    def _build_candidate(self, scene_buffers, indices, vertex_material, max_leaf_size):
+        """An LBVH over the device-resident vertices of `scene_buffers`, not bound yet: (nodes, tris, gmupt_lbvh_info dict, indices used)."""
         from . import capi
-        if verts is not None:
-            scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
         if indices is None:
             indices = self._indices if self._indices is not None else scene_buffers.tris.read(capi.triangle_dtype)["v"]
         if vertex_material is None:
@@ -112,6 +135,10 @@ class ProgressiveSession:
         if self.lbvh is None:
             self.lbvh = capi.Lbvh(self.renderer.dev)
         nodes, tris, info = self.lbvh.build(scene_buffers.verts, indices, vertex_material, max_leaf_size=max_leaf_size)
+        return nodes, tris, info, indices
+
+    def _adopt(self, scene_buffers, nodes, tris, indices):
+        """A freshly built tree takes the place of the bound one: a new binding is a new geometry."""
         old = (scene_buffers.nodes, scene_buffers.tris)
         scene_buffers.nodes, scene_buffers.tris = nodes, tris
         self.renderer.bind_scene(scene_buffers)      # waits for the renderer's stream before it touches anything
@@ -123,6 +150,21 @@ class ProgressiveSession:
         self.camera.reset_accumulation()
         if self.temporal is not None:
             self.temporal.reset()
+
+    def rebuild(self, scene_buffers, verts=None, indices=None, vertex_material=None, max_leaf_size=4):
+        """The geometry changed beyond what a refit covers -- vertices that moved far, or another triangle list (a cut, a spawn, an LOD
+        switch): upload `verts` when given (at most the vertex count the buffer was created with), build an LBVH on the GPU from the
+        device-resident vertices (capi.Lbvh, gmupt_lbvh_build), put its node and triangle buffers into `scene_buffers` (the old ones are
+        closed), bind, restart the accumulation and drop the temporal history: a new binding is a new geometry.
+        indices: (n, 3) int32, numpy or a torch device tensor; None = the list of the last rebuild(), or, before any, the triangle
+        records the scene is bound to (an SBVH's spatial splits then appear as repeated triangles).  vertex_material: per vertex; None =
+        the materialID column of the property records.  Returns the gmupt_lbvh_info dict.  The baseline of
+        set_vertices(rebuild_above=...) is forgotten: the next such call measures the new tree."""
+        if verts is not None:
+            scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
+        nodes, tris, info, indices = self._build_candidate(scene_buffers, indices, vertex_material, max_leaf_size)
+        self._adopt(scene_buffers, nodes, tris, indices)
+        self.baseline = None                         # of the tree that is gone
         return info
 
     def close(self):

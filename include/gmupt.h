@@ -666,6 +666,52 @@ int gmupt_normals_update(gmupt_normals* n, gmupt_normals_info* info /* may be NU
 void gmupt_normals_destroy(gmupt_normals* n);
 int gmupt_buffer_update_device(gmupt_buffer* buf, const void* device_src, size_t bytes);
 
+/* ---- Tree cost: the surface-area cost of a node buffer, measured where the buffer lives (an extension; the reference builds once and
+ * never asks).  It tells a caller whose mesh deforms when the refitted tree has degraded far enough for a rebuild (gmupt_lbvh_build) to
+ * pay: compare `sah` of the refitted tree with `sah` at bind time, and with that of a candidate tree before it is bound.
+ *
+ * The rule, for the N >= 1 records of a GMUPT_BUFFER_BVH_NODES array (gmupt_tree_cost_host and the kernels run the same statements,
+ * csrc/pt_treecost.hpp).  No link is followed: every record counts on its own, so any N records are valid input, a buffer that is not a
+ * tree included.  All arithmetic is IEEE binary64, nothing contracted.
+ *   Extent, per axis:  d = (double)max - (double)min;  e = d > 0 ? d : 0  (a NaN gives 0, so does max < min).
+ *   Half area:         a = (ex*ey + ey*ez) + ez*ex.
+ *   Weight:            inner node (isLeaf == 0): w = 2;  leaf: w = (double)(uint32_t)(right - left), the subtraction done in uint32
+ *                      (right < left wraps).
+ *   Term:              a * w.
+ *   Sums:              sum_inner over the inner nodes, sum_leaf over the leaves; in each a record of the other kind contributes +0.0.
+ *   Order of a sum:    the N terms in record order, padded with +0.0 to a multiple of 256.  Every run of 256 consecutive entries is
+ *                      reduced by stride halving -- for s = 128, 64, .., 1: x[i] = x[i] + x[i+s] for all i < s -- and leaves x[0].  The
+ *                      results, in run order, are the entries of the next level; repeat until one value is left (N <= 256: one level).
+ *                      It is what a block of 256 threads does: s = 128 and 64 across its waves, s = 32 .. 1 inside the first wave.
+ *   Integers:          num_inner, num_leaves; num_refs = the sum of the leaf weights as uint64; max_leaf_refs = the largest leaf weight.
+ *   SAH:               root_half_area = a of record 0;  sah = (sum_inner + sum_leaf) / root_half_area if root_half_area > 0, else 0.0.
+ *                      It is the quantity gmupt_sbvh_sah reports at its default costs (node_cost = tri_cost = 1), from the flattened
+ *                      boxes and in a stated order.
+ *   Infinite extents are no error: a term may be +inf.  Only inf * 0 (an infinite extent next to a flat axis or an empty leaf) gives a
+ *   NaN; the sums are then NaN, and the sign and payload of that NaN are not part of the rule.
+ * gmupt_tree_cost_host: the rule on a host array, no device.  Runs on up to `threads` std::threads (0 -> 1, at most 16); not a bit of the
+ *   result depends on the count.  ms = 0.  n == 0 or a NULL pointer: GMUPT_ERR_INVALID_ARGUMENT, *info untouched.
+ * gmupt_renderer_tree_cost: the rule on device memory.  nodes_or_null == NULL: the node buffer the renderer is bound to, as
+ *   gmupt_renderer_refit keeps it current (GMUPT_ERR_NOT_BOUND without a scene).  Otherwise any GMUPT_BUFFER_BVH_NODES buffer of the
+ *   renderer's device, bound or not -- e.g. the one gmupt_lbvh_build just returned; a scene need not be bound.  Another kind, another
+ *   device, an empty buffer or more than 2^32 - 1 records: GMUPT_ERR_INVALID_ARGUMENT, as are a NULL renderer or info.  No error path
+ *   allocates anything or writes *info.  The launches go on the renderer's stream, behind a preceding gmupt_renderer_refit or gmupt_iterate
+ *   without a host wait: one thread per record, one block per run (k_tc_nodes), then one launch per further level over the partial
+ *   results (k_tc_reduce) -- four launches at 20 M nodes; no float atomics.  Then ONE readback of 48 bytes and a synchronise.  The partial
+ *   results live in scratch of the renderer (48 bytes per 256 records), allocated by the first call, grown when a larger buffer comes and
+ *   kept.  ms = device time of the launches (hipEvents).  Bit for bit the result of gmupt_tree_cost_host on the same records.  The frame,
+ *   path state, queues, counters, statistics, tables and the node buffer are not touched. */
+typedef struct {
+    double sum_inner, sum_leaf;
+    uint32_t num_inner, num_leaves;
+    uint64_t num_refs;
+    uint32_t max_leaf_refs, pad;
+    double root_half_area, sah;
+    double ms;
+} gmupt_tree_cost_info;   /* 64 bytes */
+int gmupt_tree_cost_host(const gmupt_bvh_node* nodes, uint32_t n, gmupt_tree_cost_info* info, uint32_t threads);
+int gmupt_renderer_tree_cost(gmupt_renderer* r, gmupt_buffer* nodes_or_null, gmupt_tree_cost_info* info);
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);
