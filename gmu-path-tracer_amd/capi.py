@@ -171,6 +171,14 @@ class NormalsInfo(C.Structure):
 assert C.sizeof(NormalsInfo) == 24
 
 
+class PoseInfo(C.Structure):
+    """gmupt_pose_info: 16 bytes."""
+    _fields_ = [("num_verts", C.c_uint32), ("active_targets", C.c_uint32), ("ms", C.c_double)]
+
+
+assert C.sizeof(PoseInfo) == 16
+
+
 class TreeCostInfo(C.Structure):
     """gmupt_tree_cost_info: 64 bytes."""
     _fields_ = [("sum_inner", C.c_double), ("sum_leaf", C.c_double), ("num_inner", C.c_uint32), ("num_leaves", C.c_uint32),
@@ -263,6 +271,11 @@ SYMBOLS = {
     "gmupt_buffer_update_device": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_tree_cost_host": (C.c_int, [_P, C.c_uint32, C.POINTER(TreeCostInfo), C.c_uint32]),
     "gmupt_renderer_tree_cost": (C.c_int, [_P, _P, C.POINTER(TreeCostInfo)]),
+    "gmupt_pose_host": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32]),
+    "gmupt_pose_create": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(_P)]),
+    "gmupt_pose_update": (C.c_int, [_P, _P, _P, C.POINTER(PoseInfo)]),
+    "gmupt_pose_update_device": (C.c_int, [_P, _P, _P, C.POINTER(PoseInfo)]),
+    "gmupt_pose_destroy": (None, [_P]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -550,6 +563,7 @@ class Renderer:
         self._scene = None
         self._temporals = []   # history handles of this renderer: closed before it
         self._normals = []     # Normals handles of this renderer: closed before it
+        self._poses = []       # Pose handles of this renderer: closed before it
 
     def bind_scene(self, sb):
         self._scene = sb  # keep the buffers alive
@@ -786,7 +800,7 @@ class Renderer:
 
     def close(self):
         if self.h:
-            for t in self._temporals + self._normals:
+            for t in self._temporals + self._normals + self._poses:
                 t.close()
             lib().gmupt_renderer_destroy(self.h)
             self.h = _P()
@@ -856,6 +870,143 @@ def vertex_normals_host(verts, indices, threads=16):
     indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
     out = np.empty_like(verts)
     _check(lib().gmupt_vertex_normals_host(_ptr(verts), verts.shape[0], _ptr(indices), indices.shape[0], _ptr(out), int(threads)))
+    return out
+
+
+def _rig_arrays(rest, joints, weights, num_joints, deltas):
+    """The arrays of a rig as contiguous numpy arrays of the C-ABI's types (None where the rule ignores them) and V, K, J, T."""
+    rest = np.ascontiguousarray(rest, dtype=np.float32).reshape(-1, 3)
+    V, J = rest.shape[0], int(num_joints)
+    K = 0
+    if J:
+        weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(V, -1) if V else np.zeros((0, 1), np.float32)
+        K = weights.shape[1]
+        joints = np.ascontiguousarray(joints, dtype=np.uint16).reshape(V, K)
+    else:
+        joints = weights = None
+    deltas = None if deltas is None else np.ascontiguousarray(deltas, dtype=np.float32).reshape(-1, V, 3)
+    T = 0 if deltas is None else deltas.shape[0]
+    return rest, joints, weights, (deltas if T else None), V, K, J, T
+
+
+class Pose:
+    """gmupt_pose: the rig of one mesh -- rest positions, skinning influences, dense morph targets -- kept on the GPU, and update(), which
+    writes the posed vertices into the vertex buffer the renderer is bound to (include/gmupt.h "Pose" states the rule).  rest (V, 3)
+    float32, joints (V, K) uint16, weights (V, K) float32, deltas (T, V, 3) float32 or None; each a numpy array (uploaded) or a torch
+    device tensor of that dtype (used in place; the handle keeps its own copies).  num_joints = 0: morph only, joints and weights are
+    ignored.  It uses the renderer's device and stream and is closed with it at the latest."""
+
+    def __init__(self, renderer, rest, joints, weights, num_joints, deltas=None):
+        import torch
+        device = torch.device("cuda", getattr(renderer.dev, "index", 0))
+        J = int(num_joints)
+
+        def dev(a, np_dtype, t_dtype, what):
+            if a is None:
+                return None
+            if isinstance(a, torch.Tensor):
+                if a.device != device or a.dtype != t_dtype:
+                    raise GmuptError("Pose: a %s tensor must be %s on %s" % (what, t_dtype, device), ERR_INVALID_ARGUMENT)
+                return a.contiguous()
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype)).to(device)
+
+        rest = dev(rest, np.float32, torch.float32, "rest")
+        weights = dev(weights, np.float32, torch.float32, "weights") if J else None
+        if J and isinstance(joints, torch.Tensor):
+            if joints.device != device or joints.dtype not in (getattr(torch, "uint16", torch.int16), torch.int16):
+                raise GmuptError("Pose: a joints tensor must be uint16 (or its bits as int16) on %s" % device, ERR_INVALID_ARGUMENT)
+            joints = joints.contiguous()
+        elif J:
+            joints = torch.from_numpy(np.ascontiguousarray(joints, dtype=np.uint16).view(np.int16)).to(device)
+        else:
+            joints = None
+        deltas = dev(deltas, np.float32, torch.float32, "deltas")
+        V = rest.numel() // 3
+        K = (weights.numel() // V if V else 0) if J else 0
+        T = deltas.numel() // (3 * V) if (deltas is not None and V) else 0
+        if J and (weights.numel() != V * K or joints.numel() != V * K):
+            raise GmuptError("Pose: joints and weights must hold the same number of influences for each of the %d vertices" % V, ERR_INVALID_ARGUMENT)
+        if deltas is not None and deltas.numel() != T * V * 3:
+            raise GmuptError("Pose: deltas must hold 3 floats per vertex and target", ERR_INVALID_ARGUMENT)
+        self.renderer = renderer
+        self.num_verts, self.influences, self.num_joints, self.num_targets = V, K, J, T
+        self._device = device
+        self._pending = []     # device tensors of update() calls the stream may not have read yet
+        self.h = _P()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        torch.cuda.current_stream(device).synchronize()
+        _check(lib().gmupt_pose_create(renderer.h, p(rest), p(joints), p(weights), K, J, p(deltas) if T else None, T, C.byref(self.h)))
+        renderer._poses.append(self)
+
+    def update(self, joint_mats, target_weights=None, info=False):
+        """gmupt_pose_update (numpy / host arrays) or gmupt_pose_update_device (joint_mats a torch device tensor; target_weights then a
+        device tensor too, or a host array that is uploaded first) on the renderer's stream.  joint_mats: (J, 12) float32, None for a
+        morph-only rig; target_weights: (T,) float32, None = all zero.  info=False: no host synchronisation, returns None.  info=True:
+        synchronises and returns the gmupt_pose_info fields as a dict (ms = device time of the copies and the two launches).  Device
+        tensors are kept referenced until a synchronising call has shown that the stream is past them."""
+        J, T = self.num_joints, self.num_targets
+        pi = PoseInfo() if info else None
+        on_device = hasattr(joint_mats, "is_cuda") or hasattr(target_weights, "is_cuda")
+        if on_device:
+            import torch
+
+            def dev(a, n, what):
+                if n == 0:
+                    return None
+                if a is None:
+                    return torch.zeros(n, dtype=torch.float32, device=self._device)
+                if not isinstance(a, torch.Tensor):
+                    a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+                if a.dtype != torch.float32 or a.numel() != n:
+                    raise GmuptError("Pose.update: %s must hold %d float32" % (what, n), ERR_INVALID_ARGUMENT)
+                if a.device != self._device:
+                    if a.is_cuda:
+                        raise GmuptError("Pose.update: %s is on %s, the renderer on %s" % (what, a.device, self._device), ERR_INVALID_ARGUMENT)
+                    a = a.to(self._device)
+                return a.contiguous()
+
+            jm, tw = dev(joint_mats, 12 * J, "joint_mats"), dev(target_weights, T, "target_weights")
+            torch.cuda.current_stream(self._device).synchronize()
+            if len(self._pending) >= 64:
+                self.renderer.synchronize(); self._pending.clear()
+            self._pending.append((jm, tw))
+            p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            _check(lib().gmupt_pose_update_device(self.h, p(jm), p(tw), C.byref(pi) if info else None))
+        else:
+            jm = None if J == 0 else np.ascontiguousarray(joint_mats, dtype=np.float32).reshape(-1)
+            tw = None if T == 0 else (np.zeros(T, np.float32) if target_weights is None else np.ascontiguousarray(target_weights, dtype=np.float32).reshape(-1))
+            if (J and jm.size != 12 * J) or (T and tw.size != T):
+                raise GmuptError("Pose.update: %d joints need %d matrix floats, %d targets %d weights" % (J, 12 * J, T, T), ERR_INVALID_ARGUMENT)
+            _check(lib().gmupt_pose_update(self.h, _ptr(jm) if J else None, _ptr(tw) if T else None, C.byref(pi) if info else None))
+        if not info:
+            return None
+        self._pending.clear()                                    # the call has synchronised the stream
+        return {"num_verts": int(pi.num_verts), "active_targets": int(pi.active_targets), "ms": float(pi.ms)}
+
+    def close(self):
+        if self.h:
+            lib().gmupt_pose_destroy(self.h)                     # synchronises the stream
+            self.h = _P()
+            self._pending = []
+            if self in self.renderer._poses:                     # (Renderer.close() walks a copy of the list)
+                self.renderer._poses.remove(self)
+
+
+def pose_host(rest, joints, weights, num_joints, joint_mats, deltas=None, target_weights=None, threads=16):
+    """gmupt_pose_host: the pose rule of include/gmupt.h on the CPU in binary32, bit for bit what Pose.update() writes.  Arrays as for
+    Pose and Pose.update (numpy).  Returns (V, 3) float32."""
+    rest, joints, weights, deltas, V, K, J, T = _rig_arrays(rest, joints, weights, num_joints, deltas)
+    jm = np.ascontiguousarray(joint_mats, dtype=np.float32).reshape(-1) if J else None
+    if J and jm.size != 12 * J:
+        raise GmuptError("pose_host: %d joints need %d matrix floats" % (J, 12 * J), ERR_INVALID_ARGUMENT)
+    tw = None
+    if T:
+        tw = np.zeros(T, np.float32) if target_weights is None else np.ascontiguousarray(target_weights, dtype=np.float32).reshape(-1)
+        if tw.size != T:
+            raise GmuptError("pose_host: %d targets need %d weights" % (T, T), ERR_INVALID_ARGUMENT)
+    out = np.empty_like(rest)
+    p = lambda a: _ptr(a) if a is not None else None
+    _check(lib().gmupt_pose_host(p(rest), V, p(joints), p(weights), K, p(jm), J, p(deltas), p(tw), T, _ptr(out), int(threads)))
     return out
 
 

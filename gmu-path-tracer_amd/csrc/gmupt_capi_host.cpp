@@ -265,6 +265,25 @@ extern "C" int gmupt_tree_cost_host(const gmupt_bvh_node* nodes, uint32_t n, gmu
     return GMUPT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ pose: the host reference (pt_pose.cpp) of gmupt_pose_update
+extern "C" int gmupt_pose_host(const float* rest, uint32_t num_verts, const uint16_t* joints, const float* weights, uint32_t influences, const float* joint_mats,
+                               uint32_t num_joints, const float* deltas, const float* target_weights, uint32_t num_targets, float* verts_out, uint32_t threads)
+{
+    if (!rest || !verts_out || num_verts == 0) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pose_host: null or empty array");
+    if (num_joints == 0 && num_targets == 0) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pose_host: neither joints nor morph targets");
+    if (num_joints > kPsMaxJoints || num_targets > kPsMaxTargets)
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pose_host: %u joints (at most %u), %u targets (at most %u)", num_joints, kPsMaxJoints, num_targets, kPsMaxTargets);
+    if (num_joints && (influences < 1 || influences > kPsMaxInfluences)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pose_host: influences = %u (1..%u)", influences, kPsMaxInfluences);
+    if (num_joints && (!joints || !weights || !joint_mats)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pose_host: %u joints without joint numbers, weights or matrices", num_joints);
+    if (num_targets && (!deltas || !target_weights)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pose_host: %u targets without deltas or weights", num_targets);
+    if (num_joints) {
+        const size_t bad = pose_first_bad_joint(joints, weights, influences, num_joints, num_verts);
+        if (bad < num_verts) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pose_host: an influence of vertex %zu with a weight that is not zero names a joint outside the %u joints", bad, num_joints);
+    }
+    pose_host(rest, num_verts, joints, weights, influences, joint_mats, num_joints, deltas, target_weights, num_targets, verts_out, clamp_threads(threads));
+    return GMUPT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ host: SBVH
 extern "C" void gmupt_sbvh_default_params(gmupt_sbvh_params* p)
 {

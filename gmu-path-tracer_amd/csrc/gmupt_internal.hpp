@@ -9,6 +9,7 @@
 #include "pt_lbvh.hpp"                // and with it pt_refit.hpp, pt_device.hpp, detmath.hpp
 #include "pt_normals.hpp"
 #include "pt_treecost.hpp"
+#include "pt_pose.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
@@ -59,6 +60,15 @@ struct DevMem {
         *this = std::move(m);
         return GMUPT_OK;
     }
+};
+
+// Pinned host memory of one handle (the staging area of a small per-call upload), freed with it
+struct PinnedMem {
+    void* ptr = nullptr; size_t bytes = 0; PinnedMem() = default;
+    PinnedMem(const PinnedMem&) = delete; PinnedMem& operator=(const PinnedMem&) = delete;
+    ~PinnedMem() { if (ptr) (void)hipHostFree(ptr); }
+    template <class T> T* as() const { return static_cast<T*>(ptr); }
+    int alloc(size_t n) { HIP_TRY(hipHostMalloc(&ptr, n ? n : 16, hipHostMallocDefault)); bytes = n ? n : 16; return GMUPT_OK; }
 };
 
 // N events of one handle, created on first use and destroyed with it
@@ -161,6 +171,16 @@ struct gmupt_normals {
     gmupt_renderer* r = nullptr;
     uint32_t numVerts = 0, numTris = 0, maxValence = 0;
     DevMem mem; NmLayout off{};
+    EventPair ev;
+};
+
+// the rig of one mesh for a renderer's vertices (gmupt_pose_*): device memory laid out by pose_layout (pt_pose.hip), and the pinned
+// staging area of gmupt_pose_update with the event that tells when the stream has read it
+struct gmupt_pose {
+    gmupt_renderer* r = nullptr;
+    uint32_t numVerts = 0, influences = 0, numJoints = 0, numTargets = 0;
+    DevMem mem; PsLayout off{};
+    PinnedMem staging; DevEvents<1> staged; bool stagingBusy = false;
     EventPair ev;
 };
 

@@ -1,14 +1,14 @@
 // Host-side entry points of the kernel files and of the host workers next to them, as the C-API units (gmupt_capi*.hip) call them.
 // Every file that defines one of these includes this header, so that the compiler checks the definition against the declaration
 // (lbvh_build_host of pt_lbvh.cpp is declared in pt_lbvh.hpp, normals_host of pt_normals.cpp in pt_normals.hpp, tree_cost_host of
-// pt_treecost.cpp in pt_treecost.hpp).
+// pt_treecost.cpp in pt_treecost.hpp, pose_host of pt_pose.cpp in pt_pose.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "../../include/gmupt.h"
 
 namespace gmupt {
-struct RenderParams; struct SceneView; struct DnParams; struct TpParams; struct TpPrev; struct RfArgs; struct LbScratch; struct LbStaging; struct NmLayout; struct NmArgs; struct TcPartial;   // pt_*.hpp
+struct RenderParams; struct SceneView; struct DnParams; struct TpParams; struct TpPrev; struct RfArgs; struct LbScratch; struct LbStaging; struct NmLayout; struct NmArgs; struct TcPartial; struct PsLayout; struct PsArgs;   // pt_*.hpp
 
 void launch_clear(const RenderParams& p, hipStream_t s);
 void launch_logic(const RenderParams& p, hipStream_t s);
@@ -53,6 +53,9 @@ hipError_t normals_sort_temp_bytes(uint32_t numTris, uint32_t numVerts, size_t* 
 NmLayout normals_layout(uint32_t numTris, uint32_t numVerts, size_t sortTemp);
 hipError_t launch_normals_create(const NmArgs& a, void* sortTemp, size_t sortTempBytes, hipStream_t s);
 void launch_normals_update(const NmArgs& a, hipStream_t s);
+PsLayout pose_layout(uint32_t numVerts, uint32_t influences, uint32_t numJoints, uint32_t numTargets);
+hipError_t launch_pose_create(const PsArgs& a, hipStream_t s);
+void launch_pose_update(const PsArgs& a, hipStream_t s);
 size_t tree_cost_scratch_partials(uint32_t n);
 const TcPartial* launch_tree_cost(const gmupt_bvh_node* nodes, uint32_t n, TcPartial* scratch, hipStream_t s);
 }

@@ -53,6 +53,7 @@ void Renderer::createBuffers(Resolution res)
 void Renderer::initScene(const std::string& name)
 {
 	mNormals.reset();
+	mPose.reset();
 	mScene = Scene(mDevice.get(), name); // old resources die with the temporary (Source/Renderer.cpp:55)
 	mScene.mHipDevice = mHipDevice;
 	mScene.mCamera.getBuffer()->lightCount = static_cast<uint32_t>(mScene.lightCount() < 2 ? 2 : mScene.lightCount()); // Camera.hpp:20: never below the default 2
@@ -215,6 +216,36 @@ gmupt_refit_info Renderer::refitScene(bool keepHistory, bool smoothNormals)
 	mScene.mCamera.getBuffer()->iterationCounter = -1; // paths in flight carry hits of the old geometry
 	if (!keepHistory) resetHistory();
 	return info;
+}
+
+gmupt_refit_info Renderer::poseScene(const std::vector<float>& jointMats, const std::vector<float>& targetWeights, bool keepHistory, bool smoothNormals)
+{
+	const Scene::Rig* rig = mScene.rig();
+	if (!rig) throw std::runtime_error("poseScene: the scene has no rig (Scene::loadRig)");
+	if (jointMats.size() != 12 * static_cast<size_t>(rig->numJoints) || targetWeights.size() != rig->numTargets)
+		throw std::runtime_error("poseScene: " + std::to_string(jointMats.size()) + " matrix floats and " + std::to_string(targetWeights.size()) + " target weights for a rig of " +
+		                         std::to_string(rig->numJoints) + " joints and " + std::to_string(rig->numTargets) + " targets");
+	bindScene(); // (the scene is bound on first use, as in refitScene)
+	if (!mPose)
+	{
+		if (hipSetDevice(mHipDevice) != hipSuccess) throw std::runtime_error("poseScene: cannot select the device");
+		auto upload = [](const void* src, size_t bytes) {
+			void* d = nullptr;
+			if (bytes == 0) return DeviceMemory(nullptr);
+			if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("poseScene: cannot allocate the rig on the device");
+			DeviceMemory mem(d);
+			if (hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("poseScene: cannot upload the rig");
+			return mem;
+		};
+		const DeviceMemory rest = upload(rig->rest.data(), rig->rest.size() * sizeof(float)), joints = upload(rig->joints.data(), rig->joints.size() * sizeof(uint16_t));
+		const DeviceMemory weights = upload(rig->weights.data(), rig->weights.size() * sizeof(float)), deltas = upload(rig->deltas.data(), rig->deltas.size() * sizeof(float));
+		gmupt_pose* p = nullptr;
+		check(gmupt_pose_create(mRenderer.get(), static_cast<const float*>(rest.get()), static_cast<const uint16_t*>(joints.get()), static_cast<const float*>(weights.get()),
+		                        rig->influences, rig->numJoints, static_cast<const float*>(deltas.get()), rig->numTargets, &p));
+		mPose.reset(p);
+	}
+	check(gmupt_pose_update(mPose.get(), jointMats.empty() ? nullptr : jointMats.data(), targetWeights.empty() ? nullptr : targetWeights.data(), nullptr));
+	return refitScene(keepHistory, smoothNormals);
 }
 
 gmupt_tree_cost_info Renderer::treeCost()

@@ -73,6 +73,11 @@ public:
 	// "normals") through this renderer's own handle, built on first use from the scene's index list and dropped by rebuildScene / initScene.
 	// Throws like the other wrappers.
 	gmupt_refit_info refitScene(bool keepHistory = false, bool smoothNormals = false);
+	// after Scene::loadRig: the mesh posed on the GPU (gmupt_pose_update, include/gmupt.h "Pose") from jointMats (12 floats per joint of the
+	// rig) and targetWeights (one per morph target) straight into the vertex buffer, then refitScene(keepHistory, smoothNormals).  The handle
+	// is this renderer's own, built on first use from the scene's rig and dropped by initScene.  The posed vertices are never read back:
+	// MeshData::vertices keeps the last host-given positions.  Throws std::runtime_error without a rig or on a wrong count.
+	gmupt_refit_info poseScene(const std::vector<float>& jointMats, const std::vector<float>& targetWeights, bool keepHistory = false, bool smoothNormals = false);
 	// the surface-area cost of the bound tree, measured on the GPU on the renderer's stream (gmupt_renderer_tree_cost, include/gmupt.h
 	// "Tree cost"): after a refitScene it tells how far the refitted tree has degraded against its value at bind time, i.e. when
 	// rebuildScene pays.  Binds the scene on first use; touches neither the frame nor the accumulation.
@@ -93,12 +98,14 @@ private:
 	struct RendererDeleter { void operator()(gmupt_renderer* r) const { gmupt_renderer_destroy(r); } };
 	struct TemporalDeleter { void operator()(gmupt_temporal* t) const { gmupt_temporal_destroy(t); } };
 	struct NormalsDeleter { void operator()(gmupt_normals* n) const { gmupt_normals_destroy(n); } };
+	struct PoseDeleter { void operator()(gmupt_pose* p) const { gmupt_pose_destroy(p); } };
 
 	void* mHwnd;
 	std::unique_ptr<gmupt_device, DeviceDeleter> mDevice;
 	std::unique_ptr<gmupt_renderer, RendererDeleter> mRenderer; // path state, queues, counters, accumulation target
 	std::unique_ptr<gmupt_temporal, TemporalDeleter> mTemporal; // history of denoiseTemporal (declared after mRenderer: destroyed before it)
 	std::unique_ptr<gmupt_normals, NormalsDeleter> mNormals;    // adjacency of refitScene(.., smoothNormals) (declared after mRenderer: destroyed before it)
+	std::unique_ptr<gmupt_pose, PoseDeleter> mPose;             // the rig of poseScene on the device (declared after mRenderer: destroyed before it)
 	Scene mScene;
 	Resolution mResolution;
 	RowBand mBand;

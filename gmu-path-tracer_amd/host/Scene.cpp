@@ -1,4 +1,6 @@
 #include "Scene.hpp"
+#include <cstdio>
+#include <cstring>
 #include <stdexcept>
 #include <thread>
 #include <hip/hip_runtime_api.h>
@@ -147,6 +149,31 @@ void Scene::setVertices(const std::vector<float>& xyz, const std::vector<float>*
 		check(gmupt_buffer_update(mTriangleProperties.get(), props.data(), props.size() * sizeof(gmupt_tri_props)));
 		mScene.normals = *normals;
 	}
+}
+
+void Scene::loadRig(const std::string& path)
+{
+	std::FILE* f = std::fopen(path.c_str(), "rb");
+	if (!f) throw std::runtime_error("loadRig: cannot read " + path);
+	std::unique_ptr<std::FILE, int (*)(std::FILE*)> closer(f, &std::fclose);
+	char magic[4]; uint32_t head[5];
+	if (std::fread(magic, 1, 4, f) != 4 || std::memcmp(magic, "GRIG", 4) != 0 || std::fread(head, 4, 5, f) != 5) throw std::runtime_error("loadRig: " + path + " is no .grig file");
+	if (head[0] != 1) throw std::runtime_error("loadRig: " + path + " has version " + std::to_string(head[0]) + ", this build reads 1");
+	std::unique_ptr<Rig> rig(new Rig());
+	rig->numVerts = head[1]; rig->influences = head[2]; rig->numJoints = head[3]; rig->numTargets = head[4];
+	if (rig->numVerts != mScene.numVertices()) throw std::runtime_error("loadRig: a rig of " + std::to_string(rig->numVerts) + " vertices for a mesh of " + std::to_string(mScene.numVertices()));
+	if (rig->numJoints > 65535 || rig->numTargets > 256 || (rig->numJoints == 0 && rig->numTargets == 0) || (rig->numJoints && (rig->influences < 1 || rig->influences > 8)))
+		throw std::runtime_error("loadRig: " + std::to_string(rig->numJoints) + " joints, " + std::to_string(rig->influences) + " influences, " + std::to_string(rig->numTargets) + " targets are outside the limits of the pose rule");
+	const size_t V = rig->numVerts, VK = rig->numJoints ? V * rig->influences : 0;
+	rig->rest.resize(3 * V); rig->joints.resize(VK); rig->weights.resize(VK); rig->deltas.resize(3 * V * rig->numTargets);
+	auto take = [&](void* dst, size_t size, size_t count) { if (count && std::fread(dst, size, count, f) != count) throw std::runtime_error("loadRig: " + path + " is shorter than its header says"); };
+	take(rig->rest.data(), 4, rig->rest.size()); take(rig->joints.data(), 2, VK); take(rig->weights.data(), 4, VK); take(rig->deltas.data(), 4, rig->deltas.size());
+	if (std::fgetc(f) != EOF) throw std::runtime_error("loadRig: " + path + " is longer than its header says");
+	for (size_t i = 0; i < VK; i++) // rule 4 of the pose rule, here so that the message names the file
+		if (rig->weights[i] != 0.0f && rig->joints[i] >= rig->numJoints)
+			throw std::runtime_error("loadRig: " + path + ": influence " + std::to_string(i % rig->influences) + " of vertex " + std::to_string(i / rig->influences) + " has a weight that is not zero and names joint " +
+			                         std::to_string(rig->joints[i]) + " of " + std::to_string(rig->numJoints));
+	mRig = std::move(rig);
 }
 
 gmupt_lbvh_info Scene::rebuildOnDevice(unsigned maxLeafSize, const std::vector<int32_t>* indices)

@@ -78,6 +78,19 @@ public:
 	// Renderer::rebuildScene(), which does.  Throws std::runtime_error (a bad index, a non-finite used vertex, ...) and then keeps the tree, the buffers and the mesh's
 	// triangle list as they were (only the internal device copy of the index list may hold the refused one; the next call uploads again).
 	gmupt_lbvh_info rebuildOnDevice(unsigned maxLeafSize = 4, const std::vector<int32_t>* indices = nullptr);
+	// the rig of the loaded mesh (an extension; include/gmupt.h "Pose"): a ".grig" file -- "GRIG", then version (1), num_verts, influences,
+	// num_joints, num_targets as little-endian uint32, then the arrays in the order of gmupt_pose_create: rest (3 floats per vertex), joints
+	// (uint16) and weights (float), `influences` per vertex each and absent when num_joints is 0, deltas (3 floats per vertex and target).
+	// Throws std::runtime_error on a file that is not one, a vertex count other than the mesh's, counts outside the rule's limits, a
+	// length that does not match or a joint number outside the rig's joints behind a weight that is not zero.  Renderer::poseScene poses with it.
+	struct Rig
+	{
+		uint32_t numVerts = 0, influences = 0, numJoints = 0, numTargets = 0;
+		std::vector<float> rest, weights, deltas;
+		std::vector<uint16_t> joints;
+	};
+	void loadRig(const std::string& path);
+	const Rig* rig() const { return mRig.get(); }
 
 private:
 	void loadScene(const std::string& path);
@@ -106,6 +119,7 @@ private:
 	size_t mDeviceIndexCapacity = 0;
 	int mHipDevice = -1;                          // set by the Renderer that owns the scene: the device of rebuildOnDevice's own allocations
 	Buffer mRetiredBVHBuffer, mRetiredIndexBuffer;
+	std::unique_ptr<Rig> mRig;                    // loadRig
 
 	std::array<Light, MAX_LIGHTS> mLights{};
 	size_t mLightCount = 0;

@@ -19,6 +19,10 @@
 //                                                         refit info; not with --ranks
 //                [--smooth-normals]                       with --vertices: smooth vertex normals recomputed on the GPU from the moved vertices before
 //                                                         the refit (Renderer::refitScene(.., smoothNormals = true))
+//                [--rig FILE --pose FILE]                 before the frames: the mesh posed on the GPU (Scene::loadRig + Renderer::poseScene): --rig a ".grig" rig
+//                                                         of the scene's vertex count, --pose raw little-endian float32, 12 per joint of the rig, then
+//                                                         one weight per morph target; one JSON line with the refit info.  --smooth-normals and
+//                                                         --temporal act as with --vertices; not with --vertices, not with --ranks
 //                [--tree-cost]                            the surface-area cost of the bound tree (Renderer::treeCost), once after bind and once more
 //                                                         after --vertices is applied: one JSON line each with the gmupt_tree_cost_info fields, the
 //                                                         doubles as hex bit patterns; not with --ranks
@@ -79,6 +83,16 @@ void writeAovPfm(const std::string& path, const std::vector<gmupt_aov>& aov, uns
 	}
 	std::fclose(f);
 }
+std::vector<float> readFloats(const std::string& path)   // a raw float32 file
+{
+	std::FILE* f = std::fopen(path.c_str(), "rb");
+	if (!f) throw std::runtime_error("cannot read " + path);
+	std::vector<float> v;
+	float chunk[3072];
+	for (size_t n; (n = std::fread(chunk, sizeof(float), 3072, f)) > 0;) v.insert(v.end(), chunk, chunk + n);
+	std::fclose(f);
+	return v;
+}
 // the gmupt_tree_cost_info fields as one JSON line; the doubles as the hex bit patterns of their binary64 values (ms as a decimal: it is a time)
 void printTreeCost(const char* when, const gmupt_tree_cost_info& c)
 {
@@ -100,6 +114,7 @@ int main(int argc, char** argv)
 	std::string paramsOnly, rendezvous;
 	bool doPick = false; float pickX = 0.f, pickY = 0.f;
 	std::string verticesFile; bool smoothNormals = false;
+	std::string rigFile, poseFile;
 	std::string aovPrefix; unsigned aovSamples = 1;
 	std::string denoisePrefix;
 	std::string temporalPrefix;
@@ -131,6 +146,8 @@ int main(int argc, char** argv)
 		else if (a == "--denoise") denoisePrefix = next();
 		else if (a == "--vertices") verticesFile = next();
 		else if (a == "--smooth-normals") smoothNormals = true;
+		else if (a == "--rig") rigFile = next();
+		else if (a == "--pose") poseFile = next();
 		else if (a == "--temporal") temporalPrefix = next();
 		else if (a == "--builder") { builder = next(); if (builder != "sbvh" && builder != "lbvh") { std::fprintf(stderr, "--builder takes sbvh or lbvh\n"); return 2; } }
 		else if (a == "--leaf") { char* end = nullptr; const char* v = next(); leaf = std::strtoul(v, &end, 10); if (end == v || *end || leaf < 1 || leaf > 64) { std::fprintf(stderr, "--leaf takes a number in 1..64\n"); return 2; } }
@@ -148,6 +165,8 @@ int main(int argc, char** argv)
 			            "                                 then on the moved one, and the preview keeps its history across the refit (Renderer::denoiseTemporalMotion)\n"
 			            "             [--vertices FILE]   before the frames: moved positions of all vertices (raw float32 xyz), refitted on the GPU; not with --ranks\n"
 			            "             [--smooth-normals]  with --vertices: smooth vertex normals recomputed on the GPU from the moved vertices before the refit\n"
+			            "             [--rig FILE --pose FILE]   before the frames: the mesh posed on the GPU from a .grig rig and a pose (raw float32: 12 per joint, then one\n"
+			            "                                 weight per morph target), then refitted; --smooth-normals and --temporal as with --vertices; not with --vertices or --ranks\n"
 			            "             [--tree-cost]       the surface-area cost of the bound tree, measured on the GPU, after bind and again after --vertices is applied:\n"
 			            "                                 one JSON line each, the doubles as hex bit patterns; not with --ranks\n"
 			            "             [--builder sbvh|lbvh [--leaf L]]   lbvh: the tree rebuilt on the GPU before the frames (linear BVH, leaves of at most L triangles,\n"
@@ -234,8 +253,16 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--denoise filters the frame of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
 		if (!verticesFile.empty() && ranks > 1)
 			throw std::invalid_argument("--vertices moves the geometry of a single process: it cannot be combined with --ranks N > 1");
-		if (smoothNormals && verticesFile.empty())
-			throw std::invalid_argument("--smooth-normals recomputes the normals of moved vertices: it needs --vertices FILE");
+		if (!poseFile.empty() && rigFile.empty())
+			throw std::invalid_argument("--pose holds the matrices and weights of a rig: it needs --rig FILE");
+		if (!rigFile.empty() && poseFile.empty())
+			throw std::invalid_argument("--rig loads a rig to pose: it needs --pose FILE");
+		if (!poseFile.empty() && !verticesFile.empty())
+			throw std::invalid_argument("--pose computes the vertices on the GPU, --vertices uploads them: give one of the two");
+		if (!poseFile.empty() && ranks > 1)
+			throw std::invalid_argument("--pose moves the geometry of a single process: it cannot be combined with --ranks N > 1");
+		if (smoothNormals && verticesFile.empty() && poseFile.empty())
+			throw std::invalid_argument("--smooth-normals recomputes the normals of moved vertices: it needs --vertices FILE or --rig FILE --pose FILE");
 		if (treeCost && ranks > 1)
 			throw std::invalid_argument("--tree-cost measures the tree of a single process: it cannot be combined with --ranks N > 1");
 		if (builder == "lbvh" && ranks > 1)
@@ -268,21 +295,28 @@ int main(int argc, char** argv)
 		}
 		Renderer renderer(nullptr, { w, h }, scene, 0, pool, live);
 		if (treeCost) printTreeCost("bind", renderer.treeCost());
-		if (!verticesFile.empty() && !temporalPrefix.empty()) {   // the history of the loaded pose, which the preview after the refit follows
+		if ((!verticesFile.empty() || !poseFile.empty()) && !temporalPrefix.empty()) {   // the history of the loaded pose, which the preview after the refit follows
 			for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
 			renderer.denoiseTemporalMotion(aovSamples);
 		}
 		if (!verticesFile.empty()) {
-			std::FILE* f = std::fopen(verticesFile.c_str(), "rb");
-			if (!f) throw std::runtime_error("cannot read " + verticesFile);
-			std::vector<float> xyz;
-			float chunk[3072];
-			for (size_t n; (n = std::fread(chunk, sizeof(float), 3072, f)) > 0;) xyz.insert(xyz.end(), chunk, chunk + n);
-			std::fclose(f);
-			renderer.scene().setVertices(xyz);
+			renderer.scene().setVertices(readFloats(verticesFile));
 			const gmupt_refit_info info = renderer.refitScene(!temporalPrefix.empty(), smoothNormals);
 			std::printf("{\"refit\": {\"rebuilt\": %u, \"reason\": %u, \"levels\": %u, \"opened_nodes\": %u, \"ms\": %.6g}}\n", info.rebuilt, info.reason, info.levels, info.opened_nodes, info.ms);
 			if (treeCost) printTreeCost("vertices", renderer.treeCost());
+		}
+		if (!poseFile.empty()) {
+			renderer.scene().loadRig(rigFile);
+			std::vector<float> pose = readFloats(poseFile);
+			const Scene::Rig& rig = *renderer.scene().rig();
+			const size_t matFloats = 12 * static_cast<size_t>(rig.numJoints);
+			if (pose.size() != matFloats + rig.numTargets)
+				throw std::runtime_error(poseFile + " holds " + std::to_string(pose.size()) + " floats, the rig needs " + std::to_string(matFloats) + " + " + std::to_string(rig.numTargets));
+			const std::vector<float> targetWeights(pose.begin() + static_cast<std::ptrdiff_t>(matFloats), pose.end());
+			pose.resize(matFloats);
+			const gmupt_refit_info info = renderer.poseScene(pose, targetWeights, !temporalPrefix.empty(), smoothNormals);
+			std::printf("{\"refit\": {\"rebuilt\": %u, \"reason\": %u, \"levels\": %u, \"opened_nodes\": %u, \"ms\": %.6g}}\n", info.rebuilt, info.reason, info.levels, info.opened_nodes, info.ms);
+			if (treeCost) printTreeCost("pose", renderer.treeCost());
 		}
 		if (builder == "lbvh") {
 			const gmupt_lbvh_info info = renderer.rebuildScene(leaf);

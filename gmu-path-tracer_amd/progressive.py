@@ -72,20 +72,40 @@ class ProgressiveSession:
         A baseline of 0 (a root without area) never triggers.  The returned dict then also holds cost, baseline (the value the
         decision was made against), candidate_cost (None when none was built) and tree_rebuilt.  There is no default threshold:
         DESIGN.md "Tree cost" has the measurements."""
-        smooth = isinstance(normals, str)
-        if smooth and normals != "smooth":
-            raise ValueError("set_vertices: normals=%r (None, an array or \"smooth\")" % (normals,))
-        if rebuild_above is not None:
-            rebuild_above = float(rebuild_above)
-            if not rebuild_above > 1.0:
-                raise ValueError("set_vertices: rebuild_above=%r (None or a float > 1)" % (rebuild_above,))
-            if self.baseline is None:
-                self.baseline = self.renderer.tree_cost()["sah"]
+        rebuild_above = self._moved_args("set_vertices", normals, rebuild_above)
         if hasattr(verts, "is_cuda"):
             scene_buffers.verts.update_from_device(verts)
         else:
             scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
-        if smooth:
+        return self._after_vertices(scene_buffers, normals, keep_history, indices, rebuild_above)
+
+    def set_pose(self, scene_buffers, pose, joint_mats, target_weights=None, normals=None, keep_history=False, indices=None, rebuild_above=None):
+        """The geometry moved because its rig did: pose.update(joint_mats, target_weights) (capi.Pose: skinning and morph targets on the
+        GPU, a few kilobytes of input, no vertex array crosses the bus) writes the vertex buffer the renderer is bound to, then exactly
+        what set_vertices does after its upload -- normals, refit, accumulation restart, history, the rebuild policy; the baseline of
+        rebuild_above is taken before the pose.  The other arguments and the returned dict are set_vertices'.  joint_mats /
+        target_weights: numpy arrays or torch device tensors.  The session does not own `pose`: a rebuild() that keeps the vertex count
+        keeps it valid, and closing it is the caller's business (the renderer closes it at the latest)."""
+        rebuild_above = self._moved_args("set_pose", normals, rebuild_above)
+        pose.update(joint_mats, target_weights)
+        return self._after_vertices(scene_buffers, normals, keep_history, indices, rebuild_above)
+
+    def _moved_args(self, who, normals, rebuild_above):
+        """The argument checks set_vertices and set_pose share, and the baseline of the rebuild policy, measured before the vertices
+        change; returns rebuild_above as a float or None."""
+        if isinstance(normals, str) and normals != "smooth":
+            raise ValueError("%s: normals=%r (None, an array or \"smooth\")" % (who, normals))
+        if rebuild_above is not None:
+            rebuild_above = float(rebuild_above)
+            if not rebuild_above > 1.0:
+                raise ValueError("%s: rebuild_above=%r (None or a float > 1)" % (who, rebuild_above))
+            if self.baseline is None:
+                self.baseline = self.renderer.tree_cost()["sah"]
+        return rebuild_above
+
+    def _after_vertices(self, scene_buffers, normals, keep_history, indices, rebuild_above):
+        """What follows new contents of the bound vertex buffer (set_vertices documents it): normals, refit, restart, history, policy."""
+        if isinstance(normals, str):
             from . import capi
             if indices is not None and self.normals is not None:
                 self.normals.close(); self.normals = None

@@ -305,6 +305,102 @@ def refit_scene(scene, verts, normals=None):
     return out
 
 
+def make_rig(mesh, num_joints=4, influences=4, num_targets=2, seed=0):
+    """A deterministic synthetic rig for any mesh or scene dict (capi.Pose, include/gmupt.h "Pose"): `num_joints` bones spaced evenly along
+    the mesh's longest axis; per vertex the `influences` nearest bones with weights that fall off with the distance along that axis,
+    normalised in float32 (more influences than joints: the spare ones have weight 0 and joint 0); `num_targets` morph targets, each a
+    smooth bump around a centre drawn from `seed`, pushing along a drawn direction.  Returns a dict: rest (V, 3) float32, joints (V, K)
+    uint16, weights (V, K) float32, deltas (T, V, 3) float32, num_joints, and what rig_pose needs (axis, pivots, extent)."""
+    rest = np.ascontiguousarray(mesh["verts"], np.float32).reshape(-1, 3)
+    V, J, K, T = rest.shape[0], int(num_joints), int(influences), int(num_targets)
+    x = rest.astype(np.float64)
+    lo, hi = x.min(axis=0), x.max(axis=0)
+    axis = int(np.argmax(hi - lo))
+    extent = float(max((hi - lo).max(), 1e-30))
+    rig = {"rest": rest, "num_joints": J, "axis": axis, "extent": extent, "lo": lo, "hi": hi}
+    if J:
+        along = lo[axis] + (np.arange(J) + 0.5) * (hi[axis] - lo[axis]) / J
+        pivots = np.tile((lo + hi) * 0.5, (J, 1)); pivots[:, axis] = along
+        dist = np.abs(x[:, axis:axis + 1] - along[None, :])                      # (V, J)
+        order = np.argsort(dist, axis=1, kind="stable")[:, :K]
+        fall = 1.0 / (1.0 + (np.take_along_axis(dist, order, axis=1) * (2.0 * J / extent)) ** 2)
+        joints = np.zeros((V, K), np.uint16); weights = np.zeros((V, K), np.float32)
+        n = order.shape[1]
+        joints[:, :n] = order
+        w = fall.astype(np.float32)
+        weights[:, :n] = w / w.sum(axis=1, dtype=np.float32, keepdims=True)
+        rig.update({"joints": joints, "weights": weights, "pivots": pivots})
+    else:
+        rig.update({"joints": None, "weights": None, "pivots": np.zeros((0, 3))})
+    rng = np.random.default_rng(977 + int(seed))
+    deltas = np.zeros((T, V, 3), np.float32)
+    for t in range(T):
+        centre = lo + rng.uniform(0.2, 0.8, 3) * (hi - lo)
+        direction = rng.normal(size=3); direction /= np.linalg.norm(direction)
+        bump = np.exp(-np.sum((x - centre) ** 2, axis=1) / (0.3 * extent) ** 2)
+        deltas[t] = (bump[:, None] * direction[None, :] * (0.08 * extent)).astype(np.float32)
+    rig["deltas"] = deltas
+    return rig
+
+
+def rig_pose(rig, phase):
+    """A pose of a make_rig rig: (joint_mats (J, 12) float32, target_weights (T,) float32).  Joint j turns about its pivot around an axis
+    across the bones by an angle that swings with `phase` (period 1) and grows along the chain, with a small shift; target t's weight
+    swings between 0 and 1, and is exactly 0 at phase 0, where every matrix is the identity."""
+    J, T = rig["num_joints"], rig["deltas"].shape[0]
+    turn = 2.0 * np.pi * float(phase)
+    mats = np.zeros((J, 12), np.float32)
+    a, b = (rig["axis"] + 1) % 3, (rig["axis"] + 2) % 3                         # the rotation is about axis b, in the plane (axis, a)
+    for j in range(J):
+        ang = 0.25 * np.sin(turn) * (j + 1) / max(J, 1)
+        rot = np.eye(3); c, s = np.cos(ang), np.sin(ang)
+        rot[rig["axis"], rig["axis"]] = c; rot[rig["axis"], a] = -s; rot[a, rig["axis"]] = s; rot[a, a] = c
+        shift = np.zeros(3); shift[b] = 0.02 * rig["extent"] * np.sin(turn) * np.cos(j)
+        p = rig["pivots"][j]
+        m = np.concatenate([rot, (p - rot @ p + shift)[:, None]], axis=1)         # x -> rot (x - p) + p + shift
+        mats[j] = m.reshape(12).astype(np.float32)
+    tw = np.array([0.5 - 0.5 * np.cos(turn * (t + 1)) for t in range(T)], np.float32)
+    return mats, tw
+
+
+def save_grig(rig, path):
+    """Writes the ".grig" rig file host/Scene.cpp reads (INTEGRATION.md has the format): "GRIG", version 1, num_verts, influences,
+    num_joints, num_targets as little-endian uint32, then rest, joints, weights, deltas in the order of gmupt_pose_create."""
+    V, J, T = rig["rest"].shape[0], int(rig["num_joints"]), rig["deltas"].shape[0]
+    K = rig["joints"].shape[1] if J else 0
+    with open(path, "wb") as f:
+        f.write(b"GRIG")
+        f.write(np.array([1, V, K, J, T], "<u4").tobytes())
+        f.write(np.ascontiguousarray(rig["rest"], "<f4").tobytes())
+        if J:
+            f.write(np.ascontiguousarray(rig["joints"], "<u2").tobytes())
+            f.write(np.ascontiguousarray(rig["weights"], "<f4").tobytes())
+        f.write(np.ascontiguousarray(rig["deltas"], "<f4").tobytes())
+
+
+def load_grig(path):
+    """Reads a ".grig" file as the arrays of a rig dict: rest, joints, weights (None without joints), deltas, num_joints."""
+    raw = open(path, "rb").read()
+    if raw[:4] != b"GRIG":
+        raise ValueError("load_grig: %s is no .grig file" % path)
+    version, V, K, J, T = (int(x) for x in np.frombuffer(raw, "<u4", 5, 4))
+    if version != 1:
+        raise ValueError("load_grig: version %d" % version)
+    off = 24
+    def take(dtype, count):
+        nonlocal off
+        a = np.frombuffer(raw, dtype, count, off).copy()
+        off += a.nbytes
+        return a
+    rig = {"num_joints": J, "rest": take("<f4", V * 3).reshape(V, 3)}
+    rig["joints"] = take("<u2", V * K).reshape(V, K) if J else None
+    rig["weights"] = take("<f4", V * K).reshape(V, K) if J else None
+    rig["deltas"] = take("<f4", T * V * 3).reshape(T, V, 3)
+    if off != len(raw):
+        raise ValueError("load_grig: %d bytes for a file of %d" % (len(raw), off))
+    return rig
+
+
 def save_gmesh(mesh, path, params_path=None):
     """Writes the ".gmesh" dump host/MeshData.cpp reads, and optionally the sibling ".params" CSV in the reference's format
     (row 0: camera x,y,z,pitch,yaw; rows 1..: light x,y,z,falloff,r,g,b,radius -- Source/Scene.cpp:34-55)."""

@@ -712,6 +712,67 @@ typedef struct {
 int gmupt_tree_cost_host(const gmupt_bvh_node* nodes, uint32_t n, gmupt_tree_cost_info* info, uint32_t threads);
 int gmupt_renderer_tree_cost(gmupt_renderer* r, gmupt_buffer* nodes_or_null, gmupt_tree_cost_info* info);
 
+/* ---- Pose: linear-blend skinning and dense morph targets on the GPU (an extension; the reference's meshes never move).  It produces what
+ * gmupt_normals_update, gmupt_renderer_refit and the motion-aware history start from -- "the vertex buffer holds the new pose" -- from a
+ * few kilobytes per frame (joint matrices, target weights) instead of a vertex array.
+ *
+ * The rule (binary32, nothing contracted; gmupt_pose_host and the kernel run the same statements, csrc/pt_pose.hpp).  Input:
+ *   num_verts rest positions R, 3 floats each;
+ *   influences K in 1..8; per vertex K joint numbers (uint16_t) and K weights (float), vertex-major: joints[v*K + k], weights[v*K + k];
+ *   num_joints J in 0..65535 joint matrices M, each 3 rows x 4 columns, row-major, 12 floats: M[j][c][i] = joint_mats[12*j + 4*c + i].  The
+ *     caller supplies the joint's global transform times its inverse bind matrix;
+ *   num_targets T in 0..256 dense morph targets D[t], 3 floats per vertex each: deltas[3*(t*num_verts + v) + c], and T target weights a.
+ *   J == 0: morph only; K, joints, weights and joint_mats are ignored and may be 0 / NULL.  T == 0: skin only; deltas and target_weights
+ *   may be NULL.  J == 0 together with T == 0 is an error.
+ * For vertex v, per component:
+ *   1. Morph.  m = R[v].  For t = 0 .. T-1 in ascending order, every target with a[t] != 0.0f: m = m + a[t] * D[t][v].  A target whose weight
+ *      compares equal to zero (either sign) is skipped, not multiplied: 0 * inf would be a NaN, and the skip is what lets the kernel leave
+ *      the memory of inactive targets alone.  A NaN weight is not equal to zero: the target counts.
+ *   2. Skin (J > 0).  p = (0, 0, 0), any = false.  For k = 0 .. K-1 in ascending order, w = weights[v][k], j = joints[v][k], every influence
+ *      with w != 0.0f:  q_c = ((M[j][c][0]*m.x + M[j][c][1]*m.y) + M[j][c][2]*m.z) + M[j][c][3]  for c = 0..2, then p_c = p_c + w * q_c and
+ *      any = true.
+ *   3. Result: p if any, else m -- a vertex without influences follows the morph only.  Weights are not normalised; that is the caller's
+ *      business, as in glTF.  A skinned component that is -0 comes out as +0 (p starts from +0); an unskinned one keeps its sign.
+ *   4. A joint number >= J on an influence whose weight is not zero is an error (at gmupt_pose_create for the device path).  The joint
+ *      number of an influence of weight zero may be anything: it is never followed.
+ *   5. Non-finite matrices, weights or deltas are no error; they propagate into the vertex.  gmupt_renderer_refit then refuses a non-finite
+ *      vertex that a triangle uses, as it does for any vertex buffer; a later pose with finite input recovers.
+ *   Only the 3 floats of the vertices 0 .. num_verts-1 are written.
+ * gmupt_pose_host: the rule on host arrays, no device; verts_out holds 3 floats per vertex.  Up to `threads` std::threads (0 -> 1, at most
+ *   16); the result does not depend on the count.  A NULL rest or verts_out, num_verts == 0, K outside 1..8 with J > 0, J or T beyond their
+ *   limits, J == T == 0, a missing array, rule 4: GMUPT_ERR_INVALID_ARGUMENT, nothing written.
+ * gmupt_pose: a handle of a renderer for one rig: it uses the renderer's device and stream and must not outlive the renderer.
+ *   gmupt_pose_create: rest, joints, weights and deltas are caller-owned DEVICE memory in the layout above, finished by the caller, floats
+ *   4-byte and joint numbers 2-byte aligned; the handle keeps its own copies.  It needs a bound scene (GMUPT_ERR_NOT_BOUND); num_verts =
+ *   the element count of the bound vertex buffer.  One launch on the renderer's stream copies the rig into the handle's layout and checks
+ *   rule 4, then ONE flag word is read back and the stream synchronised once; on an error no handle is created.  Device memory kept per
+ *   vertex (the count rounded up to 64): 12 bytes of rest position, 6 per influence, 12 per target -- every component its own array, so
+ *   that a wave reads whole rows in lane order; plus 48 bytes per joint, 12 per target and 64 bytes of words.  A pinned host staging area of
+ *   48 * J + 4 * T bytes belongs to the handle too.
+ * gmupt_pose_update: joint_mats (12 * J floats) and target_weights (T floats) are HOST pointers (NULL where the count is 0).  They are
+ *   copied into the handle's pinned staging area and from there to the device on the renderer's stream; the call returns without waiting
+ *   for the stream (it waits only for the staging area's previous copy, a few kilobytes, when that has not run yet).
+ * gmupt_pose_update_device: the same with DEVICE pointers that the caller has finished and keeps unchanged until the renderer's stream has
+ *   passed the call (gmupt_synchronize, or any call that synchronises): they are copied on that stream.
+ * Both updates write the vertex buffer the renderer is bound to NOW (a rebind to buffers of the same vertex count needs no new handle).
+ *   GMUPT_ERR_NOT_BOUND without a scene; a bound vertex count other than at create: GMUPT_ERR_INVALID_ARGUMENT, nothing written or copied.
+ *   Two launches on the renderer's stream, ahead of a following gmupt_normals_update / gmupt_renderer_refit / gmupt_iterate without a host
+ *   wait: one block that lists the targets whose weight is not zero, then one thread per vertex, which reads the deltas of those targets
+ *   only; joint matrices sit in LDS up to 640 joints and are read from global memory above (the same statements).  No float atomics.
+ *   info == NULL: no host synchronisation.  With info: synchronises; ms = device time of the copies and launches (hipEvents),
+ *   active_targets = the number of target weights that are not zero.  Nothing else of the renderer is touched: as after any vertex update,
+ *   call gmupt_renderer_refit before the next gmupt_iterate and restart the accumulation. */
+typedef struct { uint32_t num_verts, active_targets; double ms; } gmupt_pose_info;   /* 16 bytes */
+int gmupt_pose_host(const float* rest, uint32_t num_verts, const uint16_t* joints, const float* weights, uint32_t influences, const float* joint_mats,
+                    uint32_t num_joints, const float* deltas, const float* target_weights, uint32_t num_targets, float* verts_out /* 3 per vertex */,
+                    uint32_t threads);
+typedef struct gmupt_pose gmupt_pose;
+int gmupt_pose_create(gmupt_renderer* r, const float* device_rest, const uint16_t* device_joints, const float* device_weights, uint32_t influences,
+                      uint32_t num_joints, const float* device_deltas, uint32_t num_targets, gmupt_pose** out);
+int gmupt_pose_update(gmupt_pose* p, const float* joint_mats, const float* target_weights, gmupt_pose_info* info /* may be NULL */);
+int gmupt_pose_update_device(gmupt_pose* p, const float* device_joint_mats, const float* device_target_weights, gmupt_pose_info* info /* may be NULL */);
+void gmupt_pose_destroy(gmupt_pose* p);
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);
