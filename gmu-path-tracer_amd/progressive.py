@@ -69,6 +69,9 @@ class ProgressiveSession:
         and its sah measured before anything is bound.  A cheaper candidate is adopted exactly as by rebuild() -- buffers swapped, bound,
         the Normals handle and the temporal history dropped -- and its cost is the new baseline; a candidate that is no cheaper is
         closed, the refitted tree stays and its cost becomes the baseline, so that a losing candidate is not built again every frame.
+        A candidate the builder refuses with GMUPT_ERR_UNSUPPORTED (rule 9 of the LBVH: a tree deeper than 64 levels) is a candidate
+        that lost: no exception, the refitted tree stays and its cost becomes the baseline, candidate_cost stays None and the dict
+        also holds candidate_refused, the library's message.  Every other error of the build propagates.
         A baseline of 0 (a root without area) never triggers.  The returned dict then also holds cost, baseline (the value the
         decision was made against), candidate_cost (None when none was built) and tree_rebuilt.  There is no default threshold:
         DESIGN.md "Tree cost" has the measurements."""
@@ -134,7 +137,15 @@ class ProgressiveSession:
         cost = self.renderer.tree_cost()["sah"]                  # on the renderer's stream, behind the refit
         info = dict(info, cost=cost, baseline=self.baseline, candidate_cost=None, tree_rebuilt=False)
         if self.baseline > 0 and cost > rebuild_above * self.baseline:
-            nodes, tris, _, picked = self._build_candidate(scene_buffers, None, None, 4)
+            from . import capi
+            try:
+                nodes, tris, _, picked = self._build_candidate(scene_buffers, None, None, 4)
+            except capi.GmuptError as e:
+                if e.code != capi.ERR_UNSUPPORTED:
+                    raise
+                info["candidate_refused"] = str(e)       # a tree the builder refuses (deeper than 64 levels) is a candidate that lost
+                self.baseline = cost
+                return info
             info["candidate_cost"] = self.renderer.tree_cost(nodes=nodes)["sah"]
             if info["candidate_cost"] < cost:
                 self._adopt(scene_buffers, nodes, tris, picked)

@@ -100,6 +100,69 @@ def soup(n, seed):
     return _mesh(v, np.arange(3 * n).reshape(n, 3), seed)
 
 
+def key_chain(copies, half=0.0):
+    """A Morton key chain: the mesh that puts the tree on either side of rule 9's depth limit.  Triangle centres, in this order: `copies`
+    at the origin (key 0), one per key bit j = 0..62 at 2^(j // 3) / 2^21 on axis 2 - j % 3 (key 1 << j), one at (1, 1, 1) (cmin = 0 and
+    ext = 1 on every axis; the last cell, key all ones).  half == 0: every triangle is its centre three times; half > 0: the centre plus
+    (-h, -h, -h), (h, -h, h), (-h, h, h), whose box centre is the centre again -- exactly, for half in {2^-23, 0.125, 0.25}.  Every inner
+    node of the chain has one leaf and one inner child: the highest differing bit takes every position 62..0, then the copies continue
+    the chain through the position tie-break.  KEY_CHAIN_DEPTH has the depths."""
+    c = np.zeros((copies + 64, 3), F)
+    for j in range(63):
+        c[copies + j, 2 - j % 3] = F(2.0 ** (j // 3 - 21))
+    c[copies + 63] = 1.0
+    h = F(half)
+    corners = np.array([[-h, -h, -h], [h, -h, h], [-h, h, h]], F)
+    v = c[:, None, :] + corners[None, :, :]
+    assert v.dtype == np.float32
+    return _mesh(v.reshape(-1, 3), np.arange(3 * len(c)).reshape(len(c), 3), copies)
+
+
+# copies -> the depth of key_chain(copies, half)'s tree for L = 1, 2, 4, whatever half is: by the rule, the chain of 63 key bits below the
+# root's split, shortened by the leaf size at its lower end and extended by ceil(log2) levels of the position tie-break among the copies
+KEY_CHAIN_DEPTH = {1: (63, 62, 60), 2: (64, 63, 61), 3: (65, 64, 62), 4: (65, 64, 63), 5: (66, 65, 64), 8: (66, 65, 64), 9: (67, 66, 65),
+                   300: (72, 71, 70)}
+KEY_CHAIN_LEAF_SIZES = (1, 2, 4)
+KEY_CHAIN_HALVES = (0.0, 0.125)
+MAX_DEPTH = 64                                      # rule 9
+KEY_CHAIN_MIN_STACK = 40                            # what the oracle's walk of key_chain(2, 0.125), L = 1 must at least stack (it measured 46)
+
+
+def key_chain_cases(accepted):
+    """(copies, L, depth) of every cell of KEY_CHAIN_DEPTH on one side of the limit."""
+    return [(c, L, d) for c, row in KEY_CHAIN_DEPTH.items() for L, d in zip(KEY_CHAIN_LEAF_SIZES, row) if (d <= MAX_DEPTH) == accepted]
+
+
+def key_chain_render_mesh(scenes, copies, half):
+    return render_mesh(scenes, key_chain(copies, half), "key_chain%d" % copies)
+
+
+def render_mesh(scenes, mesh, name):
+    """A mesh of this file as one scenes.build_scene takes: face normals, the materials and lights of the library's triangle soup, a
+    camera that looks at the key chain's corner from z = 2."""
+    m = dict(mesh)
+    n = len(m["indices"])
+    soup_ = scenes.random_triangles_mesh(n, seed=1)
+    v, t = m["verts"], m["indices"]
+    fn = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+    fn /= np.maximum(np.linalg.norm(fn, axis=1, keepdims=True), 1e-20)
+    m.update({"normals": np.repeat(fn, 3, axis=0).astype(F), "vertex_material": soup_["vertex_material"], "materials": soup_["materials"],
+              "lights": soup_["lights"], "light_count": soup_["light_count"], "camera": (0.3, 0.3, 2.0, 0.0, 270.0),
+              "name": name})
+    return m
+
+
+def key_chain_rays(n=4096, seed=0):
+    """(n, 8) closest-hit rays (origin, tmax = FLT_MAX, direction, pad) from around the key chain towards its corner at the origin, where
+    the deep end of the tree lies: most of them hit, and those walk the chain to its bottom."""
+    rng = np.random.default_rng(seed)
+    o = rng.uniform(-0.3, 0.8, (n, 3)).astype(F)
+    target = rng.uniform(-0.1, 0.1, (n, 3)).astype(F)
+    rays = np.zeros((n, 8), F)
+    rays[:, 0:3] = o; rays[:, 3] = np.finfo(F).max; rays[:, 4:7] = target - o
+    return rays
+
+
 def crafted_meshes(L=4):
     """name -> mesh(verts, indices, vertex_material): the edge cases of the rule."""
     out = {}

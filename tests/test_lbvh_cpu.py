@@ -1,6 +1,7 @@
 """gmupt_lbvh_build_host (the host reference of the GPU LBVH builder) against an independent builder written from the rule in
 include/gmupt.h (tests/lbvh_util.py), bit for bit; the structure bind, refit and the oracle rely on; the errors of rule 9.  No GPU."""
 import ctypes as C
+import re
 
 import numpy as np
 import pytest
@@ -25,12 +26,13 @@ def meshes(pkg):
     return m
 
 
-def check_tree(pkg, mesh, L, name):
+def check_tree(pkg, mesh, L, name, want_depth=None):
     capi = pkg.capi
     v, t, vm = mesh["verts"], mesh["indices"], mesh["vertex_material"]
     got = capi.lbvh_build_host(v, t, vm, L)
     nodes, tris, ref, depth, leaves = LU.build(v, t, vm, L, capi.bvh_node_dtype, capi.triangle_dtype)
     what = "%s, L = %d" % (name, L)
+    assert want_depth is None or depth == want_depth, "%s: the independent builder finds depth %d, the construction states %d" % (what, depth, want_depth)
     assert np.array_equal(got["ref_triangle"], ref), what
     assert got["tris"].tobytes() == tris.tobytes(), what
     assert len(got["nodes"]) == len(nodes), what
@@ -68,6 +70,42 @@ def test_host_build_equals_the_rule(pkg, meshes, L):
             assert np.array_equal(got["ref_triangle"], np.arange(37)), "equal keys keep index order"
         if name == "grid16":
             assert len(set(LU.morton_keys(mesh["verts"], mesh["indices"]))) == 2, "the grid lies in one cell of the key space"
+
+
+@pytest.mark.parametrize("half", [0.0, 2.0**-23, 0.125, 0.25])
+def test_key_chain_keys(half):
+    """The construction of lbvh_util.key_chain: 65 distinct keys, every single bit 0..62 among them, whatever the triangles' size."""
+    for copies in (1, 2, 9):
+        mesh = LU.key_chain(copies, half)
+        keys = LU.morton_keys(mesh["verts"], mesh["indices"])
+        assert keys == [0] * copies + [1 << j for j in range(63)] + [(1 << 63) - 1], (copies, half)
+
+
+@pytest.mark.parametrize("half", LU.KEY_CHAIN_HALVES)
+def test_key_chain_trees_up_to_the_depth_limit(pkg, half):
+    """Every accepted cell of the depth table, the largest accepted depth 64 among them: the highest differing bit takes every position
+    62..0 in one tree, then delta continues into the position tie-break."""
+    cases = LU.key_chain_cases(accepted=True)
+    assert sorted(d for _, _, d in cases)[-1] == LU.MAX_DEPTH and len(cases) == 12
+    for copies, L, depth in cases:
+        got = check_tree(pkg, LU.key_chain(copies, half), L, "key_chain(%d, %r)" % (copies, half), want_depth=depth)
+        assert got["depth"] == depth
+
+
+def test_key_chain_oracle_stack_depth(pkg):
+    """What makes the GPU frames on the depth-64 tree (test_lbvh_deep_gpu.py) mean something: the oracle's walk of that scene stacks far
+    beyond the 24-entry LDS part of the casts' stacks and close to the limit of 64.  Measured: 46 (48 with half = 0.25)."""
+    scene = pkg.scenes.build_scene(LU.key_chain_render_mesh(pkg.scenes, 2, 0.125), builder="lbvh", max_leaf_size=1)
+    assert scene["depth"] == LU.MAX_DEPTH
+    orc = O.Renderer(scene, 32, 18, 1024, threads=4)
+    cam = O.Camera(32, 18); cam.set_pose(*scene["camera"]); cam.buffer.lightCount = scene["light_count"]
+    for _ in range(4):
+        cam.update(); orc.set_camera(cam.buffer); orc.iterate()
+    max_stack = orc.stats().maxStack
+    samples = int(orc.framebuffer()[..., 3].view(np.uint32).sum())
+    orc.close()
+    print("key_chain(2, 0.125), L = 1: oracle maxStack %d" % max_stack)
+    assert samples > 0 and LU.KEY_CHAIN_MIN_STACK <= max_stack <= LU.MAX_DEPTH
 
 
 def test_default_leaf_size_and_scene_builder(pkg):
@@ -136,9 +174,11 @@ def test_errors_write_nothing(pkg):
     mesh = LU.soup(9, 5)
     v, t = mesh["verts"].copy(), mesh["indices"].copy()
     n = len(t)
-    nodes = np.full(2 * n - 1, 0x5A, np.uint8).repeat(48).view(capi.bvh_node_dtype)
-    tris = np.full(n * 16, 0x5A, np.uint8).view(capi.triangle_dtype)
-    ref = np.full(n, 0x5A5A5A5A, np.int32)
+    deep = LU.key_chain_cases(accepted=False)
+    room = max(n, max(c for c, _, _ in deep) + 64)                            # the outputs hold the largest refused mesh too
+    nodes = np.full(2 * room - 1, 0x5A, np.uint8).repeat(48).view(capi.bvh_node_dtype)
+    tris = np.full(room * 16, 0x5A, np.uint8).view(capi.triangle_dtype)
+    ref = np.full(room, 0x5A5A5A5A, np.int32)
     keep = (nodes.tobytes(), tris.tobytes(), ref.tobytes())
 
     def refused(code, *args):
@@ -160,11 +200,22 @@ def test_errors_write_nothing(pkg):
     for bad in (np.nan, np.inf, -np.inf):
         v2 = v.copy(); v2[t[n - 1, 1], 2] = bad
         refused(INVALID, v2, len(v2), t, n, 4, nodes, tris, ref)
-    assert UNSUPPORTED == -5   # (rule 9's depth error needs 2^k coincident centres deep inside the key space; stated in the header, not built here)
+    # rule 9's depth error: every cell of the key chain's depth table beyond 64, the nearest (65) and the farthest (72) among them
+    assert UNSUPPORTED == capi.ERR_UNSUPPORTED and len(deep) == 12 and {65, 72} <= {d for _, _, d in deep}
+    for copies, L, depth in deep:
+        for half in LU.KEY_CHAIN_HALVES:
+            m = LU.key_chain(copies, half)
+            kv, kt = m["verts"], np.ascontiguousarray(m["indices"], np.int32)
+            assert LU.build(kv, kt, None, L, capi.bvh_node_dtype, capi.triangle_dtype)[3] == depth, (copies, L, half)
+            refused(UNSUPPORTED, kv, len(kv), kt, len(kt), L, nodes, tris, ref)
+            with pytest.raises(capi.GmuptError) as e:
+                capi.lbvh_build_host(kv, kt, m["vertex_material"], L)
+            assert e.value.code == UNSUPPORTED and re.findall(r"\d+", str(e.value).split(":", 1)[1]) == [str(depth), "64"], str(e.value)
     # a vertex no triangle uses may hold anything
     v3 = np.concatenate([v, [[np.nan, np.inf, 0.0]]]).astype(np.float32)
     assert call_host(pkg, v3, len(v3), t, n, 4, nodes, tris, ref) == 0
     want = capi.lbvh_build_host(v, t, None, 4)
-    assert nodes[:len(want["nodes"])].tobytes() == want["nodes"].tobytes() and tris.tobytes() == want["tris"].tobytes() and np.array_equal(ref, want["ref_triangle"])
+    assert nodes[:len(want["nodes"])].tobytes() == want["nodes"].tobytes() and tris[:n].tobytes() == want["tris"].tobytes() and np.array_equal(ref[:n], want["ref_triangle"])
+    assert (nodes[len(want["nodes"]):].tobytes(), tris[n:].tobytes(), ref[n:].tobytes()) == (keep[0][len(want["nodes"]) * 48:], keep[1][n * 16:], keep[2][n * 4:])
     # ref_triangle_out may be NULL
     assert call_host(pkg, v, len(v), t, n, 4, nodes, tris, None) == 0

@@ -66,6 +66,7 @@ def test_library_meshes_agree_with_tree_sah(pkg, library):
     """Reordering N non-negative double terms moves their sum by at most N * 2^-53 relative per addition chain end to end, i.e. well within
     N * 2^-52; tree_sah's 2 * area and int count differ from the rule's half area and uint32 weight by exact factors, its final
     division and the handful of roundings per term by a few ulp more: (N + 8) * 2^-52."""
+    assert library["key_chain"][2]["depth"] == 64, "the key chain's LBVH is the deepest tree the builder accepts"
     for name, (_, sbvh, lbvh) in library.items():
         for what, scene in (("sbvh", sbvh), ("lbvh", lbvh)):
             nodes = scene["nodes"]

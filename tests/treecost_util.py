@@ -2,6 +2,8 @@
 share: crafted record arrays (no tree needed: the rule follows no link), the library meshes, and the two seeded poses of the policy tests."""
 import numpy as np
 
+import lbvh_util as LU
+
 RUN = 256
 INT_FIELDS = ("num_inner", "num_leaves", "num_refs", "max_leaf_refs")
 DOUBLE_FIELDS = ("sum_inner", "sum_leaf", "root_half_area", "sah")
@@ -98,9 +100,11 @@ def special_records(kind, node_dtype, n=300):
 
 
 def library_scenes(scenes):
-    """name -> (mesh, sbvh scene, lbvh scene) of the three library meshes the GPU tests bind."""
+    """name -> (mesh, sbvh scene, lbvh scene) of the three library meshes the GPU tests bind, and of the Morton key chain whose LBVH (leaf
+    size 4) is 64 levels deep, the deepest tree the builder accepts."""
     meshes = {"cornell": scenes.cornell_mesh(), "soup": scenes.random_triangles_mesh(2000, seed=1),
-              "spheres_small": scenes.spheres_mesh(n_spheres=12, subdiv=2, seed=7, floor_quads=4)}
+              "spheres_small": scenes.spheres_mesh(n_spheres=12, subdiv=2, seed=7, floor_quads=4),
+              "key_chain": LU.key_chain_render_mesh(scenes, 8, 0.125)}
     return {k: (m, scenes.build_scene(m), scenes.build_scene(m, builder="lbvh")) for k, m in meshes.items()}
 
 
