@@ -194,6 +194,25 @@ class TreeCostInfo(C.Structure):
 assert C.sizeof(TreeCostInfo) == 64
 
 
+class TreeoptParams(C.Structure):
+    """gmupt_treeopt_params."""
+    _fields_ = [("passes", C.c_uint32)]
+
+
+class TreeoptInfo(C.Structure):
+    """gmupt_treeopt_info: 40 bytes."""
+    _fields_ = [("num_nodes", C.c_uint32), ("depth_before", C.c_uint32), ("depth_after", C.c_uint32), ("treelets_rewritten", C.c_uint32),
+                ("cost_before", C.c_double), ("cost_after", C.c_double), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {"num_nodes": int(self.num_nodes), "depth_before": int(self.depth_before), "depth_after": int(self.depth_after),
+                "treelets_rewritten": int(self.treelets_rewritten), "cost_before": float(self.cost_before), "cost_after": float(self.cost_after),
+                "ms": float(self.ms)}
+
+
+assert C.sizeof(TreeoptInfo) == 40
+
+
 class GmuptError(RuntimeError):
     def __init__(self, msg, code=0):
         super().__init__(msg)
@@ -271,6 +290,11 @@ SYMBOLS = {
     "gmupt_buffer_update_device": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_tree_cost_host": (C.c_int, [_P, C.c_uint32, C.POINTER(TreeCostInfo), C.c_uint32]),
     "gmupt_renderer_tree_cost": (C.c_int, [_P, _P, C.POINTER(TreeCostInfo)]),
+    "gmupt_treeopt_default_params": (None, [C.POINTER(TreeoptParams)]),
+    "gmupt_tree_optimize_host": (C.c_int, [_P, C.c_uint32, C.POINTER(TreeoptParams), _P, C.POINTER(TreeoptInfo)]),
+    "gmupt_treeopt_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "gmupt_treeopt_destroy": (None, [_P]),
+    "gmupt_treeopt_run": (C.c_int, [_P, _P, C.POINTER(TreeoptParams), C.POINTER(_P), C.POINTER(TreeoptInfo)]),
     "gmupt_pose_host": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32]),
     "gmupt_pose_create": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(_P)]),
     "gmupt_pose_update": (C.c_int, [_P, _P, _P, C.POINTER(PoseInfo)]),
@@ -1374,6 +1398,38 @@ def tree_cost_host(nodes, threads=16):
     return ti.as_dict()
 
 
+def tree_optimize_host(nodes, passes=3):
+    """gmupt_tree_optimize_host: the treelet optimiser of include/gmupt.h ("Tree optimisation") on the CPU, bit for bit what
+    TreeOptimizer.run returns for the same records.  Returns (nodes, info dict); ms = 0."""
+    nodes = np.ascontiguousarray(nodes, dtype=bvh_node_dtype)
+    out = np.zeros(max(nodes.shape[0], 1), dtype=bvh_node_dtype)[:nodes.shape[0]]
+    pp, info = TreeoptParams(int(passes)), TreeoptInfo()
+    _check(lib().gmupt_tree_optimize_host(_ptr(nodes), nodes.shape[0], C.byref(pp), _ptr(out), C.byref(info)))
+    return out, info.as_dict()
+
+
+class TreeOptimizer:
+    """gmupt_treeopt: the GPU treelet optimiser of one device -- a stream and the scratch of the largest tree optimised so far."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.h = _P()
+        _check(lib().gmupt_treeopt_create(dev.h, C.byref(self.h)))
+
+    def run(self, nodes, passes=3):
+        """gmupt_treeopt_run on `nodes`, a Buffer of kind BUFFER_BVH_NODES (left as it is).  Returns (a new nodes Buffer the caller closes,
+        info dict)."""
+        out, info = _P(), TreeoptInfo()
+        pp = TreeoptParams(int(passes))
+        _check(lib().gmupt_treeopt_run(self.h, nodes.h, C.byref(pp), C.byref(out), C.byref(info)))
+        return Buffer.wrap(self.dev, out), info.as_dict()
+
+    def close(self):
+        if self.h:
+            lib().gmupt_treeopt_destroy(self.h)
+            self.h = _P()
+
+
 class Lbvh:
     """gmupt_lbvh: the GPU LBVH builder of one device -- a stream and the scratch of the largest mesh built so far, kept between builds."""
 
@@ -1381,11 +1437,15 @@ class Lbvh:
         self.dev = dev
         self.h = _P()
         _check(lib().gmupt_lbvh_create(dev.h, C.byref(self.h)))
+        self.optimizer = None     # the TreeOptimizer of build(optimize=...), created by the first such build
 
-    def build(self, vertex_buffer, indices, vertex_material=None, max_leaf_size=4, ref_triangle=False):
+    def build(self, vertex_buffer, indices, vertex_material=None, max_leaf_size=4, ref_triangle=False, optimize=0):
         """gmupt_lbvh_build on the device-resident vertices of `vertex_buffer` (a Buffer of kind BUFFER_VERTICES).  indices / vertex_material:
         torch device tensors (int32 / a 4-byte integer type, used in place) or numpy arrays (uploaded).  Returns (nodes Buffer, tris Buffer,
-        info dict); the caller closes the buffers.  ref_triangle=True adds info["ref_triangle"], the source triangle of every record."""
+        info dict); the caller closes the buffers.  ref_triangle=True adds info["ref_triangle"], the source triangle of every record.
+        optimize=N > 0 runs N passes of the treelet optimiser (TreeOptimizer.run) on the new tree: the nodes Buffer is the optimised one,
+        info["optimize"] its info dict and info["depth"] the new depth; an optimiser error (a tree that became too deep) is raised and no
+        buffer is left behind."""
         import torch
         device = torch.device("cuda", self.dev.index)
 
@@ -1412,9 +1472,25 @@ class Lbvh:
         out = info.as_dict()
         if ref is not None:
             out["ref_triangle"] = ref[:n].cpu().numpy()
-        return Buffer.wrap(self.dev, nodes), Buffer.wrap(self.dev, tris), out
+        nodes, tris = Buffer.wrap(self.dev, nodes), Buffer.wrap(self.dev, tris)
+        if optimize:
+            if self.optimizer is None:
+                self.optimizer = TreeOptimizer(self.dev)
+            try:
+                better, out["optimize"] = self.optimizer.run(nodes, passes=optimize)
+            except GmuptError:
+                tris.close()
+                raise
+            finally:
+                nodes.close()
+            nodes = better
+            out["depth"] = out["optimize"]["depth_after"]
+        return nodes, tris, out
 
     def close(self):
+        if self.optimizer is not None:
+            self.optimizer.close()
+            self.optimizer = None
         if self.h:
             lib().gmupt_lbvh_destroy(self.h)
             self.h = _P()

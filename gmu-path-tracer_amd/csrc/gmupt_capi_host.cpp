@@ -235,6 +235,42 @@ extern "C" int gmupt_lbvh_build_host(const float* verts, uint32_t num_verts, con
     return GMUPT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ tree optimisation: the host reference (pt_treeopt.cpp) of gmupt_treeopt_run
+static_assert(sizeof(gmupt_treeopt_info) == 40 && offsetof(gmupt_treeopt_info, cost_before) == 16 && offsetof(gmupt_treeopt_info, ms) == 32, "gmupt_treeopt_info layout");
+
+extern "C" void gmupt_treeopt_default_params(gmupt_treeopt_params* p) { if (p) p->passes = 3; }
+
+void treeopt_fill_info(gmupt_treeopt_info* info, const ToResult& res, double ms)
+{
+    if (!info) return;
+    info->num_nodes = res.numNodes; info->depth_before = res.depthBefore; info->depth_after = res.depthAfter; info->treelets_rewritten = res.rewritten;
+    info->cost_before = res.costBefore; info->cost_after = res.costAfter; info->ms = ms;
+}
+
+int treeopt_passes(const char* fn, const gmupt_treeopt_params* params, uint32_t* passes)
+{
+    *passes = params ? params->passes : 3u;
+    if (*passes < 1 || *passes > kToMaxPasses) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: passes %u outside 1..%u", fn, *passes, kToMaxPasses);
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_tree_optimize_host(const gmupt_bvh_node* nodes, uint32_t n, const gmupt_treeopt_params* params, gmupt_bvh_node* nodes_out, gmupt_treeopt_info* info)
+{
+    if (!nodes || !nodes_out || n == 0 || n > 0x7FFFFFFFu) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_tree_optimize_host: null or empty array, or more than 2^31 - 1 records");
+    uint32_t passes;
+    GMUPT_TRY(treeopt_passes("gmupt_tree_optimize_host", params, &passes));
+    ToResult res{};
+    int status = GMUPT_OK;
+    try {
+        const std::string err = tree_optimize_host(nodes, n, passes, nodes_out, res, &status);
+        if (status != GMUPT_OK) return fail(status, "gmupt_tree_optimize_host: %s", err.c_str());
+    } catch (const std::bad_alloc&) {
+        return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_tree_optimize_host: out of host memory for %u records", n);
+    }
+    treeopt_fill_info(info, res, 0.0);
+    return GMUPT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ normals: the host reference (pt_normals.cpp) of gmupt_normals_update
 extern "C" int gmupt_vertex_normals_host(const float* verts, uint32_t num_verts, const int32_t* indices, uint32_t num_tris, float* normals_out, uint32_t threads)
 {

@@ -9,6 +9,7 @@
 #include "pt_lbvh.hpp"                // and with it pt_refit.hpp, pt_device.hpp, detmath.hpp
 #include "pt_normals.hpp"
 #include "pt_treecost.hpp"
+#include "pt_treeopt.hpp"
 #include "pt_pose.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
@@ -166,6 +167,12 @@ struct gmupt_lbvh {
     ~gmupt_lbvh() { if (stream) (void)hipStreamDestroy(stream); }        // gmupt_lbvh_destroy has synchronised it
 };
 
+// the optimiser handle: a stream, two events and the scratch of the largest tree optimised so far
+struct gmupt_treeopt {
+    gmupt_device* dev; hipStream_t stream = nullptr; EventPair ev; DevMem scratch; uint32_t capNodes = 0; size_t sortTemp = 0;
+    ~gmupt_treeopt() { if (stream) (void)hipStreamDestroy(stream); }     // gmupt_treeopt_destroy has synchronised it
+};
+
 // the adjacency of one index list for a renderer's vertices (gmupt_normals_*): device memory laid out by normals_layout (pt_normals.hip)
 struct gmupt_normals {
     gmupt_renderer* r = nullptr;
@@ -195,6 +202,8 @@ int denoise_args(const char* fn, const void* beauty, const void* aov, uint32_t W
 int temporal_params(const char* fn, const gmupt_temporal_params* p, DnParams& dn, TpParams& tp);
 int lbvh_leaf_size(const char* fn, const gmupt_lbvh_params* params, uint32_t* L);
 void lbvh_fill_info(gmupt_lbvh_info* info, const LbResult& res, uint32_t numTris, double ms);
+int treeopt_passes(const char* fn, const gmupt_treeopt_params* params, uint32_t* passes);
+void treeopt_fill_info(gmupt_treeopt_info* info, const ToResult& res, double ms);
 
 // one copy on a stream, waited for
 inline int copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s)

@@ -8,7 +8,7 @@
 #include "../../include/gmupt.h"
 
 namespace gmupt {
-struct RenderParams; struct SceneView; struct DnParams; struct TpParams; struct TpPrev; struct RfArgs; struct LbScratch; struct LbStaging; struct NmLayout; struct NmArgs; struct TcPartial; struct PsLayout; struct PsArgs;   // pt_*.hpp
+struct RenderParams; struct SceneView; struct DnParams; struct TpParams; struct TpPrev; struct RfArgs; struct LbScratch; struct LbStaging; struct NmLayout; struct NmArgs; struct TcPartial; struct PsLayout; struct PsArgs; struct ToScratch;   // pt_*.hpp
 
 void launch_clear(const RenderParams& p, hipStream_t s);
 void launch_logic(const RenderParams& p, hipStream_t s);
@@ -58,4 +58,8 @@ hipError_t launch_pose_create(const PsArgs& a, hipStream_t s);
 void launch_pose_update(const PsArgs& a, hipStream_t s);
 size_t tree_cost_scratch_partials(uint32_t n);
 const TcPartial* launch_tree_cost(const gmupt_bvh_node* nodes, uint32_t n, TcPartial* scratch, hipStream_t s);
+hipError_t treeopt_sort_temp_bytes(uint32_t n, size_t* bytes);
+ToScratch treeopt_scratch_layout(uint32_t n, size_t sortTemp);
+hipError_t launch_treeopt(void* scratch, const ToScratch& off, size_t sortTemp, const gmupt_bvh_node* nodes, uint32_t n, uint32_t passes, hipStream_t s,
+                          const void** words, const void** staged);
 }

@@ -3,9 +3,30 @@
 #include <cstring>
 #include <stdexcept>
 
-BVHWrapper::BVHWrapper(const MeshData& scene, Builder builder, unsigned maxLeafSize)
+BVHWrapper::BVHWrapper(const MeshData& scene, Builder builder, unsigned maxLeafSize, unsigned optimizePasses)
 {
+	if (optimizePasses && builder != Builder::LBVH) throw std::runtime_error("BVHWrapper: the treelet optimiser goes with the LBVH builder");
 	if (builder == Builder::LBVH) buildLBVH(scene, maxLeafSize); else buildSBVH(scene);
+	if (optimizePasses)
+	{
+		gmupt_treeopt_params params;
+		gmupt_treeopt_default_params(&params);
+		params.passes = optimizePasses;
+		std::vector<BVHNode> better(mGPUTree.size());
+		if (gmupt_tree_optimize_host(mGPUTree.data(), static_cast<uint32_t>(mGPUTree.size()), &params, better.data(), &mOptimizeInfo) != GMUPT_OK)
+			throw std::runtime_error(gmupt_last_error());
+		mGPUTree.swap(better);
+	}
+}
+
+gmupt_buffer* BVHWrapper::optimizeOnDevice(gmupt_treeopt* optimizer, const gmupt_buffer* nodes, unsigned passes, gmupt_treeopt_info* info)
+{
+	gmupt_treeopt_params params;
+	gmupt_treeopt_default_params(&params);
+	params.passes = passes;
+	gmupt_buffer* better = nullptr;
+	if (gmupt_treeopt_run(optimizer, nodes, &params, &better, info) != GMUPT_OK) throw std::runtime_error(gmupt_last_error());
+	return better;
 }
 
 void BVHWrapper::fillProperties(const MeshData& scene)

@@ -16,8 +16,16 @@ public:
 	// through its host reference gmupt_lbvh_build_host -- the arrays Scene::rebuildOnDevice gets from the GPU, bit for bit.
 	enum class Builder { SBVH, LBVH };
 
+	// optimizePasses > 0 (LBVH only): that many passes of the treelet optimiser's host reference (gmupt_tree_optimize_host, include/gmupt.h
+	// "Tree optimisation") on the built tree -- the nodes optimizeOnDevice gets from the GPU, bit for bit.  Throws std::runtime_error.
 	BVHWrapper() = default;
-	explicit BVHWrapper(const MeshData& scene, Builder builder = Builder::SBVH, unsigned maxLeafSize = 4);
+	explicit BVHWrapper(const MeshData& scene, Builder builder = Builder::SBVH, unsigned maxLeafSize = 4, unsigned optimizePasses = 0);
+
+	// The treelet optimiser on the device (gmupt_treeopt_run) for a node buffer that lives there, e.g. the one gmupt_lbvh_build returned:
+	// a new node buffer of the same leaves, which the caller owns; `nodes` stays as it is and the triangle buffer stays valid.  Throws
+	// std::runtime_error with gmupt_last_error (a tree deeper than 64 levels after a pass, ...) and then creates nothing.
+	static gmupt_buffer* optimizeOnDevice(gmupt_treeopt* optimizer, const gmupt_buffer* nodes, unsigned passes, gmupt_treeopt_info* info = nullptr);
+	const gmupt_treeopt_info& optimizeInfo() const { return mOptimizeInfo; } // of the constructor's passes; zeros without
 
 	const std::vector<BVHNode>& tree() const { return mGPUTree; }
 	const std::vector<Triangle>& indices() const { return mIndices; }
@@ -37,6 +45,7 @@ private:
 	std::vector<float> mVertices;
 	float mSAH = 0.f;
 	gmupt_lbvh_info mLBVHInfo{};
+	gmupt_treeopt_info mOptimizeInfo{};
 
 	friend class Scene;
 };

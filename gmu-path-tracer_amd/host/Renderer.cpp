@@ -256,9 +256,9 @@ gmupt_tree_cost_info Renderer::treeCost()
 	return info;
 }
 
-gmupt_lbvh_info Renderer::rebuildScene(unsigned maxLeafSize, const std::vector<int32_t>* indices)
+gmupt_lbvh_info Renderer::rebuildScene(unsigned maxLeafSize, const std::vector<int32_t>* indices, unsigned optimizePasses, gmupt_treeopt_info* optimizeInfo)
 {
-	const gmupt_lbvh_info info = mScene.rebuildOnDevice(maxLeafSize, indices);
+	const gmupt_lbvh_info info = mScene.rebuildOnDevice(maxLeafSize, indices, optimizePasses, optimizeInfo);
 	mNormals.reset();                                  // another triangle list needs another adjacency
 	mSceneBound = false;
 	bindScene();                                       // waits for the renderer's stream before it lets go of the old tree

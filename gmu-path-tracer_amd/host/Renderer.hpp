@@ -85,7 +85,9 @@ public:
 	// geometry a refit does not cover (after Scene::setVertices with vertices that moved far, or with another triangle list): a new tree
 	// from the GPU LBVH builder (Scene::rebuildOnDevice) bound in place of the old one, the accumulation restarted and the temporal history
 	// dropped -- a new binding is a new geometry.  The host pass of the bind (the traversal tables) runs as for any bind.
-	gmupt_lbvh_info rebuildScene(unsigned maxLeafSize = 4, const std::vector<int32_t>* indices = nullptr);
+	// optimizePasses > 0: the treelet optimiser runs on the new tree before it is bound (Scene::rebuildOnDevice has the details).
+	gmupt_lbvh_info rebuildScene(unsigned maxLeafSize = 4, const std::vector<int32_t>* indices = nullptr, unsigned optimizePasses = 0,
+	                             gmupt_treeopt_info* optimizeInfo = nullptr);
 
 private:
 	void createDevice(int hipDevice);

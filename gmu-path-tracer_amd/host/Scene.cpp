@@ -176,7 +176,7 @@ void Scene::loadRig(const std::string& path)
 	mRig = std::move(rig);
 }
 
-gmupt_lbvh_info Scene::rebuildOnDevice(unsigned maxLeafSize, const std::vector<int32_t>* indices)
+gmupt_lbvh_info Scene::rebuildOnDevice(unsigned maxLeafSize, const std::vector<int32_t>* indices, unsigned optimizePasses, gmupt_treeopt_info* optimizeInfo)
 {
 	const std::vector<int32_t>& list = indices ? *indices : mScene.indices;
 	if (list.empty() || list.size() % 3 != 0) throw std::runtime_error("rebuildOnDevice: " + std::to_string(list.size()) + " indices are no triangle list");
@@ -198,6 +198,16 @@ gmupt_lbvh_info Scene::rebuildOnDevice(unsigned maxLeafSize, const std::vector<i
 	gmupt_buffer *nodes = nullptr, *tris = nullptr;
 	check(gmupt_lbvh_build(mLBVH.get(), mVertexBuffer.get(), static_cast<const int32_t*>(mDeviceIndices.get()), static_cast<uint32_t>(list.size() / 3),
 	                       static_cast<const uint32_t*>(mDeviceVertexMaterial.get()), &params, &nodes, &tris, nullptr, &info));
+	if (optimizePasses)
+	{
+		Buffer plain(nodes), records(tris);                 // released below; destroyed when the optimiser throws
+		if (!mTreeopt) { gmupt_treeopt* h = nullptr; check(gmupt_treeopt_create(mDevice, &h)); mTreeopt.reset(h); }
+		gmupt_treeopt_info oinfo{};
+		nodes = BVHWrapper::optimizeOnDevice(mTreeopt.get(), plain.get(), optimizePasses, &oinfo);
+		tris = records.release();
+		info.depth = oinfo.depth_after;
+		if (optimizeInfo) *optimizeInfo = oinfo;
+	}
 	if (!mRetiredBVHBuffer) { mRetiredBVHBuffer = std::move(mBVHBuffer); mRetiredIndexBuffer = std::move(mIndexBuffer); }   // (else: never bound, dropped below)
 	mBVHBuffer.reset(nodes);
 	mIndexBuffer.reset(tris);

@@ -46,6 +46,7 @@ private:
 struct BufferDeleter { void operator()(gmupt_buffer* b) const { gmupt_buffer_destroy(b); } };
 using Buffer = std::unique_ptr<gmupt_buffer, BufferDeleter>;
 struct LbvhDeleter { void operator()(gmupt_lbvh* h) const { gmupt_lbvh_destroy(h); } };
+struct TreeoptDeleter { void operator()(gmupt_treeopt* h) const { gmupt_treeopt_destroy(h); } };
 struct DeviceFree { void operator()(void* p) const; };   // hipFree
 using DeviceMemory = std::unique_ptr<void, DeviceFree>;
 
@@ -77,7 +78,11 @@ public:
 	// The node and triangle buffers are replaced; the renderer still reads the old ones until it binds again, so call this through
 	// Renderer::rebuildScene(), which does.  Throws std::runtime_error (a bad index, a non-finite used vertex, ...) and then keeps the tree, the buffers and the mesh's
 	// triangle list as they were (only the internal device copy of the index list may hold the refused one; the next call uploads again).
-	gmupt_lbvh_info rebuildOnDevice(unsigned maxLeafSize = 4, const std::vector<int32_t>* indices = nullptr);
+	// optimizePasses > 0: the new tree goes through that many passes of the treelet optimiser on the device before it takes the place of the
+	// old one (BVHWrapper::optimizeOnDevice, include/gmupt.h "Tree optimisation"; the optimiser handle is created on first use and kept);
+	// *optimizeInfo (may be nullptr) then holds its info.  An optimiser error is thrown like a builder error: everything stays as it was.
+	gmupt_lbvh_info rebuildOnDevice(unsigned maxLeafSize = 4, const std::vector<int32_t>* indices = nullptr, unsigned optimizePasses = 0,
+	                                gmupt_treeopt_info* optimizeInfo = nullptr);
 	// the rig of the loaded mesh (an extension; include/gmupt.h "Pose"): a ".grig" file -- "GRIG", then version (1), num_verts, influences,
 	// num_joints, num_targets as little-endian uint32, then the arrays in the order of gmupt_pose_create: rest (3 floats per vertex), joints
 	// (uint16) and weights (float), `influences` per vertex each and absent when num_joints is 0, deltas (3 floats per vertex and target).
@@ -115,6 +120,7 @@ private:
 
 	// rebuildOnDevice: the builder, its inputs on the device, and the tree the renderer is still bound to until Renderer::rebuildScene rebinds
 	std::unique_ptr<gmupt_lbvh, LbvhDeleter> mLBVH;
+	std::unique_ptr<gmupt_treeopt, TreeoptDeleter> mTreeopt;
 	DeviceMemory mDeviceIndices, mDeviceVertexMaterial;
 	size_t mDeviceIndexCapacity = 0;
 	int mHipDevice = -1;                          // set by the Renderer that owns the scene: the device of rebuildOnDevice's own allocations

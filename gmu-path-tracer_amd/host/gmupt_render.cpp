@@ -30,6 +30,9 @@
 //                                                         vertices (Renderer::rebuildScene: Scene::rebuildOnDevice + bind), leaves of at most L
 //                                                         triangles (default 4); one JSON line with the build info; not with --ranks.
 //                                                         With --build-only: BVHWrapper::buildLBVH, the host reference of that build
+//                [--optimize N]                           with --builder lbvh: N passes (1..8; 0, the default: none) of the treelet optimiser on the new
+//                                                         tree before it is bound (Scene::rebuildOnDevice -> BVHWrapper::optimizeOnDevice), one more
+//                                                         JSON line with its info.  With --build-only: gmupt_tree_optimize_host, its host reference
 //                [--dump-tree FILE]                       with --build-only: the flattened tree, raw: the 48-byte nodes, then the 16-byte triangle records
 //                [--help]                                 this list
 #include <chrono>
@@ -118,7 +121,7 @@ int main(int argc, char** argv)
 	std::string aovPrefix; unsigned aovSamples = 1;
 	std::string denoisePrefix;
 	std::string temporalPrefix;
-	std::string builder = "sbvh", dumpTree; unsigned leaf = 4;
+	std::string builder = "sbvh", dumpTree; unsigned leaf = 4, optimize = 0;
 	bool treeCost = false;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
@@ -151,6 +154,7 @@ int main(int argc, char** argv)
 		else if (a == "--temporal") temporalPrefix = next();
 		else if (a == "--builder") { builder = next(); if (builder != "sbvh" && builder != "lbvh") { std::fprintf(stderr, "--builder takes sbvh or lbvh\n"); return 2; } }
 		else if (a == "--leaf") { char* end = nullptr; const char* v = next(); leaf = std::strtoul(v, &end, 10); if (end == v || *end || leaf < 1 || leaf > 64) { std::fprintf(stderr, "--leaf takes a number in 1..64\n"); return 2; } }
+		else if (a == "--optimize") { char* end = nullptr; const char* v = next(); optimize = std::strtoul(v, &end, 10); if (end == v || *end || optimize > 8) { std::fprintf(stderr, "--optimize takes a number of passes in 0..8\n"); return 2; } }
 		else if (a == "--dump-tree") dumpTree = next();
 		else if (a == "--tree-cost") treeCost = true;
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
@@ -171,6 +175,8 @@ int main(int argc, char** argv)
 			            "                                 one JSON line each, the doubles as hex bit patterns; not with --ranks\n"
 			            "             [--builder sbvh|lbvh [--leaf L]]   lbvh: the tree rebuilt on the GPU before the frames (linear BVH, leaves of at most L triangles,\n"
 			            "                                 default 4), one JSON line with the build info; not with --ranks.  With --build-only: the host reference of that build\n"
+			            "             [--optimize N]      with --builder lbvh: N = 1..8 passes of the treelet optimiser on the new tree before it is bound (0, the\n"
+			            "                                 default: none), one more JSON line with its info.  With --build-only: the host reference of the optimiser\n"
 			            "             [--dump-tree FILE]  with --build-only: the flattened tree, raw (48-byte nodes, then 16-byte triangle records)\n"
 			            "             [--denoise PREFIX [--aov-samples S]]   after the frames: the frame through the a-trous denoiser guided by the AOV buffers\n"
 			            "                            (S samples per axis): PREFIX.pfm (PF) and PREFIX.png (8-bit, truncated like --capture); not with --ranks\n");
@@ -230,7 +236,7 @@ int main(int argc, char** argv)
 			for (size_t i = 0; i < mesh.materials.size(); i++) { char buf[96]; std::snprintf(buf, sizeof(buf), "%s[%d, %d, %d]", i ? ", " : "", mesh.materials[i].textureIndices[0], mesh.materials[i].textureIndices[1], mesh.materials[i].textureIndices[2]); texInfo += buf; }
 			texInfo += "]";
 			const auto t0 = std::chrono::steady_clock::now();
-			BVHWrapper bvh(mesh, builder == "lbvh" ? BVHWrapper::Builder::LBVH : BVHWrapper::Builder::SBVH, leaf);
+			BVHWrapper bvh(mesh, builder == "lbvh" ? BVHWrapper::Builder::LBVH : BVHWrapper::Builder::SBVH, leaf, optimize);
 			const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 			float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
 			for (size_t i = 0; i < mesh.numVertices(); i++) for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], mesh.vertices[3 * i + k]); hi[k] = std::max(hi[k], mesh.vertices[3 * i + k]); }
@@ -265,6 +271,8 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--smooth-normals recomputes the normals of moved vertices: it needs --vertices FILE or --rig FILE --pose FILE");
 		if (treeCost && ranks > 1)
 			throw std::invalid_argument("--tree-cost measures the tree of a single process: it cannot be combined with --ranks N > 1");
+		if (optimize && builder != "lbvh")
+			throw std::invalid_argument("--optimize restructures the tree of --builder lbvh: it needs that option");
 		if (builder == "lbvh" && ranks > 1)
 			throw std::invalid_argument("--builder lbvh rebuilds the tree of a single process: it cannot be combined with --ranks N > 1");
 		if (ranks > 1 || !rendezvous.empty())
@@ -319,8 +327,12 @@ int main(int argc, char** argv)
 			if (treeCost) printTreeCost("pose", renderer.treeCost());
 		}
 		if (builder == "lbvh") {
-			const gmupt_lbvh_info info = renderer.rebuildScene(leaf);
+			gmupt_treeopt_info oinfo{};
+			const gmupt_lbvh_info info = renderer.rebuildScene(leaf, nullptr, optimize, &oinfo);
 			std::printf("{\"lbvh\": {\"num_nodes\": %u, \"num_leaves\": %u, \"depth\": %u, \"num_tris\": %u, \"ms\": %.6g}}\n", info.num_nodes, info.num_leaves, info.depth, info.num_tris, info.ms);
+			if (optimize)
+				std::printf("{\"optimize\": {\"passes\": %u, \"num_nodes\": %u, \"depth_before\": %u, \"depth_after\": %u, \"treelets_rewritten\": %u, \"cost_before\": %.17g, \"cost_after\": %.17g, \"ms\": %.6g}}\n",
+				            optimize, oinfo.num_nodes, oinfo.depth_before, oinfo.depth_after, oinfo.treelets_rewritten, oinfo.cost_before, oinfo.cost_after, oinfo.ms);
 		}
 		for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
 		if (capture) { renderer.requestCapture(); renderer.update(0.f); std::printf("capture %s\n", renderer.lastCapturePath().c_str()); }

@@ -47,7 +47,7 @@ class ProgressiveSession:
         if self.temporal is not None:
             self.temporal.reset()                    # the history was lit by the old lights
 
-    def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False, indices=None, rebuild_above=None):
+    def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False, indices=None, rebuild_above=None, optimize=0):
         """The geometry moved (same vertex count, same triangles): upload the vertices, and `normals` (when given) into the property
         records, refit the tree and the renderer's traversal tables on the GPU (gmupt_renderer_refit), restart the accumulation.  The
         temporal history shows the old surface and is dropped; with keep_history=True it is kept, and denoised_temporal() from then on
@@ -72,6 +72,9 @@ class ProgressiveSession:
         A candidate the builder refuses with GMUPT_ERR_UNSUPPORTED (rule 9 of the LBVH: a tree deeper than 64 levels) is a candidate
         that lost: no exception, the refitted tree stays and its cost becomes the baseline, candidate_cost stays None and the dict
         also holds candidate_refused, the library's message.  Every other error of the build propagates.
+        optimize: 0 (the default) leaves the candidate as built.  N > 0 runs N passes of the treelet optimiser on it (capi.TreeOptimizer,
+        include/gmupt.h "Tree optimisation"): the optimised tree is the candidate that is measured, compared and bound, and
+        candidate_cost is its cost.  An optimiser refusal with GMUPT_ERR_UNSUPPORTED (deeper than 64 levels) counts like the builder's.
         A baseline of 0 (a root without area) never triggers.  The returned dict then also holds cost, baseline (the value the
         decision was made against), candidate_cost (None when none was built) and tree_rebuilt.  There is no default threshold:
         DESIGN.md "Tree cost" has the measurements."""
@@ -80,9 +83,10 @@ class ProgressiveSession:
             scene_buffers.verts.update_from_device(verts)
         else:
             scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
-        return self._after_vertices(scene_buffers, normals, keep_history, indices, rebuild_above)
+        return self._after_vertices(scene_buffers, normals, keep_history, indices, rebuild_above, optimize)
 
-    def set_pose(self, scene_buffers, pose, joint_mats, target_weights=None, normals=None, keep_history=False, indices=None, rebuild_above=None):
+    def set_pose(self, scene_buffers, pose, joint_mats, target_weights=None, normals=None, keep_history=False, indices=None, rebuild_above=None,
+                 optimize=0):
         """The geometry moved because its rig did: pose.update(joint_mats, target_weights) (capi.Pose: skinning and morph targets on the
         GPU, a few kilobytes of input, no vertex array crosses the bus) writes the vertex buffer the renderer is bound to, then exactly
         what set_vertices does after its upload -- normals, refit, accumulation restart, history, the rebuild policy; the baseline of
@@ -91,7 +95,7 @@ class ProgressiveSession:
         keeps it valid, and closing it is the caller's business (the renderer closes it at the latest)."""
         rebuild_above = self._moved_args("set_pose", normals, rebuild_above)
         pose.update(joint_mats, target_weights)
-        return self._after_vertices(scene_buffers, normals, keep_history, indices, rebuild_above)
+        return self._after_vertices(scene_buffers, normals, keep_history, indices, rebuild_above, optimize)
 
     def _moved_args(self, who, normals, rebuild_above):
         """The argument checks set_vertices and set_pose share, and the baseline of the rebuild policy, measured before the vertices
@@ -106,7 +110,7 @@ class ProgressiveSession:
                 self.baseline = self.renderer.tree_cost()["sah"]
         return rebuild_above
 
-    def _after_vertices(self, scene_buffers, normals, keep_history, indices, rebuild_above):
+    def _after_vertices(self, scene_buffers, normals, keep_history, indices, rebuild_above, optimize=0):
         """What follows new contents of the bound vertex buffer (set_vertices documents it): normals, refit, restart, history, policy."""
         if isinstance(normals, str):
             from . import capi
@@ -139,7 +143,7 @@ class ProgressiveSession:
         if self.baseline > 0 and cost > rebuild_above * self.baseline:
             from . import capi
             try:
-                nodes, tris, _, picked = self._build_candidate(scene_buffers, None, None, 4)
+                nodes, tris, _, picked = self._build_candidate(scene_buffers, None, None, 4, optimize)
             except capi.GmuptError as e:
                 if e.code != capi.ERR_UNSUPPORTED:
                     raise
@@ -156,8 +160,9 @@ class ProgressiveSession:
                 self.baseline = cost
         return info
 
-    def _build_candidate(self, scene_buffers, indices, vertex_material, max_leaf_size):
-        """An LBVH over the device-resident vertices of `scene_buffers`, not bound yet: (nodes, tris, gmupt_lbvh_info dict, indices used)."""
+    def _build_candidate(self, scene_buffers, indices, vertex_material, max_leaf_size, optimize=0):
+        """An LBVH over the device-resident vertices of `scene_buffers`, not bound yet: (nodes, tris, gmupt_lbvh_info dict, indices used).
+        optimize > 0: after that many passes of the treelet optimiser."""
         from . import capi
         if indices is None:
             indices = self._indices if self._indices is not None else scene_buffers.tris.read(capi.triangle_dtype)["v"]
@@ -165,7 +170,7 @@ class ProgressiveSession:
             vertex_material = np.ascontiguousarray(scene_buffers.props.read(capi.tri_props_dtype)["materialID"])
         if self.lbvh is None:
             self.lbvh = capi.Lbvh(self.renderer.dev)
-        nodes, tris, info = self.lbvh.build(scene_buffers.verts, indices, vertex_material, max_leaf_size=max_leaf_size)
+        nodes, tris, info = self.lbvh.build(scene_buffers.verts, indices, vertex_material, max_leaf_size=max_leaf_size, optimize=optimize)
         return nodes, tris, info, indices
 
     def _adopt(self, scene_buffers, nodes, tris, indices):
@@ -182,18 +187,19 @@ class ProgressiveSession:
         if self.temporal is not None:
             self.temporal.reset()
 
-    def rebuild(self, scene_buffers, verts=None, indices=None, vertex_material=None, max_leaf_size=4):
+    def rebuild(self, scene_buffers, verts=None, indices=None, vertex_material=None, max_leaf_size=4, optimize=0):
         """The geometry changed beyond what a refit covers -- vertices that moved far, or another triangle list (a cut, a spawn, an LOD
         switch): upload `verts` when given (at most the vertex count the buffer was created with), build an LBVH on the GPU from the
         device-resident vertices (capi.Lbvh, gmupt_lbvh_build), put its node and triangle buffers into `scene_buffers` (the old ones are
         closed), bind, restart the accumulation and drop the temporal history: a new binding is a new geometry.
         indices: (n, 3) int32, numpy or a torch device tensor; None = the list of the last rebuild(), or, before any, the triangle
         records the scene is bound to (an SBVH's spatial splits then appear as repeated triangles).  vertex_material: per vertex; None =
-        the materialID column of the property records.  Returns the gmupt_lbvh_info dict.  The baseline of
-        set_vertices(rebuild_above=...) is forgotten: the next such call measures the new tree."""
+        the materialID column of the property records.  optimize: N > 0 runs N passes of the treelet optimiser on the new tree before it
+        is bound (capi.Lbvh.build(optimize=N); the dict then holds "optimize", the optimiser's info).  Returns the gmupt_lbvh_info dict.
+        The baseline of set_vertices(rebuild_above=...) is forgotten: the next such call measures the new tree."""
         if verts is not None:
             scene_buffers.verts.update(np.ascontiguousarray(verts, np.float32))
-        nodes, tris, info, indices = self._build_candidate(scene_buffers, indices, vertex_material, max_leaf_size)
+        nodes, tris, info, indices = self._build_candidate(scene_buffers, indices, vertex_material, max_leaf_size, optimize)
         self._adopt(scene_buffers, nodes, tris, indices)
         self.baseline = None                         # of the tree that is gone
         return info

@@ -228,13 +228,20 @@ def textured_mesh(seed=5):
     return m
 
 
-def build_scene(mesh, sbvh_params=None, builder="sbvh", max_leaf_size=4):
+def build_scene(mesh, sbvh_params=None, builder="sbvh", max_leaf_size=4, optimize=0):
     """BVHWrapper::buildSBVH: host SBVH build + flatten -> the buffers Renderer::draw binds (t0-t4, b1).  builder="lbvh": the tree of
-    gmupt_lbvh_build_host instead (the host reference of the GPU builder; capi.Lbvh builds the same arrays on the device)."""
+    gmupt_lbvh_build_host instead (the host reference of the GPU builder; capi.Lbvh builds the same arrays on the device).
+    optimize=N > 0 (with builder="lbvh"): N passes of the treelet optimiser's host reference (capi.tree_optimize_host) on that tree; the
+    scene then also holds "optimize", its info dict."""
+    if optimize and builder != "lbvh":
+        raise ValueError("build_scene: optimize=%r goes with builder='lbvh'" % (optimize,))
     if builder == "sbvh":
         built = capi.sbvh_build(mesh["verts"], mesh["indices"], mesh["vertex_material"], sbvh_params)
     elif builder == "lbvh":
         built = capi.lbvh_build_host(mesh["verts"], mesh["indices"], mesh["vertex_material"], max_leaf_size)
+        if optimize:
+            nodes, info = capi.tree_optimize_host(built["nodes"], optimize)
+            built = dict(built, nodes=nodes, sah=capi.tree_sah(nodes), depth=info["depth_after"], optimize=info)
     else:
         raise ValueError("build_scene: builder %r is neither 'sbvh' nor 'lbvh'" % (builder,))
     nv = mesh["verts"].shape[0]
@@ -248,6 +255,8 @@ def build_scene(mesh, sbvh_params=None, builder="sbvh", max_leaf_size=4):
              "light_count": mesh["light_count"], "camera": mesh["camera"], "name": mesh["name"],
              "sah": built["sah"], "depth": built["depth"], "ref_triangle": built["ref_triangle"],
              "num_triangles": int(mesh["indices"].shape[0])}
+    if "optimize" in built:
+        scene["optimize"] = built["optimize"]
     for k in ("tex_diffuse", "tex_metallic_roughness", "tex_normal"):
         scene[k] = mesh.get(k)
     return scene

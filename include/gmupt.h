@@ -712,6 +712,69 @@ typedef struct {
 int gmupt_tree_cost_host(const gmupt_bvh_node* nodes, uint32_t n, gmupt_tree_cost_info* info, uint32_t threads);
 int gmupt_renderer_tree_cost(gmupt_renderer* r, gmupt_buffer* nodes_or_null, gmupt_tree_cost_info* info);
 
+/* ---- Tree optimisation: treelet restructuring of a node buffer, so that its tree cost falls (an extension; Karras & Aila 2013, "Fast
+ * Parallel Construction of High-Quality Bounding Volume Hierarchies", section 3).  It is meant for the tree gmupt_lbvh_build returns,
+ * between the build and gmupt_renderer_bind_scene, and is opt-in everywhere.  Only node records are read and written: the leaves keep
+ * their triangle ranges and boxes, so the triangle buffer and ref_triangle of the tree stay valid as they are.
+ *
+ * The rule (gmupt_tree_optimize_host and the kernels run the same statements, csrc/pt_treeopt.hpp; binary64 for areas and costs, nothing
+ * contracted; lo / hi and the union of two boxes as in the refit section).
+ *   Input.  N >= 1 records that gmupt_renderer_bind_scene accepts as a tree: the root is record 0, an inner node (isLeaf == 0) has both
+ *     children in (its own number, N), and every record but the root is the child of exactly one inner node -- otherwise
+ *     GMUPT_ERR_INVALID_ARGUMENT.  Depth: root 0, a child one more than its parent; an input deeper than 64: GMUPT_ERR_UNSUPPORTED.
+ *     passes in 1..8 (default 3), otherwise GMUPT_ERR_INVALID_ARGUMENT.
+ *   Working copy.  The records under their input numbers, the "working ids"; links may then point to any working id.
+ *   Cost, in the terms of the tree cost:  a(box) = (ex*ey + ey*ez) + ez*ex of the extents e = d > 0 ? d : 0, d = (double)max - (double)min.
+ *     C(leaf) = a * (double)(uint32_t)(right - left).   C(inner) = a * 2.0 + (C(left) + C(right)).
+ *   Processing an inner node X (all nodes below it have been processed in this pass):
+ *     1. Treelet.  Slot 0 = X's left child, slot 1 = its right child.  While there are fewer than 7 slots and one of them holds an inner
+ *        node: among those take the one whose box has the largest a -- slots scanned in ascending order, a later slot wins with a
+ *        larger a, or with an equal a and a lower working id.  That node joins the treelet's inner nodes; its left child takes its
+ *        slot, its right child the next free slot.  k = the number of slots at the end (2..7).
+ *     2. X's box becomes the union of its children's boxes (left, then right), pad0 = pad1 = pad2 = 0;
+ *        C(X) = a(X) * 2.0 + (C(left) + C(right)).  With k < 3 that is all.
+ *     3. Programme over the non-empty subsets s of the slots, bit j of s = slot j.  a[s] = a of the box of the lowest slot in s with the
+ *        other slots of s folded in by ascending slot (lo / hi per component).  c[{j}] = C(node of slot j).  For two slots or more:
+ *        c[s] = a[s] * 2.0 + min over p of (c[p] + c[s \ p]), p running over the proper subsets of s that contain the lowest slot of s, in
+ *        increasing numeric value; a candidate replaces the best one only when it is strictly smaller.  part[s] = that best p.
+ *     4. Only when c[all] < C(X), strictly, the treelet is rewritten (the current topology is one of the candidates and evaluates to the
+ *        same bits, so a tie keeps it).  Subset `all` is X, which keeps its id.  The k - 2 other inner ids of the old treelet are given,
+ *        ascending, to the other subsets of two slots or more in pre-order of the new topology: a subset s has the left child part[s]
+ *        and the right child s \ part[s]; a subset of one slot is that slot's node.  Then, children first, every inner node of the new
+ *        treelet gets the box, the padding and the cost of step 2; its C equals c[its subset] bit for bit.
+ *   A pass processes every inner node once, each after all nodes of its subtree.  A rewrite keeps the set of ids below X, and touches
+ *     no node outside it but X, so the result does not depend on the order among nodes that are not below one another.  The depths as
+ *     they were at the start of the pass are a valid schedule -- deepest first, any order within a depth -- because every id below X had a
+ *     larger depth than X then and still lies below X when X's turn comes; a post-order recursion is another.
+ *   After each pass the depths are recomputed.  A tree deeper than 64 after any pass: GMUPT_ERR_UNSUPPORTED (the pass does not rebalance).
+ *   Output.  After the last pass the nodes are numbered by ascending (depth, working id): root = 0, children above their parent (siblings
+ *     are not adjacent in general).  A leaf record is copied byte for byte; an inner record has its links renumbered.  Every inner box is
+ *     the union of its children's, so gmupt_bvh_refit_host changes no byte of an optimised tree whose leaf boxes follow the refit rule.
+ *   cost_before = C(root) of the input by step 2 alone (no rewrite), cost_after = C(root) after the last pass: what gmupt_tree_cost_host
+ *     reports as sum_inner + sum_leaf, up to the order of the sum.  cost_after <= cost_before.  treelets_rewritten counts step 4 over all
+ *     passes.  Non-finite boxes are no error; the comparisons above decide as they are written.
+ * gmupt_tree_optimize_host: the rule on host arrays, no device; nodes_out holds n records and may be the input array.  info (may be
+ *   NULL): ms = 0.  On an error nothing is written.
+ * gmupt_treeopt: an optimiser handle of a device.  It owns a stream, two events and its scratch (working copy, staged output, parent links,
+ *   costs, sort keys and storage: about 160 bytes per node), allocated by the first run, grown when a larger tree comes and kept.
+ * gmupt_treeopt_run: nodes = a GMUPT_BUFFER_BVH_NODES buffer of the optimiser's device; it is not modified.  The whole run is enqueued on
+ *   the optimiser's stream (it does not wait for other streams: finish the work that writes the buffer first, as gmupt_lbvh_build has when
+ *   it returns): per pass a depth launch, a radix sort of (depth, id) and one launch per depth 63 .. 0, in which one wave handles one
+ *   treelet with a[] and c[] in LDS; no launch waits for another workgroup of the same launch.  Then ONE small readback -- flags, depths,
+ *   the rewrite count, the two costs -- and a synchronise.  On success *nodes_out is a new GMUPT_BUFFER_BVH_NODES buffer the caller
+ *   destroys, bit for bit the array of gmupt_tree_optimize_host; on an error no buffer is created and *info is untouched.
+ *   info->ms = device time of the run's launches (hipEvents). */
+typedef struct { uint32_t passes; } gmupt_treeopt_params;
+void gmupt_treeopt_default_params(gmupt_treeopt_params* p);
+typedef struct { uint32_t num_nodes, depth_before, depth_after, treelets_rewritten; double cost_before, cost_after, ms; } gmupt_treeopt_info;   /* 40 bytes */
+int gmupt_tree_optimize_host(const gmupt_bvh_node* nodes, uint32_t n, const gmupt_treeopt_params* params /* may be NULL */,
+                             gmupt_bvh_node* nodes_out, gmupt_treeopt_info* info /* may be NULL */);
+typedef struct gmupt_treeopt gmupt_treeopt;
+int gmupt_treeopt_create(gmupt_device* dev, gmupt_treeopt** out);
+void gmupt_treeopt_destroy(gmupt_treeopt* h);
+int gmupt_treeopt_run(gmupt_treeopt* h, const gmupt_buffer* nodes, const gmupt_treeopt_params* params /* may be NULL */,
+                      gmupt_buffer** nodes_out, gmupt_treeopt_info* info /* may be NULL */);
+
 /* ---- Pose: linear-blend skinning and dense morph targets on the GPU (an extension; the reference's meshes never move).  It produces what
  * gmupt_normals_update, gmupt_renderer_refit and the motion-aware history start from -- "the vertex buffer holds the new pose" -- from a
  * few kilobytes per frame (joint matrices, target weights) instead of a vertex array.
