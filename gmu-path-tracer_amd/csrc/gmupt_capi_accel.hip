@@ -1,5 +1,5 @@
 // C-ABI of libgmupt.so: the traversal tables of a bound scene (upload, refit, debug reads) and the LBVH builder handle.
-#include "gmupt_internal.hpp"
+#include "gmupt_work.hpp"
 
 // GMUPT_TOP_ORDER=bfs and GMUPT_NODE_PAIRING=0 are A/B switches of the numbering (pt_travtables.cpp); results do not depend on them
 static TravOptions trav_options(bool wantWide, bool topOrderBfs, bool nodePairing)
@@ -203,40 +203,8 @@ extern "C" int gmupt_debug_wide_tables_addressable(uint32_t wide_nodes, uint32_t
 }
 
 // ------------------------------------------------------------------------------------------------ LBVH: the GPU builder (pt_lbvh.hip)
-extern "C" int gmupt_lbvh_create(gmupt_device* dev, gmupt_lbvh** out)
-{
-    if (!dev || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_lbvh_create: null argument");
-    *out = nullptr;
-    gmupt_lbvh* h = new (std::nothrow) gmupt_lbvh();
-    if (!h) return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_lbvh_create: out of host memory");
-    h->dev = dev;
-    hipError_t e = hipSetDevice(dev->id);
-    if (e == hipSuccess) e = hipStreamCreate(&h->stream);
-    if (e != hipSuccess) { gmupt_lbvh_destroy(h); return fail(GMUPT_ERR_HIP, "gmupt_lbvh_create: %s", hipGetErrorString(e)); }
-    *out = h;
-    return GMUPT_OK;
-}
-
-extern "C" void gmupt_lbvh_destroy(gmupt_lbvh* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->dev->id);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    delete h;
-}
-
-// a gmupt_buffer of `elems` elements filled from device memory on stream s (the caller synchronises)
-static int lbvh_output_buffer(gmupt_device* dev, gmupt_buffer_kind kind, size_t elems, const void* src, hipStream_t s, gmupt_buffer** out)
-{
-    hipError_t e = hipSuccess;
-    gmupt_buffer* b = buffer_alloc(dev, kind, elems, elems * kind_stride(kind), &e);
-    if (!b) return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_lbvh_build: out of host memory");
-    if (e == hipSuccess) e = hipMemsetAsync((char*)b->dptr + b->bytes, 0, 16, s);      // the slack
-    if (e == hipSuccess) e = hipMemcpyAsync(b->dptr, src, b->bytes, hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) { gmupt_buffer_destroy(b); return fail(GMUPT_ERR_HIP, "gmupt_lbvh_build(%zu bytes): %s", elems * kind_stride(kind), hipGetErrorString(e)); }
-    *out = b;
-    return GMUPT_OK;
-}
+extern "C" int gmupt_lbvh_create(gmupt_device* dev, gmupt_lbvh** out) { return work_create("gmupt_lbvh_create", dev, out); }
+extern "C" void gmupt_lbvh_destroy(gmupt_lbvh* h) { work_destroy(h); }
 
 extern "C" int gmupt_lbvh_build(gmupt_lbvh* h, const gmupt_buffer* vertices, const int32_t* device_indices, uint32_t num_tris, const uint32_t* device_vertex_material,
                                 const gmupt_lbvh_params* params, gmupt_buffer** nodes_out, gmupt_buffer** triangles_out, int32_t* device_ref_triangle,
@@ -252,21 +220,13 @@ extern "C" int gmupt_lbvh_build(gmupt_lbvh* h, const gmupt_buffer* vertices, con
     uint32_t L;
     GMUPT_TRY(lbvh_leaf_size("gmupt_lbvh_build", params, &L));
     HIP_TRY(hipSetDevice(h->dev->id));
-    // the sort's temporary storage is asked for per build (a host-only call): a smaller mesh is not assumed to need less than the capacity did.
-    // (capTris, sortTemp) is "large enough for every build so far", not "what the capacity needs": a later build may grow either once more
     size_t sortTemp = 0;
     HIP_TRY(lbvh_sort_temp_bytes(num_tris, &sortTemp));
-    if (num_tris > h->capTris || sortTemp > h->sortTemp) {
-        const uint32_t cap = std::max(num_tris, h->capTris);
-        h->capTris = 0; h->sortTemp = 0;                                        // should the scratch fail to grow
-        GMUPT_TRY(h->scratch.grow(h->stream, lbvh_scratch_layout(cap, sortTemp).total));
-        h->capTris = cap; h->sortTemp = sortTemp;
-    }
-    const LbScratch off = lbvh_scratch_layout(h->capTris, h->sortTemp);     // the parts are placed for the capacity: a smaller mesh uses the front of each
+    GMUPT_TRY(h->reserve(num_tris, sortTemp, lbvh_scratch_bytes));
 
     LbStaging st{};
     GMUPT_TRY(h->ev.start(h->stream));
-    HIP_TRY(launch_lbvh(h->scratch.ptr, off, h->sortTemp, (const float*)vertices->dptr, (uint32_t)vertices->elems, device_indices, num_tris, device_vertex_material, L, h->stream, st));
+    HIP_TRY(launch_lbvh(h->scratch.ptr, h->cap, h->sortTemp, (const float*)vertices->dptr, (uint32_t)vertices->elems, device_indices, num_tris, device_vertex_material, L, h->stream, st));
     GMUPT_TRY(h->ev.stop(h->stream));
     uint32_t back[16] = { 0 };
     GMUPT_TRY(copy_sync(back, st.words, sizeof(back), hipMemcpyDeviceToHost, h->stream));
@@ -275,14 +235,14 @@ extern "C" int gmupt_lbvh_build(gmupt_lbvh* h, const gmupt_buffer* vertices, con
     LbResult res{};
     res.numNodes = back[1]; res.numLeaves = (back[1] + 1) / 2; res.depth = back[2];
     for (int k = 0; k < 3; k++) { std::memcpy(&res.rootMin[k], &back[4 + k], 4); std::memcpy(&res.rootMax[k], &back[8 + k], 4); }
-    if (res.depth > kLbMaxDepth) return fail(GMUPT_ERR_UNSUPPORTED, "gmupt_lbvh_build: the tree is %u levels deep, the traversal stacks hold %u", res.depth, kLbMaxDepth);
+    if (res.depth > kMaxTreeDepth) return fail(GMUPT_ERR_UNSUPPORTED, "gmupt_lbvh_build: the tree is %u levels deep, the traversal stacks hold %u", res.depth, kMaxTreeDepth);
     if (res.numNodes == 0 || res.numNodes > 2 * (size_t)num_tris - 1) return fail(GMUPT_ERR_HIP, "gmupt_lbvh_build: the device reported %u nodes for %u triangles", res.numNodes, num_tris);
     float ms = 0.0f;
     GMUPT_TRY(h->ev.elapsed_ms(&ms));
 
     gmupt_buffer* nb = nullptr; gmupt_buffer* tb = nullptr;
-    int rc = lbvh_output_buffer(h->dev, GMUPT_BUFFER_BVH_NODES, res.numNodes, st.nodes, h->stream, &nb);
-    if (rc == GMUPT_OK) rc = lbvh_output_buffer(h->dev, GMUPT_BUFFER_TRIANGLES, num_tris, st.tris, h->stream, &tb);
+    int rc = output_buffer(h->dev, GMUPT_BUFFER_BVH_NODES, res.numNodes, st.nodes, h->stream, "gmupt_lbvh_build", &nb);
+    if (rc == GMUPT_OK) rc = output_buffer(h->dev, GMUPT_BUFFER_TRIANGLES, num_tris, st.tris, h->stream, "gmupt_lbvh_build", &tb);
     hipError_t e = hipSuccess;
     if (rc == GMUPT_OK && device_ref_triangle) e = hipMemcpyAsync(device_ref_triangle, st.ref, (size_t)num_tris * 4, hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);

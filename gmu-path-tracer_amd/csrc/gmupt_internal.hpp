@@ -161,17 +161,7 @@ struct gmupt_temporal {
     EventPair ev;
 };
 
-// the builder handle: a stream, two events and the scratch of the largest mesh built so far
-struct gmupt_lbvh {
-    gmupt_device* dev; hipStream_t stream = nullptr; EventPair ev; DevMem scratch; uint32_t capTris = 0; size_t sortTemp = 0;
-    ~gmupt_lbvh() { if (stream) (void)hipStreamDestroy(stream); }        // gmupt_lbvh_destroy has synchronised it
-};
-
-// the optimiser handle: a stream, two events and the scratch of the largest tree optimised so far
-struct gmupt_treeopt {
-    gmupt_device* dev; hipStream_t stream = nullptr; EventPair ev; DevMem scratch; uint32_t capNodes = 0; size_t sortTemp = 0;
-    ~gmupt_treeopt() { if (stream) (void)hipStreamDestroy(stream); }     // gmupt_treeopt_destroy has synchronised it
-};
+// (the builder and optimiser handles, gmupt_lbvh and gmupt_treeopt: gmupt_work.hpp)
 
 // the adjacency of one index list for a renderer's vertices (gmupt_normals_*): device memory laid out by normals_layout (pt_normals.hip)
 struct gmupt_normals {

@@ -8,7 +8,7 @@
 #include "../../include/gmupt.h"
 
 namespace gmupt {
-struct RenderParams; struct SceneView; struct DnParams; struct TpParams; struct TpPrev; struct RfArgs; struct LbScratch; struct LbStaging; struct NmLayout; struct NmArgs; struct TcPartial; struct PsLayout; struct PsArgs; struct ToScratch;   // pt_*.hpp
+struct RenderParams; struct SceneView; struct DnParams; struct TpParams; struct TpPrev; struct RfArgs; struct LbStaging; struct NmLayout; struct NmArgs; struct TcPartial; struct PsLayout; struct PsArgs;   // pt_*.hpp
 
 void launch_clear(const RenderParams& p, hipStream_t s);
 void launch_logic(const RenderParams& p, hipStream_t s);
@@ -46,8 +46,8 @@ uint32_t launch_refit_boxes(const RfArgs& a, const std::vector<uint32_t>& levelO
 void launch_refit_tables(const RfArgs& a, hipStream_t s);
 void refit_host(gmupt_bvh_node* nodes, size_t N, const gmupt_triangle* tris, const float* verts, int threads);
 hipError_t lbvh_sort_temp_bytes(uint32_t n, size_t* bytes);
-LbScratch lbvh_scratch_layout(uint32_t n, size_t sortTemp);
-hipError_t launch_lbvh(void* scratch, const LbScratch& off, size_t sortTemp, const float* verts, uint32_t numVerts, const int32_t* indices, uint32_t n,
+size_t lbvh_scratch_bytes(uint32_t cap, size_t sortTemp);
+hipError_t launch_lbvh(void* scratch, uint32_t cap, size_t sortTemp, const float* verts, uint32_t numVerts, const int32_t* indices, uint32_t n,
                        const uint32_t* vertexMaterial, uint32_t maxLeaf, hipStream_t s, LbStaging& st);
 hipError_t normals_sort_temp_bytes(uint32_t numTris, uint32_t numVerts, size_t* bytes);
 NmLayout normals_layout(uint32_t numTris, uint32_t numVerts, size_t sortTemp);
@@ -59,7 +59,7 @@ void launch_pose_update(const PsArgs& a, hipStream_t s);
 size_t tree_cost_scratch_partials(uint32_t n);
 const TcPartial* launch_tree_cost(const gmupt_bvh_node* nodes, uint32_t n, TcPartial* scratch, hipStream_t s);
 hipError_t treeopt_sort_temp_bytes(uint32_t n, size_t* bytes);
-ToScratch treeopt_scratch_layout(uint32_t n, size_t sortTemp);
-hipError_t launch_treeopt(void* scratch, const ToScratch& off, size_t sortTemp, const gmupt_bvh_node* nodes, uint32_t n, uint32_t passes, hipStream_t s,
+size_t treeopt_scratch_bytes(uint32_t cap, size_t sortTemp);
+hipError_t launch_treeopt(void* scratch, uint32_t cap, size_t sortTemp, const gmupt_bvh_node* nodes, uint32_t n, uint32_t passes, hipStream_t s,
                           const void** words, const void** staged);
 }

@@ -60,9 +60,9 @@ std::string lbvh_build_host(const float* verts, uint32_t numVerts, const int32_t
         tree.push_back({ r.first, s, r.depth + 1, -1 });
         tree.push_back({ s + 1, r.last, r.depth + 1, -1 });
     }
-    if (depth > kLbMaxDepth) {
+    if (depth > kMaxTreeDepth) {
         *status = GMUPT_ERR_UNSUPPORTED;
-        return "the tree is " + std::to_string(depth) + " levels deep, the traversal stacks hold " + std::to_string(kLbMaxDepth);
+        return "the tree is " + std::to_string(depth) + " levels deep, the traversal stacks hold " + std::to_string(kMaxTreeDepth);
     }
 
     // rule 8: records

@@ -3,36 +3,33 @@
 // synchronisation in between; every kernel is safe on invalid input (an index outside the vertex array is flagged and never followed).
 //
 //   k_lb_bounds   one thread per triangle: indices in range, vertices finite (else a flag bit), centre; min / max of the block's centres
-//   k_lb_bounds2  one block: min / max over the blocks' partial results -> cmin, cmax
+//                 (lb_block_minmax)
+//   k_lb_bounds2  one block: min / max over the blocks' partial results (lb_block_minmax again) -> cmin, cmax
 //   k_lb_keys     one thread per triangle: the 63-bit Morton key of its centre, value = its index
 //   (sort)        rocPRIM radix sort of (key, index) on bits 0..62: stable, so equal keys keep index order
 //   k_lb_hier     one thread per inner node of the binary radix tree (Karras 2012): range, split, parent links of both children.
 //                 Node ids: inner node i = i (0 = root), sorted position p = numTris - 1 + p
-//   k_lb_depth    one thread per node id: depth by walking the parent links; kept = root, or the parent's range holds more than L
-//                 positions; sort key = depth << 32 | first for a kept node, all ones for a dropped one
-//   (sort)        rocPRIM radix sort of (that key, node id) on bits 0..39: the sorted position of a kept node IS its number (rule 7)
-//   k_lb_levels   one thread per sorted entry: number of each node id, where each depth starts, node count, depth
+//   k_lb_depth    one thread per node id: depth by walking the parent links (level_depth); kept = root, or the parent's range holds
+//                 more than L positions; sort key = level_key(depth, first), which leaves a dropped node out
+//   (sort)        level_sort of (that key, node id): the sorted position of a kept node IS its number (rule 7)
+//   k_lb_levels   one thread per sorted entry: where each depth starts (level_offsets); number of each node id, node count, depth
 //   k_lb_tris     one thread per sorted position: triangle record, ref_triangle
 //   k_lb_nodes    one thread per kept node: links; a leaf also gets its box (rf_leaf_box on the records just written)
 //   k_lb_level    inner boxes, one launch per depth 63 .. 0 on a fixed grid that strides over the nodes of that depth (the range comes
 //                 from device memory, an absent depth is an empty range): children are one level down, so no atomics and no waiting
 #include "pt_lbvh.hpp"
 #include "pt_launch.hpp"
+#include "pt_levels.hpp"          // the level step, the scratch carver, rocPRIM's radix sort
 
-#include <algorithm>
 #include <cstring>
-
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace gmupt {
 
 constexpr int kLbBlock = 256;
-constexpr uint32_t kLbDropped = 255u;            // depth byte of a node below a leaf (a kept node's depth is at most 96; k_lb_depth cuts its walk off at 128 steps)
 constexpr uint32_t kLbLevelBlocks = 1024;        // grid of k_lb_level
 
-// device words of a build: [0] flags, [1] kept nodes, [2] depth, [4..11] the root's box rows, [16..21] cmin, cmax, [32 .. 32 + 256) levelOff
-constexpr uint32_t kLbWords = 32 + 256;
-
+// device words of a build (kLevelWords of them): [0] flags, [1] kept nodes, [2] depth, [4..11] the root's box rows, [16..21] cmin, cmax,
+// then levelOff (pt_levels.hpp)
 struct LbArgs {
     const float* verts; uint32_t numVerts;
     const int32_t* indices; uint32_t n;
@@ -55,9 +52,26 @@ __device__ __forceinline__ bool lb_load_tri(const LbArgs& a, size_t i, int32_t* 
     return (uint32_t)t[0] < a.numVerts && (uint32_t)t[1] < a.numVerts && (uint32_t)t[2] < a.numVerts;
 }
 
-__global__ __launch_bounds__(kLbBlock) void k_lb_bounds(LbArgs a)
+// The block's min (rows 0..2) and max (rows 3..5) of every thread's mn / mx, by halving in LDS: the result of row r is at [r][0]
+using LbRow = float[kLbBlock];
+__device__ __forceinline__ const LbRow* lb_block_minmax(const float* mn, const float* mx)
 {
     __shared__ float red[6][kLbBlock];
+    for (int k = 0; k < 3; k++) { red[k][threadIdx.x] = mn[k]; red[3 + k][threadIdx.x] = mx[k]; }
+    __syncthreads();
+    for (int s = kLbBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int k = 0; k < 3; k++) {
+                red[k][threadIdx.x] = rf_lo(red[k][threadIdx.x], red[k][threadIdx.x + s]);
+                red[3 + k][threadIdx.x] = rf_hi(red[3 + k][threadIdx.x], red[3 + k][threadIdx.x + s]);
+            }
+        __syncthreads();
+    }
+    return red;
+}
+
+__global__ __launch_bounds__(kLbBlock) void k_lb_bounds(LbArgs a)
+{
     const size_t i = (size_t)blockIdx.x * kLbBlock + threadIdx.x;
     const float inf = u2f(0x7F800000u);
     float mn[3] = { inf, inf, inf }, mx[3] = { -inf, -inf, -inf };
@@ -78,36 +92,17 @@ __global__ __launch_bounds__(kLbBlock) void k_lb_bounds(LbArgs a)
         }
         if (bad) atomicOr(a.words, bad);
     }
-    for (int k = 0; k < 3; k++) { red[k][threadIdx.x] = mn[k]; red[3 + k][threadIdx.x] = mx[k]; }
-    __syncthreads();
-    for (int s = kLbBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int k = 0; k < 3; k++) {
-                red[k][threadIdx.x] = rf_lo(red[k][threadIdx.x], red[k][threadIdx.x + s]);
-                red[3 + k][threadIdx.x] = rf_hi(red[3 + k][threadIdx.x], red[3 + k][threadIdx.x + s]);
-            }
-        __syncthreads();
-    }
+    const LbRow* red = lb_block_minmax(mn, mx);
     if (threadIdx.x < 6 && blockIdx.x < a.numPartial) a.partial[6 * (size_t)blockIdx.x + threadIdx.x] = red[threadIdx.x][0];
 }
 
 __global__ __launch_bounds__(kLbBlock) void k_lb_bounds2(LbArgs a)
 {
-    __shared__ float red[6][kLbBlock];
     const float inf = u2f(0x7F800000u);
     float mn[3] = { inf, inf, inf }, mx[3] = { -inf, -inf, -inf };
     for (size_t b = threadIdx.x; b < a.numPartial; b += kLbBlock)
         for (int k = 0; k < 3; k++) { mn[k] = rf_lo(mn[k], a.partial[6 * b + k]); mx[k] = rf_hi(mx[k], a.partial[6 * b + 3 + k]); }
-    for (int k = 0; k < 3; k++) { red[k][threadIdx.x] = mn[k]; red[3 + k][threadIdx.x] = mx[k]; }
-    __syncthreads();
-    for (int s = kLbBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int k = 0; k < 3; k++) {
-                red[k][threadIdx.x] = rf_lo(red[k][threadIdx.x], red[k][threadIdx.x + s]);
-                red[3 + k][threadIdx.x] = rf_hi(red[3 + k][threadIdx.x], red[3 + k][threadIdx.x + s]);
-            }
-        __syncthreads();
-    }
+    const LbRow* red = lb_block_minmax(mn, mx);
     if (threadIdx.x < 6) a.words[16 + threadIdx.x] = f2u(red[threadIdx.x][0]);
 }
 
@@ -159,12 +154,11 @@ __global__ __launch_bounds__(kLbBlock) void k_lb_depth(LbArgs a)
     const int64_t n = a.n, M = 2 * n - 1;
     if (id >= M) return;
     const uint32_t first = id < n - 1 ? (uint32_t)a.range[id].x : (uint32_t)(id - (n - 1));
-    uint32_t depth = 0;
-    const int32_t par = id == 0 ? -1 : a.parent[id];
-    for (int32_t p = par; p >= 0 && (int64_t)p < n - 1 && depth < 128u; p = p == 0 ? -1 : a.parent[p]) depth++;
+    const int32_t par = a.parent[id];                                  // the root's is -1 (k_lb_hier)
+    const uint32_t depth = level_depth(a.parent, par, (uint32_t)(n - 1));
     bool kept = id == 0;
     if (par >= 0 && (int64_t)par < n - 1) { const int2 r = a.range[par]; kept = (uint32_t)(r.y - r.x + 1) > a.maxLeaf; }
-    a.keys2In[id] = kept ? ((uint64_t)depth << 32) | first : ~0ull;
+    a.keys2In[id] = level_key(kept, depth, first);
     a.vals2In[id] = (uint32_t)id;
 }
 
@@ -173,16 +167,9 @@ __global__ __launch_bounds__(kLbBlock) void k_lb_levels(LbArgs a)
     const int64_t pos = (int64_t)blockIdx.x * kLbBlock + threadIdx.x;
     const int64_t M = 2 * (int64_t)a.n - 1;
     if (pos >= M) return;
-    uint32_t* levelOff = a.words + 32;
-    const uint32_t d = (uint32_t)(a.keys2[pos] >> 32) & 0xFFu;
-    const uint32_t dprev = pos ? (uint32_t)(a.keys2[pos - 1] >> 32) & 0xFFu : kLbDropped;
-    if (d != kLbDropped) {
-        a.number[a.ids[pos]] = (uint32_t)pos;
-        if (pos == 0 || d != dprev) levelOff[d] = (uint32_t)pos;
-        if (pos == M - 1) { a.words[1] = (uint32_t)M; a.words[2] = d; levelOff[d + 1] = (uint32_t)M; }
-    } else if (pos && dprev != kLbDropped) {
-        a.words[1] = (uint32_t)pos; a.words[2] = dprev; levelOff[dprev + 1] = (uint32_t)pos;
-    }
+    const LevelEntry e = level_offsets(a.keys2, (size_t)pos, (size_t)M, a.words + kLevelWord);
+    if (e.depth != kLevelDropped) a.number[a.ids[pos]] = (uint32_t)pos;
+    if (e.count) { a.words[1] = e.count; a.words[2] = e.last; }
 }
 
 __global__ __launch_bounds__(kLbBlock) void k_lb_tris(LbArgs a)
@@ -204,7 +191,7 @@ __global__ __launch_bounds__(kLbBlock) void k_lb_nodes(LbArgs a)
     const int64_t n = a.n, M = 2 * n - 1;
     if (pos >= M) return;
     const uint64_t key = a.keys2[pos];
-    if (((uint32_t)(key >> 32) & 0xFFu) == kLbDropped) return;
+    if (level_key_depth(key) == kLevelDropped) return;
     const int64_t id = a.ids[pos];
     if (id >= M) return;
     const int64_t first = (uint32_t)key;
@@ -227,7 +214,7 @@ __global__ __launch_bounds__(kLbBlock) void k_lb_nodes(LbArgs a)
 
 __global__ __launch_bounds__(kLbBlock) void k_lb_level(LbArgs a, uint32_t depth)
 {
-    const uint32_t begin = a.words[32 + depth], end = a.words[32 + depth + 1];
+    const uint32_t begin = a.words[kLevelWord + depth], end = a.words[kLevelWord + depth + 1];
     const uint32_t kept = a.words[1];
     for (size_t i = (size_t)begin + (size_t)blockIdx.x * kLbBlock + threadIdx.x; i < end && i < kept; i += (size_t)gridDim.x * kLbBlock) {
         const int4 link = a.nodes[i].link;
@@ -239,69 +226,57 @@ __global__ __launch_bounds__(kLbBlock) void k_lb_level(LbArgs a, uint32_t depth)
     }
 }
 
-static inline uint32_t lb_grid(size_t n) { return (uint32_t)((n + kLbBlock - 1) / kLbBlock); }
-static inline size_t lb_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline uint32_t lb_grid(size_t n) { return grid_for(n, kLbBlock); }
 
-// ---- host side (gmupt_capi.hip: gmupt_lbvh_build) ----
+// ---- host side (gmupt_capi_accel.hip: gmupt_lbvh_build) ----
 
 // bytes of temporary storage the two sorts of a build of n triangles need
 hipError_t lbvh_sort_temp_bytes(uint32_t n, size_t* bytes)
 {
     size_t b1 = 0, b2 = 0;
-    const size_t M = 2 * (size_t)n - 1;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, b1, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, 63u, (hipStream_t)0);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, b2, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, M, 0u, 40u, (hipStream_t)0);
-    *bytes = lb_align(std::max(std::max(b1, b2), (size_t)256));
+    if (e == hipSuccess) e = level_sort_temp_bytes(2 * (size_t)n - 1, &b2);
+    *bytes = std::max(scratch_align(std::max(b1, (size_t)256)), b2);
     return e;
 }
 
-// The scratch of a build of up to n triangles, one allocation: every part of LbScratch placed at a 256-byte boundary, the sort's temporary
-// storage (sortTemp bytes) last.
-LbScratch lbvh_scratch_layout(uint32_t n, size_t sortTemp)
+// The parts of a build's scratch, taken for a capacity of `cap` triangles; returns the sort's temporary storage (sortTemp bytes), the
+// last part.  Staged outputs: nodes, tris, ref.
+static void* lbvh_carve(Scratch& sc, uint32_t cap, size_t sortTemp, LbArgs& a)
 {
-    const size_t M = 2 * (size_t)n - 1, blocks = lb_grid(n);
-    LbScratch L{};
-    size_t total = 0;
-    auto place = [&total](size_t& off, size_t bytes) { off = total; total += lb_align(bytes); };
-    place(L.words, kLbWords * 4);
-    place(L.partial, blocks * 24);
-    place(L.keysIn, (size_t)n * 8);
-    place(L.keys, (size_t)n * 8);
-    place(L.valsIn, (size_t)n * 4);
-    place(L.src, (size_t)n * 4);
-    place(L.keys2In, M * 8);
-    place(L.keys2, M * 8);
-    place(L.vals2In, M * 4);
-    place(L.ids, M * 4);
-    place(L.parent, M * 4);
-    place(L.split, (size_t)n * 4);
-    place(L.range, (size_t)n * 8);
-    place(L.number, M * 4);
-    place(L.nodes, M * sizeof(DNode));
-    place(L.tris, (size_t)n * sizeof(gmupt_triangle) + 16);
-    place(L.ref, (size_t)n * 4);
-    place(L.sortTemp, sortTemp);
-    L.total = total;
-    return L;
+    const size_t n = cap, M = 2 * n - 1;
+    a.words = sc.take<uint32_t>(kLevelWords);
+    a.partial = sc.take<float>(6 * (size_t)lb_grid(n));
+    a.keysIn = sc.take<uint64_t>(n); a.keys = sc.take<uint64_t>(n); a.valsIn = sc.take<uint32_t>(n); a.src = sc.take<uint32_t>(n);
+    a.keys2In = sc.take<uint64_t>(M); a.keys2 = sc.take<uint64_t>(M); a.vals2In = sc.take<uint32_t>(M); a.ids = sc.take<uint32_t>(M);
+    a.parent = sc.take<int32_t>(M); a.split = sc.take<int32_t>(n); a.range = sc.take<int2>(n); a.number = sc.take<uint32_t>(M);
+    a.nodes = sc.take<DNode>(M);
+    a.tris = sc.take<gmupt_triangle>(n + 1);                           // 16 bytes of slack, as a triangle buffer has
+    a.ref = sc.take<int32_t>(n);
+    return sc.take<char>(sortTemp);
 }
 
-// enqueues the whole build; the caller reads kLbWords back from st.words afterwards
-hipError_t launch_lbvh(void* scratch, const LbScratch& off, size_t sortTemp, const float* verts, uint32_t numVerts, const int32_t* indices, uint32_t n,
+size_t lbvh_scratch_bytes(uint32_t cap, size_t sortTemp)
+{
+    Scratch sc(nullptr);
+    LbArgs a{};
+    lbvh_carve(sc, cap, sortTemp, a);
+    return sc.used;
+}
+
+// enqueues the whole build in a scratch of lbvh_scratch_bytes(cap, sortTemp), cap >= n; the caller reads the words back from st.words afterwards
+hipError_t launch_lbvh(void* scratch, uint32_t cap, size_t sortTemp, const float* verts, uint32_t numVerts, const int32_t* indices, uint32_t n,
                        const uint32_t* vertexMaterial, uint32_t maxLeaf, hipStream_t s, LbStaging& st)
 {
-    char* base = static_cast<char*>(scratch);
+    Scratch sc(scratch);
     LbArgs a{};
     a.verts = verts; a.numVerts = numVerts; a.indices = indices; a.n = n; a.vertexMaterial = vertexMaterial; a.maxLeaf = maxLeaf;
-    a.words = (uint32_t*)(base + off.words); a.partial = (float*)(base + off.partial); a.numPartial = lb_grid(n);
-    a.keysIn = (uint64_t*)(base + off.keysIn); a.keys = (uint64_t*)(base + off.keys); a.valsIn = (uint32_t*)(base + off.valsIn); a.src = (uint32_t*)(base + off.src);
-    a.keys2In = (uint64_t*)(base + off.keys2In); a.keys2 = (uint64_t*)(base + off.keys2); a.vals2In = (uint32_t*)(base + off.vals2In); a.ids = (uint32_t*)(base + off.ids);
-    a.parent = (int32_t*)(base + off.parent); a.split = (int32_t*)(base + off.split); a.range = (int2*)(base + off.range); a.number = (uint32_t*)(base + off.number);
-    a.nodes = (DNode*)(base + off.nodes); a.tris = (gmupt_triangle*)(base + off.tris); a.ref = (int32_t*)(base + off.ref);
-    void* temp = base + off.sortTemp;
+    a.numPartial = lb_grid(n);
+    void* temp = lbvh_carve(sc, cap, sortTemp, a);
     st.words = a.words; st.nodes = a.nodes; st.tris = a.tris; st.ref = a.ref;
     const size_t M = 2 * (size_t)n - 1;
 
-    hipError_t e = hipMemsetAsync(a.words, 0, kLbWords * 4, s);
+    hipError_t e = hipMemsetAsync(a.words, 0, kLevelWords * 4, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_lb_bounds, dim3(lb_grid(n)), dim3(kLbBlock), 0, s, a);
     hipLaunchKernelGGL(k_lb_bounds2, dim3(1), dim3(kLbBlock), 0, s, a);
@@ -312,13 +287,13 @@ hipError_t launch_lbvh(void* scratch, const LbScratch& off, size_t sortTemp, con
     hipLaunchKernelGGL(k_lb_hier, dim3(lb_grid(n)), dim3(kLbBlock), 0, s, a);
     hipLaunchKernelGGL(k_lb_depth, dim3(lb_grid(M)), dim3(kLbBlock), 0, s, a);
     tb = sortTemp;
-    e = rocprim::radix_sort_pairs(temp, tb, a.keys2In, a.keys2, a.vals2In, a.ids, M, 0u, 40u, s);
+    e = level_sort(temp, tb, a.keys2In, a.keys2, a.vals2In, a.ids, M, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_lb_levels, dim3(lb_grid(M)), dim3(kLbBlock), 0, s, a);
     hipLaunchKernelGGL(k_lb_tris, dim3(lb_grid(n)), dim3(kLbBlock), 0, s, a);
     hipLaunchKernelGGL(k_lb_nodes, dim3(lb_grid(M)), dim3(kLbBlock), 0, s, a);
     const uint32_t levelGrid = std::min(lb_grid(M), kLbLevelBlocks);
-    for (uint32_t d = kLbMaxDepth; d-- > 0;) hipLaunchKernelGGL(k_lb_level, dim3(levelGrid), dim3(kLbBlock), 0, s, a, d);
+    for (uint32_t d = kMaxTreeDepth; d-- > 0;) hipLaunchKernelGGL(k_lb_level, dim3(levelGrid), dim3(kLbBlock), 0, s, a, d);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     return hipMemcpyAsync(a.words + 4, a.nodes, 32, hipMemcpyDeviceToDevice, s);      // the root's box rows next to the counts

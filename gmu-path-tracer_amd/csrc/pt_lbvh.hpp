@@ -8,16 +8,12 @@
 namespace gmupt {
 
 constexpr uint32_t kLbMaxLeaf = 64;            // params.max_leaf_size is in 1 .. kLbMaxLeaf
-constexpr uint32_t kLbMaxDepth = 64;           // the traversal stacks hold 64 entries: a deeper tree is GMUPT_ERR_UNSUPPORTED
+constexpr uint32_t kMaxTreeDepth = 64;         // the traversal stacks hold 64 entries: a deeper tree is GMUPT_ERR_UNSUPPORTED (builder and optimiser)
 constexpr uint32_t kLbMaxTris = 1u << 30;      // 2 * num_tris - 1 node ids fit an int32
 constexpr uint32_t kLbGrid = 2097152u;         // 2^21 cells per axis, 63-bit keys
 constexpr uint32_t kLbFlagNonFinite = 1u, kLbFlagBadIndex = 2u;
 
-// Byte offsets of the parts of a builder's scratch (one allocation, pt_lbvh.hip: lbvh_scratch_layout places them, launch_lbvh reads them
-// by name) and the allocation's size.  Staged outputs: nodes, tris, ref.
-struct LbScratch {
-    size_t words, partial, keysIn, keys, valsIn, src, keys2In, keys2, vals2In, ids, parent, split, range, number, nodes, tris, ref, sortTemp, total;
-};
+// what launch_lbvh (pt_lbvh.hip) leaves in the builder's scratch for the caller: the device words and the staged outputs
 struct LbStaging { const void* words; const void* nodes; const void* tris; const void* ref; };
 
 GM_HD bool lb_finite(float x) { return (f2u(x) & 0x7F800000u) != 0x7F800000u; }

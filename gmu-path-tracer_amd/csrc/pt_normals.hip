@@ -15,6 +15,7 @@
 // indices without a further check.  All arithmetic is pt_normals.hpp, which gmupt_vertex_normals_host runs too.
 #include "pt_normals.hpp"
 #include "pt_launch.hpp"
+#include "pt_scratch.hpp"
 
 #include <algorithm>
 
@@ -81,8 +82,7 @@ __global__ __launch_bounds__(kNmBlock) void k_nm_verts(NmArgs a)
     *reinterpret_cast<float3*>(a.props + v) = make_float3(n[0], n[1], n[2]);
 }
 
-static inline uint32_t nm_grid(size_t n) { return (uint32_t)((n + kNmBlock - 1) / kNmBlock); }
-static inline size_t nm_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline uint32_t nm_grid(size_t n) { return grid_for(n, kNmBlock); }
 static inline unsigned nm_key_bits(uint32_t numVerts) { unsigned b = 1; while (b < 32 && (numVerts >> b)) b++; return b; }   // the keys are 0 .. numVerts
 
 // ---- host side (gmupt_capi_normals.hip) ----
@@ -92,7 +92,7 @@ hipError_t normals_sort_temp_bytes(uint32_t numTris, uint32_t numVerts, size_t* 
     size_t b = 0;
     const hipError_t e = rocprim::radix_sort_pairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
                                                    3 * (size_t)numTris, 0u, nm_key_bits(numVerts), (hipStream_t)0);
-    *bytes = nm_align(std::max(b, (size_t)256));
+    *bytes = scratch_align(std::max(b, (size_t)256));
     return e;
 }
 
@@ -101,7 +101,7 @@ NmLayout normals_layout(uint32_t numTris, uint32_t numVerts, size_t sortTemp)
     const size_t C = 3 * (size_t)numTris;
     NmLayout L{};
     size_t total = 0;
-    auto place = [&total](size_t& off, size_t bytes) { off = total; total += nm_align(bytes); };
+    auto place = [&total](size_t& off, size_t bytes) { off = total; total += scratch_align(bytes); };
     place(L.words, kNmWords * 4);
     place(L.indices, C * 4);
     place(L.corners, C * 4);

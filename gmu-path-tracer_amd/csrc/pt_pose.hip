@@ -18,6 +18,7 @@
 // gmupt_pose_host runs too.
 #include "pt_pose.hpp"
 #include "pt_launch.hpp"
+#include "pt_scratch.hpp"
 
 #include <algorithm>
 
@@ -108,8 +109,7 @@ template <bool kLds> __global__ __launch_bounds__(kPsBlock) void k_ps_pose(PsArg
     }
 }
 
-static inline uint32_t ps_grid(size_t n) { return (uint32_t)((n + kPsBlock - 1) / kPsBlock); }
-static inline size_t ps_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline uint32_t ps_grid(size_t n) { return grid_for(n, kPsBlock); }
 
 // ---- host side (gmupt_capi_pose.hip) ----
 
@@ -119,7 +119,7 @@ PsLayout pose_layout(uint32_t numVerts, uint32_t influences, uint32_t numJoints,
     L.stride = ((size_t)numVerts + 63) & ~(size_t)63;
     const size_t K = numJoints ? influences : 0;
     size_t total = 0;
-    auto place = [&total](size_t& off, size_t bytes) { off = total; total += ps_align(bytes); };
+    auto place = [&total](size_t& off, size_t bytes) { off = total; total += scratch_align(bytes); };
     place(L.words, kPsWords * 4);
     place(L.rest, 3 * L.stride * 4);
     place(L.weights, K * L.stride * 4);

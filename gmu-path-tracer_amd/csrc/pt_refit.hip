@@ -14,6 +14,7 @@
 #include "pt_refit.hpp"
 #include "pt_denoise.hpp"
 #include "pt_launch.hpp"
+#include "pt_scratch.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -151,24 +152,22 @@ __global__ __launch_bounds__(kRfBlock) void k_rf_wide(RfArgs a)
     }
 }
 
-static inline uint32_t rf_grid(size_t n) { return (uint32_t)((n + kRfBlock - 1) / kRfBlock); }
-
 // ---- host launchers (gmupt_capi.hip: gmupt_renderer_refit) ----
 void launch_refit_check(const RfArgs& a, hipStream_t s)
 {
-    if (a.numTris) hipLaunchKernelGGL(k_rf_finite, dim3(rf_grid(a.numTris)), dim3(kRfBlock), 0, s, a);
+    if (a.numTris) hipLaunchKernelGGL(k_rf_finite, dim3(grid_for(a.numTris, kRfBlock)), dim3(kRfBlock), 0, s, a);
 }
 
 // node boxes of the caller's buffer; levelOff[h] .. levelOff[h + 1] are the nodes of height h + 1 in a.levelNodes.  Returns the launches of
 // the inner part.
 uint32_t launch_refit_boxes(const RfArgs& a, const std::vector<uint32_t>& levelOff, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_rf_leaves, dim3(rf_grid(a.numNodes)), dim3(kRfBlock), 0, s, a);
+    hipLaunchKernelGGL(k_rf_leaves, dim3(grid_for(a.numNodes, kRfBlock)), dim3(kRfBlock), 0, s, a);
     uint32_t launches = 0;
     for (size_t h = 0; h + 1 < levelOff.size(); h++) {
         const uint32_t first = levelOff[h], count = levelOff[h + 1] - first;
         if (!count) continue;
-        hipLaunchKernelGGL(k_rf_level, dim3(rf_grid(count)), dim3(kRfBlock), 0, s, a, first, count);
+        hipLaunchKernelGGL(k_rf_level, dim3(grid_for(count, kRfBlock)), dim3(kRfBlock), 0, s, a, first, count);
         launches++;
     }
     return launches;
@@ -177,10 +176,10 @@ uint32_t launch_refit_boxes(const RfArgs& a, const std::vector<uint32_t>& levelO
 // the traversal tables from the refitted boxes; a.wnodes == nullptr: no wide copy, the pair and wide parts are skipped
 void launch_refit_tables(const RfArgs& a, hipStream_t s)
 {
-    if (a.numTris) hipLaunchKernelGGL(k_rf_tris, dim3(rf_grid(a.numTris)), dim3(kRfBlock), 0, s, a);
-    if (a.wnodes && a.numPairs) hipLaunchKernelGGL(k_rf_pairs, dim3(rf_grid(a.numPairs)), dim3(kRfBlock), 0, s, a);
-    if (a.numPacked) hipLaunchKernelGGL(k_rf_nodes, dim3(rf_grid(a.numPacked)), dim3(kRfBlock), 0, s, a);
-    if (a.wnodes && a.wideCount) hipLaunchKernelGGL(k_rf_wide, dim3(rf_grid(std::max((size_t)a.wideCount * 8, (size_t)a.numOpened))), dim3(kRfBlock), 0, s, a);
+    if (a.numTris) hipLaunchKernelGGL(k_rf_tris, dim3(grid_for(a.numTris, kRfBlock)), dim3(kRfBlock), 0, s, a);
+    if (a.wnodes && a.numPairs) hipLaunchKernelGGL(k_rf_pairs, dim3(grid_for(a.numPairs, kRfBlock)), dim3(kRfBlock), 0, s, a);
+    if (a.numPacked) hipLaunchKernelGGL(k_rf_nodes, dim3(grid_for(a.numPacked, kRfBlock)), dim3(kRfBlock), 0, s, a);
+    if (a.wnodes && a.wideCount) hipLaunchKernelGGL(k_rf_wide, dim3(grid_for(std::max((size_t)a.wideCount * 8, (size_t)a.numOpened), kRfBlock)), dim3(kRfBlock), 0, s, a);
 }
 
 // ---- the host refit (gmupt_bvh_refit_host) on a validated tree: leaves in chunks on up to `threads` std::threads (every leaf reads only

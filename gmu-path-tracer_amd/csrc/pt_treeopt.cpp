@@ -53,9 +53,9 @@ std::string tree_optimize_host(const gmupt_bvh_node* nodes, uint32_t n, uint32_t
     std::vector<int32_t> order;
     order.reserve(N);
     const uint32_t depthBefore = to_depths(w, depth, order);
-    if (depthBefore > kToMaxDepth) {
+    if (depthBefore > kMaxTreeDepth) {
         *status = GMUPT_ERR_UNSUPPORTED;
-        return "the tree is " + std::to_string(depthBefore) + " levels deep, the traversal stacks hold " + std::to_string(kToMaxDepth);
+        return "the tree is " + std::to_string(depthBefore) + " levels deep, the traversal stacks hold " + std::to_string(kMaxTreeDepth);
     }
 
     std::vector<double> cost(N, 0.0), cost0(N, 0.0);
@@ -80,9 +80,9 @@ std::string tree_optimize_host(const gmupt_bvh_node* nodes, uint32_t n, uint32_t
             if (c[(1u << t.k) - 1u] < cX) { to_rewrite(w.data(), parent.data(), cost.data(), X, t, c, part); rewritten++; }
         }
         depthNow = to_depths(w, depth, order);
-        if (depthNow > kToMaxDepth) {
+        if (depthNow > kMaxTreeDepth) {
             *status = GMUPT_ERR_UNSUPPORTED;
-            return "the tree is " + std::to_string(depthNow) + " levels deep after pass " + std::to_string(pass + 1) + ", the traversal stacks hold " + std::to_string(kToMaxDepth);
+            return "the tree is " + std::to_string(depthNow) + " levels deep after pass " + std::to_string(pass + 1) + ", the traversal stacks hold " + std::to_string(kMaxTreeDepth);
         }
     }
 

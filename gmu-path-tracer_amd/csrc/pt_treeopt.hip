@@ -6,10 +6,10 @@
 //   k_to_init     one thread per record: the working copy, parent links and reference counts (a child link outside (i, N) is flagged and
 //                 not followed), the cost of a leaf
 //   k_to_check    one thread per record: the child of exactly one node (the root: of none), else a flag
-//   k_to_depth    one thread per working id: depth by walking the parent links (cut off at 128 steps); sort key = depth << 32 | id, all
-//                 ones for a leaf in the sort of a pass; the largest depth of the launch, a flag when it is beyond 64
-//   (sort)        rocPRIM radix sort of (key, id) on bits 0..39
-//   k_to_levels   one thread per sorted entry: where each depth starts; in the last sort also the number of each id
+//   k_to_depth    one thread per working id: depth by walking the parent links (level_depth); sort key = level_key(depth, id), which
+//                 leaves a leaf out of the sort of a pass; the largest depth of the launch, a flag when it is beyond 64
+//   (sort)        level_sort of (key, id)
+//   k_to_levels   one thread per sorted entry: where each depth starts (level_offsets); in the last sort also the number of each id
 //   k_to_level    one launch per depth 63 .. 0 and pass, one WAVE per inner node of that depth on a fixed grid that strides over the level:
 //                 lane 0 grows the treelet (to_form) and refreshes the node; the lanes share out the 2^k subsets -- half areas first, then
 //                 the subsets of 2, 3, .. k leaves, a barrier between two sizes -- with a[], c[] and the partitions in LDS (2.5 KiB per
@@ -18,16 +18,12 @@
 //   k_to_finish   one thread: the two costs next to the other words of the readback
 #include "pt_treeopt.hpp"
 #include "pt_launch.hpp"
-
-#include <algorithm>
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "pt_levels.hpp"          // the level step (its sort is the only one of a run), the scratch carver
 
 namespace gmupt {
 
 constexpr int kToBlock = 256;
 constexpr uint32_t kToWaves = kToBlock / 64;     // treelets per block of k_to_level
-constexpr uint32_t kToDropped = 255u;            // depth byte of an entry that is not part of a sort's order
 constexpr uint32_t kToLevelBlocks = 2048;        // grid of k_to_level
 
 struct ToArgs {
@@ -69,16 +65,15 @@ __global__ __launch_bounds__(kToBlock) void k_to_depth(ToArgs a, uint32_t call, 
     const size_t id = (size_t)blockIdx.x * kToBlock + threadIdx.x;
     uint32_t depth = 0;
     if (id < a.n) {
-        for (int32_t p = a.parent[id]; p >= 0 && (uint32_t)p < a.n && depth < 128u; p = a.parent[p]) depth++;
-        const bool kept = last || a.work[id].isLeaf == 0;
-        a.keysIn[id] = kept ? ((uint64_t)depth << 32) | (uint64_t)id : ~0ull;
+        depth = level_depth(a.parent, a.parent[id], a.n);
+        a.keysIn[id] = level_key(last || a.work[id].isLeaf == 0, depth, (uint32_t)id);
         a.valsIn[id] = (uint32_t)id;
     }
     uint32_t top = depth;
     for (int s = 32; s > 0; s >>= 1) top = max(top, (uint32_t)__shfl_xor((int)top, s, 64));
     if ((threadIdx.x & 63u) == 0 && top) {
         atomicMax(a.words + kToWordDepth + call, top);
-        if (top > kToMaxDepth) atomicOr(a.words, kToFlagDeep);
+        if (top > kMaxTreeDepth) atomicOr(a.words, kToFlagDeep);
     }
 }
 
@@ -88,16 +83,10 @@ __global__ __launch_bounds__(kToBlock) void k_to_levels(ToArgs a, uint32_t last)
     const size_t pos = (size_t)blockIdx.x * kToBlock + threadIdx.x;
     const size_t M = a.n;
     if (pos >= M) return;
-    uint32_t* levelOff = a.words + kToWordLevels;
-    const uint32_t d = (uint32_t)(a.keys[pos] >> 32) & 0xFFu;
-    const uint32_t dprev = pos ? (uint32_t)(a.keys[pos - 1] >> 32) & 0xFFu : kToDropped;
-    if (d != kToDropped) {
+    const LevelEntry e = level_offsets(a.keys, pos, M, a.words + kLevelWord);
+    if (e.depth != kLevelDropped) {
         const uint32_t id = a.ids[pos];
         if (last && id < a.n) a.number[id] = (uint32_t)pos;
-        if (pos == 0 || d != dprev) levelOff[d] = (uint32_t)pos;
-        if (pos == M - 1) levelOff[d + 1] = (uint32_t)M;
-    } else if (pos && dprev != kToDropped) {
-        levelOff[dprev + 1] = (uint32_t)pos;
     }
 }
 
@@ -119,7 +108,7 @@ __global__ __launch_bounds__(kToBlock) void k_to_level(ToArgs a, uint32_t depth,
     if (threadIdx.x == 0) flagged = a.words[0];
     __syncthreads();
     if (flagged) return;
-    const uint32_t begin = a.words[kToWordLevels + depth], end = min(a.words[kToWordLevels + depth + 1], a.n);
+    const uint32_t begin = a.words[kLevelWord + depth], end = min(a.words[kLevelWord + depth + 1], a.n);
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     ToWave& S = sh[wave];
     // the trip count is the same for the waves of a block: the barriers below are met by all of them
@@ -189,74 +178,60 @@ __global__ void k_to_finish(ToArgs a)
     c[0] = a.cost0[0]; c[1] = a.cost[0];
 }
 
-static inline uint32_t to_grid(size_t n) { return (uint32_t)((n + kToBlock - 1) / kToBlock); }
-static inline size_t to_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ---- host side (gmupt_capi_treeopt.hip) ----
 
 // bytes of temporary storage the sorts of a run over n nodes need
-hipError_t treeopt_sort_temp_bytes(uint32_t n, size_t* bytes)
+hipError_t treeopt_sort_temp_bytes(uint32_t n, size_t* bytes) { return level_sort_temp_bytes(n, bytes); }
+
+// The parts of a run's scratch, taken for a capacity of `cap` nodes; returns the sort's temporary storage (sortTemp bytes), the last
+// part.  a.out is the staged output.
+static void* treeopt_carve(Scratch& sc, uint32_t cap, size_t sortTemp, ToArgs& a)
 {
-    size_t b = 0;
-    const hipError_t e = rocprim::radix_sort_pairs(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, 40u, (hipStream_t)0);
-    *bytes = to_align(std::max(b, (size_t)256));
-    return e;
+    const size_t N = cap;
+    a.words = sc.take<uint32_t>(kLevelWords);
+    a.work = sc.take<gmupt_bvh_node>(N); a.out = sc.take<gmupt_bvh_node>(N);
+    a.parent = sc.take<int32_t>(N); a.refs = sc.take<uint32_t>(N);
+    a.cost = sc.take<double>(N); a.cost0 = sc.take<double>(N);
+    a.keysIn = sc.take<uint64_t>(N); a.keys = sc.take<uint64_t>(N); a.valsIn = sc.take<uint32_t>(N); a.ids = sc.take<uint32_t>(N);
+    a.number = sc.take<uint32_t>(N);
+    return sc.take<char>(sortTemp);
 }
 
-// The scratch of a run over up to n nodes, one allocation: every part at a 256-byte boundary, the sort's temporary storage last
-ToScratch treeopt_scratch_layout(uint32_t n, size_t sortTemp)
+size_t treeopt_scratch_bytes(uint32_t cap, size_t sortTemp)
 {
-    const size_t N = n;
-    ToScratch L{};
-    size_t total = 0;
-    auto place = [&total](size_t& off, size_t bytes) { off = total; total += to_align(bytes); };
-    place(L.words, kToWords * 4);
-    place(L.work, N * sizeof(gmupt_bvh_node));
-    place(L.out, N * sizeof(gmupt_bvh_node));
-    place(L.parent, N * 4);
-    place(L.refs, N * 4);
-    place(L.cost, N * 8);
-    place(L.cost0, N * 8);
-    place(L.keysIn, N * 8);
-    place(L.keys, N * 8);
-    place(L.valsIn, N * 4);
-    place(L.ids, N * 4);
-    place(L.number, N * 4);
-    place(L.sortTemp, sortTemp);
-    L.total = total;
-    return L;
+    Scratch sc(nullptr);
+    ToArgs a{};
+    treeopt_carve(sc, cap, sortTemp, a);
+    return sc.used;
 }
 
-// enqueues the whole run; the caller reads kToWords words back from *words afterwards, the staged output is at *staged
-hipError_t launch_treeopt(void* scratch, const ToScratch& off, size_t sortTemp, const gmupt_bvh_node* nodes, uint32_t n, uint32_t passes, hipStream_t s,
+// enqueues the whole run in a scratch of treeopt_scratch_bytes(cap, sortTemp), cap >= n; the caller reads the words back from *words
+// afterwards, the staged output is at *staged
+hipError_t launch_treeopt(void* scratch, uint32_t cap, size_t sortTemp, const gmupt_bvh_node* nodes, uint32_t n, uint32_t passes, hipStream_t s,
                           const void** words, const void** staged)
 {
-    char* base = static_cast<char*>(scratch);
+    Scratch sc(scratch);
     ToArgs a{};
     a.in = nodes; a.n = n;
-    a.words = (uint32_t*)(base + off.words); a.work = (gmupt_bvh_node*)(base + off.work); a.out = (gmupt_bvh_node*)(base + off.out);
-    a.parent = (int32_t*)(base + off.parent); a.refs = (uint32_t*)(base + off.refs); a.cost = (double*)(base + off.cost); a.cost0 = (double*)(base + off.cost0);
-    a.keysIn = (uint64_t*)(base + off.keysIn); a.keys = (uint64_t*)(base + off.keys); a.valsIn = (uint32_t*)(base + off.valsIn); a.ids = (uint32_t*)(base + off.ids);
-    a.number = (uint32_t*)(base + off.number);
-    void* temp = base + off.sortTemp;
+    void* temp = treeopt_carve(sc, cap, sortTemp, a);
     *words = a.words; *staged = a.out;
-    const uint32_t grid = to_grid(n), levelGrid = std::min((n + kToWaves - 1) / kToWaves, kToLevelBlocks);
+    const uint32_t grid = grid_for(n, kToBlock), levelGrid = std::min((n + kToWaves - 1) / kToWaves, kToLevelBlocks);
 
-    hipError_t e = hipMemsetAsync(a.words, 0, kToWords * 4, s);
+    hipError_t e = hipMemsetAsync(a.words, 0, kLevelWords * 4, s);
     if (e == hipSuccess) e = hipMemsetAsync(a.refs, 0, (size_t)n * 4, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_to_init, dim3(grid), dim3(kToBlock), 0, s, a);
     hipLaunchKernelGGL(k_to_check, dim3(grid), dim3(kToBlock), 0, s, a);
     for (uint32_t call = 0; call <= passes; call++) {
         const uint32_t last = call == passes ? 1u : 0u;
-        if (call) { e = hipMemsetAsync(a.words + kToWordLevels, 0, 256 * 4, s); if (e != hipSuccess) return e; }
+        if (call) { e = hipMemsetAsync(a.words + kLevelWord, 0, 256 * 4, s); if (e != hipSuccess) return e; }
         hipLaunchKernelGGL(k_to_depth, dim3(grid), dim3(kToBlock), 0, s, a, call, last);
         size_t tb = sortTemp;
-        e = rocprim::radix_sort_pairs(temp, tb, a.keysIn, a.keys, a.valsIn, a.ids, (size_t)n, 0u, 40u, s);
+        e = level_sort(temp, tb, a.keysIn, a.keys, a.valsIn, a.ids, (size_t)n, s);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_to_levels, dim3(grid), dim3(kToBlock), 0, s, a, last);
         if (last) break;
-        for (uint32_t d = kToMaxDepth; d-- > 0;) hipLaunchKernelGGL(k_to_level, dim3(levelGrid), dim3(kToBlock), 0, s, a, d, call == 0 ? 1u : 0u);
+        for (uint32_t d = kMaxTreeDepth; d-- > 0;) hipLaunchKernelGGL(k_to_level, dim3(levelGrid), dim3(kToBlock), 0, s, a, d, call == 0 ? 1u : 0u);
     }
     hipLaunchKernelGGL(k_to_emit, dim3(grid), dim3(kToBlock), 0, s, a);
     hipLaunchKernelGGL(k_to_finish, dim3(1), dim3(1), 0, s, a);

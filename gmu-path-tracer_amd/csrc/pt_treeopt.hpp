@@ -4,7 +4,7 @@
 // statements; nothing is contracted (build.py).  The working copy is the 48-byte node record itself with links to any working id, plus a
 // parent link and a cost per node.
 #pragma once
-#include "pt_refit.hpp"
+#include "pt_lbvh.hpp"                // kMaxTreeDepth, and with it pt_refit.hpp
 #include "pt_treecost.hpp"
 #include <string>
 
@@ -13,7 +13,6 @@ namespace gmupt {
 constexpr uint32_t kToLeaves = 7;              // treelet leaves
 constexpr uint32_t kToSubsets = 1u << kToLeaves;
 constexpr uint32_t kToMaxPasses = 8;           // params.passes is in 1 .. kToMaxPasses
-constexpr uint32_t kToMaxDepth = 64;           // the traversal stacks hold 64 entries: a deeper tree is GMUPT_ERR_UNSUPPORTED
 constexpr uint32_t kToFlagBadLink = 1u, kToFlagNotTree = 2u, kToFlagDeep = 4u;
 
 // "Half area" of the tree cost for a box
@@ -175,13 +174,9 @@ GM_HD double to_refresh(gmupt_bvh_node* nodes, int32_t X)
     return to_half_area(n.min, n.max);
 }
 
-// Byte offsets of the parts of an optimiser's scratch (one allocation, pt_treeopt.hip: treeopt_scratch_layout places them) and its size.
-// `out` is the staged output.
-struct ToScratch { size_t words, work, out, parent, refs, cost, cost0, keysIn, keys, valsIn, ids, number, sortTemp, total; };
-
 // device words of a run: [0] flags, [3] treelets rewritten, [8 + j] the depth the j-th depth launch found (j = 0: the input, j = passes:
-// the output), [20..23] cost before and after as two doubles, [32 .. 32 + 256) where each depth starts in the sorted ids
-constexpr uint32_t kToWords = 32 + 256, kToWordRewritten = 3, kToWordDepth = 8, kToWordCost = 20, kToWordLevels = 32;
+// the output), [20..23] cost before and after as two doubles; behind them where each depth starts in the sorted ids (pt_levels.hpp)
+constexpr uint32_t kToWordRewritten = 3, kToWordDepth = 8, kToWordCost = 20;
 
 // what a run reports besides the nodes
 struct ToResult { uint32_t numNodes, depthBefore, depthAfter, rewritten; double costBefore, costAfter; };

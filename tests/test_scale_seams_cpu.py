@@ -26,10 +26,12 @@ def test_mirrored_constants_equal_the_sources():
     with open(os.path.join(CSRC, "pt_normals.hip")) as f:
         assert "unsigned b = 1; while (b < 32 && (numVerts >> b)) b++; return b;" in f.read(), "nm_key_bits changed: scale_util restates it"
     # every sort of the library is rocprim::radix_sort_pairs with the default configuration: what SORT_ONE_BLOCK / SORT_MERGE_LIMIT describe
-    for name in ("pt_lbvh.hip", "pt_treeopt.hip", "pt_normals.hip"):
+    for name in ("pt_lbvh.hip", "pt_levels.hpp", "pt_normals.hip"):
         with open(os.path.join(CSRC, name)) as f:
             calls = re.findall(r"rocprim::(\w+)\s*(<?)", f.read())
         assert calls and all(c == ("radix_sort_pairs", "") for c in calls), (name, calls)
+    with open(os.path.join(CSRC, "pt_treeopt.hip")) as f:                  # its sorts are level_sort of pt_levels.hpp
+        assert "rocprim::" not in f.read()
     assert [SU.sort_path(n) for n in (1024, 1025, 1 << 20, (1 << 20) + 1)] == ["block", "merge", "merge", "onesweep"]
 
 

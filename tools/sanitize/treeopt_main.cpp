@@ -61,7 +61,7 @@ int main()
             const std::string err = tree_optimize_host(in.data(), (uint32_t)in.size(), passes, out.data(), res, &status);
             CHECK(status == c.want);
             if (status != GMUPT_OK) { CHECK(!err.empty() && std::memcmp(out.data(), keep.data(), out.size() * sizeof(gmupt_bvh_node)) == 0); continue; }
-            CHECK(res.costAfter <= res.costBefore && res.depthAfter <= kToMaxDepth && res.numNodes == in.size());
+            CHECK(res.costAfter <= res.costBefore && res.depthAfter <= kMaxTreeDepth && res.numNodes == in.size());
             uint32_t leaves = 0;
             for (size_t i = 0; i < out.size(); i++) {
                 if (out[i].isLeaf) { leaves++; continue; }
