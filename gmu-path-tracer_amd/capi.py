@@ -127,6 +127,24 @@ class TemporalParams(C.Structure):
 
 TEMPORAL_MAX_CAP = 65536.0
 assert C.sizeof(TemporalParams) == 32
+
+
+class InfillParams(C.Structure):
+    """gmupt_infill_params: 16 bytes (passes 1..8; every sigma finite and > 0)."""
+    _fields_ = [("passes", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("sigma_albedo", C.c_float)]
+
+
+class InfillInfo(C.Structure):
+    """gmupt_infill_info: 24 bytes (surface pixels with / without a sample, holes filled / left open, device time)."""
+    _fields_ = [("sources", C.c_uint32), ("holes", C.c_uint32), ("filled", C.c_uint32), ("open_left", C.c_uint32), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+INFILL_MAX_PASSES = 8
+PREVIEW_MOTION = 1
+assert C.sizeof(InfillParams) == 16 and C.sizeof(InfillInfo) == 24
 # gmupt_history: the integrated unfiltered colour, its effective sample count and the guides of one pixel (48 bytes)
 history_dtype = np.dtype([("color", "<f4", 3), ("count", "<f4"), ("normal", "<f4", 3), ("material", "<u4"), ("position", "<f4", 3),
                           ("valid", "<u4")])
@@ -260,6 +278,13 @@ SYMBOLS = {
     "gmupt_denoise_image": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _P, C.c_size_t, C.POINTER(C.c_float)]),
     "gmupt_render_denoised": (C.c_int, [_P, C.c_uint32, C.POINTER(DenoiseParams), _P, C.c_size_t, C.POINTER(TraceInfo)]),
     "gmupt_denoise_host": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _P, C.c_size_t, C.c_uint32]),
+    "gmupt_infill_default_params": (None, [C.POINTER(InfillParams)]),
+    "gmupt_infill_image": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(InfillParams), _P, C.c_size_t, C.POINTER(InfillInfo)]),
+    "gmupt_infill_host": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(InfillParams), _P, C.c_size_t, C.POINTER(InfillInfo), C.c_uint32]),
+    "gmupt_temporal_preview_image": (C.c_int, [_P, _P, _P, _P, C.POINTER(CameraBuffer), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                               C.POINTER(TemporalParams), C.POINTER(InfillParams), _P, C.c_size_t, C.POINTER(C.c_float)]),
+    "gmupt_render_preview": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), C.POINTER(InfillParams), _P, C.c_size_t,
+                                       C.POINTER(TraceInfo)]),
     "gmupt_temporal_default_params": (None, [C.POINTER(TemporalParams)]),
     "gmupt_temporal_create": (C.c_int, [_P, C.POINTER(_P)]),
     "gmupt_temporal_destroy": (None, [_P]),
@@ -782,6 +807,27 @@ class Renderer:
         self.last_denoise = ti
         return out
 
+    # preview chain (gmupt_render_preview)
+    def preview(self, temporal=None, motion=False, aov_samples=1, infill=None, info=None, **params):
+        """The preview of this renderer's frame in one call (gmupt_render_preview): AOVs -> integration with the history of `temporal`
+        (a Temporal of this renderer, or None) -> guided infill -> the a-trous filter.  infill: None (off: the call is denoise(),
+        denoise_temporal() or, with motion=True, denoise_temporal_motion() bit for bit), True (gmupt_infill_default_params) or a dict
+        of infill_params fields.  params: the temporal_params fields (without a handle only the spatial ones are read).  Returns an
+        (H, W, 4) float32 torch tensor on this renderer's GPU; a filled pixel has the alpha bits of sample count 1.  info: optional
+        TraceInfo to fill, as for denoise() (ms = AOVs + integration + infill + filter)."""
+        import torch
+        dev = torch.device("cuda", getattr(self.dev, "index", 0))
+        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+        tp = temporal_params(**params)
+        ip = _infill_arg(infill)
+        torch.cuda.current_stream(dev).synchronize()
+        ti = info if info is not None else TraceInfo()
+        _check(lib().gmupt_render_preview(self.h, temporal.h if temporal is not None else None, PREVIEW_MOTION if motion else 0, int(aov_samples),
+                                          C.byref(tp), C.byref(ip) if ip is not None else None, C.c_void_p(out.data_ptr()), out.numel() * 4,
+                                          C.byref(ti)))
+        self.last_denoise = ti
+        return out
+
     # reference-layout debug access
     def read_path_state(self):
         out = np.empty(self.pool * STATE_BYTES, dtype=np.uint8)
@@ -1126,6 +1172,68 @@ def denoise_host(beauty, aov, threads=16, **params):
     return out
 
 
+def infill_params(**params):
+    """gmupt_infill_default_params with the given fields replaced (passes, sigma_normal, sigma_plane, sigma_albedo)."""
+    ip = InfillParams()
+    lib().gmupt_infill_default_params(C.byref(ip))
+    for k, v in params.items():
+        if k not in ("passes", "sigma_normal", "sigma_plane", "sigma_albedo"):
+            raise TypeError("unknown infill parameter %r" % k)
+        setattr(ip, k, v)
+    return ip
+
+
+def _infill_arg(infill):
+    """The `infill` keyword of the preview calls: None / False -> None (off), True -> the defaults, a dict -> infill_params(**dict)."""
+    if infill is None or infill is False:
+        return None
+    if isinstance(infill, InfillParams):
+        return infill
+    return infill_params(**({} if infill is True else dict(infill)))
+
+
+def infill_image(renderer, beauty, aov, info=False, **params):
+    """gmupt_infill_image on torch tensors on the renderer's GPU: beauty (H, W, 4) float32 (a = sample-count bits), aov (H, W, 16)
+    float32 gmupt_aov records.  Returns the (H, W, 4) float32 result, enqueued on the renderer's stream after torch's current stream is
+    synchronised; with info=True the call waits and returns (result, info dict), otherwise the renderer's stream is synchronised
+    before the tensor is handed to torch.  params: the infill_params fields."""
+    import torch
+    if beauty.dim() != 3 or beauty.shape[2] != 4 or aov.dim() != 3 or aov.shape[2] != 16 or tuple(aov.shape[:2]) != tuple(beauty.shape[:2]):
+        raise GmuptError("infill_image: beauty must be (H, W, 4) and aov (H, W, 16)", ERR_INVALID_ARGUMENT)
+    if beauty.dtype != torch.float32 or aov.dtype != torch.float32 or not beauty.is_cuda or not aov.is_cuda:
+        raise GmuptError("infill_image: float32 tensors on the GPU", ERR_INVALID_ARGUMENT)
+    beauty, aov = beauty.contiguous(), aov.contiguous()
+    H, W = beauty.shape[0], beauty.shape[1]
+    out = torch.empty_like(beauty)
+    ip = infill_params(**params)
+    torch.cuda.current_stream(beauty.device).synchronize()
+    ii = InfillInfo()
+    _check(lib().gmupt_infill_image(renderer.h, C.c_void_p(beauty.data_ptr()), C.c_void_p(aov.data_ptr()), W, H, C.byref(ip),
+                                    C.c_void_p(out.data_ptr()), out.numel() * 4, C.byref(ii) if info else None))
+    if info:
+        return out, ii.as_dict()
+    renderer.synchronize()
+    return out
+
+
+def infill_host(beauty, aov, threads=16, **params):
+    """gmupt_infill_host: the same rule on the CPU, bit for bit the device result.  beauty (H, W, 4) float32, aov (H, W, 16) float32
+    (or an (H, W) array of aov_dtype); numpy or torch.  Returns ((H, W, 4) float32 numpy array, info dict)."""
+    b = beauty.cpu().numpy() if hasattr(beauty, "cpu") else np.asarray(beauty)
+    a = aov.cpu().numpy() if hasattr(aov, "cpu") else np.asarray(aov)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.dtype == aov_dtype:
+        a = a.view(np.float32).reshape(a.shape + (16,))
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if b.ndim != 3 or b.shape[2] != 4 or a.shape != b.shape[:2] + (16,):
+        raise GmuptError("infill_host: beauty must be (H, W, 4) and aov (H, W, 16)", ERR_INVALID_ARGUMENT)
+    out = np.empty_like(b)
+    ip = infill_params(**params)
+    ii = InfillInfo()
+    _check(lib().gmupt_infill_host(_ptr(b), _ptr(a), b.shape[1], b.shape[0], C.byref(ip), _ptr(out), out.nbytes, C.byref(ii), int(threads)))
+    return out, ii.as_dict()
+
+
 TEMPORAL_FIELDS = ("history_cap", "min_normal_cos", "plane_dist")
 
 
@@ -1144,11 +1252,13 @@ def temporal_params(**params):
     return tp
 
 
-def temporal_denoise_image(handle, beauty, aov, cam_buffer, new_accumulation, origin=(0, 0), ms=None, motion=None, **params):
+def temporal_denoise_image(handle, beauty, aov, cam_buffer, new_accumulation, origin=(0, 0), ms=None, motion=None, infill=None, **params):
     """gmupt_temporal_denoise_image on torch tensors on the handle's GPU: beauty (H, W, 4) float32 (a = sample-count bits), aov (H, W, 16)
     float32 records, rendered with cam_buffer (a CameraBuffer) at `origin` of its whole frame.  new_accumulation: move the latest
     call's records into the history first.  Returns the (H, W, 4) float32 result.  ms: optional list that receives the device time.
-    motion: an (H, W, 4) float32 tensor of gmupt_motion records on the same GPU (gmupt_temporal_denoise_image_motion), or None."""
+    motion: an (H, W, 4) float32 tensor of gmupt_motion records on the same GPU (gmupt_temporal_denoise_image_motion), or None.
+    infill: None, or True / a dict of infill_params fields: the call goes through gmupt_temporal_preview_image, with the guided infill
+    between the integration and the filter."""
     import torch
     if beauty.dim() != 3 or beauty.shape[2] != 4 or aov.dim() != 3 or aov.shape[2] != 16 or tuple(aov.shape[:2]) != tuple(beauty.shape[:2]):
         raise GmuptError("temporal_denoise_image: beauty must be (H, W, 4) and aov (H, W, 16)", ERR_INVALID_ARGUMENT)
@@ -1167,7 +1277,13 @@ def temporal_denoise_image(handle, beauty, aov, cam_buffer, new_accumulation, or
         motion = motion.contiguous()
     torch.cuda.current_stream(beauty.device).synchronize()
     t = C.c_float(0.0)
-    if motion is not None:
+    ip = _infill_arg(infill)
+    if ip is not None:
+        _check(lib().gmupt_temporal_preview_image(handle.h, C.c_void_p(beauty.data_ptr()), C.c_void_p(aov.data_ptr()),
+                                                  C.c_void_p(motion.data_ptr()) if motion is not None else None, C.byref(cam_buffer),
+                                                  int(origin[0]), int(origin[1]), W, H, 1 if new_accumulation else 0, C.byref(tp),
+                                                  C.byref(ip), C.c_void_p(out.data_ptr()), out.numel() * 4, C.byref(t)))
+    elif motion is not None:
         _check(lib().gmupt_temporal_denoise_image_motion(handle.h, C.c_void_p(beauty.data_ptr()), C.c_void_p(aov.data_ptr()),
                                                          C.c_void_p(motion.data_ptr()), C.byref(cam_buffer), int(origin[0]), int(origin[1]), W, H,
                                                          1 if new_accumulation else 0, C.byref(tp), C.c_void_p(out.data_ptr()), out.numel() * 4,

@@ -22,33 +22,48 @@ extern "C" int gmupt_denoise_image(gmupt_renderer* r, const float* beauty_rgba, 
     return GMUPT_OK;
 }
 
-extern "C" int gmupt_render_denoised(gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, float* out_rgba, size_t bytes, gmupt_trace_info* info)
+// gmupt_render_denoised; with `infill` gmupt_render_preview without a history: the infill stage between the framebuffer copy and the filter
+int render_denoised(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, const IfParams* infill, float* out_rgba, size_t bytes,
+                    gmupt_trace_info* info)
 {
     if (info) std::memset(info, 0, sizeof(*info));
-    if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_denoised: null renderer");
+    if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer", fn);
     const uint32_t W = r->p.fbW, H = r->p.fbH;
-    if (!out_rgba || ((uintptr_t)out_rgba & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_denoised: null or misaligned output (16 bytes)");
-    if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_denoised: %zu output bytes for %ux%u RGBA32F texels", bytes, W, H);
+    if (!out_rgba || ((uintptr_t)out_rgba & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned output (16 bytes)", fn);
+    if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu output bytes for %ux%u RGBA32F texels", fn, bytes, W, H);
     DnParams prm;
-    GMUPT_TRY(denoise_params("gmupt_render_denoised", p, prm));
+    GMUPT_TRY(denoise_params(fn, p, prm));
     // what gmupt_render_aovs would refuse, before the scratch is grown for it
-    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_denoised: no scene bound");
-    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_denoised: no camera set");
-    GMUPT_TRY(aov_sample_plan("gmupt_render_denoised", "aov_samples", W, aov_samples, nullptr));
-    GMUPT_TRY(query_supported(r, "gmupt_render_denoised"));
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
+    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "%s: no camera set", fn);
+    GMUPT_TRY(aov_sample_plan(fn, "aov_samples", W, aov_samples, nullptr));
+    GMUPT_TRY(query_supported(r, fn));
     HIP_TRY(hipSetDevice(r->dev->id));
     GMUPT_TRY(r->dnInput.grow(r->stream, (size_t)W * H * (sizeof(gmupt_aov) + 16)));
+    if (infill) GMUPT_TRY(r->ifImage.grow(r->stream, (size_t)W * H * 16));
     gmupt_aov* aov = r->dnInput.as<gmupt_aov>();
-    float* beauty = reinterpret_cast<float*>(r->dnInput.as<char>() + (size_t)W * H * sizeof(gmupt_aov));
+    const float* beauty = reinterpret_cast<float*>(r->dnInput.as<char>() + (size_t)W * H * sizeof(gmupt_aov));
     gmupt_trace_info ai;
     int rc = gmupt_render_aovs(r, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai);
     if (info) *info = ai;
     if (rc != GMUPT_OK) return rc;
-    GMUPT_TRY(gmupt_copy_framebuffer_to_device(r, beauty, (size_t)W * H * 16));
-    float ms = 0.0f;
-    rc = gmupt_denoise_image(r, beauty, aov, W, H, p, out_rgba, bytes, &ms);
-    if (info) info->ms = ai.ms + ms;
+    GMUPT_TRY(gmupt_copy_framebuffer_to_device(r, const_cast<float*>(beauty), (size_t)W * H * 16));
+    if (infill) {   // enqueued, not waited for: the filter's launches follow on the same stream
+        GMUPT_TRY(r->ifEv.start(r->stream));
+        GMUPT_TRY(enqueue_infill(r, reinterpret_cast<const float4*>(beauty), reinterpret_cast<const float4*>(aov), W, H, *infill, r->ifImage.as<float4>(), nullptr));
+        GMUPT_TRY(r->ifEv.stop(r->stream));
+        beauty = r->ifImage.as<const float>();
+    }
+    float ms = 0.0f, msInfill = 0.0f;
+    rc = gmupt_denoise_image(r, beauty, aov, W, H, p, out_rgba, bytes, &ms);   // synchronises the stream
+    if (rc == GMUPT_OK && infill) GMUPT_TRY(r->ifEv.elapsed_ms(&msInfill));
+    if (info) info->ms = ai.ms + msInfill + ms;
     return rc;
+}
+
+extern "C" int gmupt_render_denoised(gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, float* out_rgba, size_t bytes, gmupt_trace_info* info)
+{
+    return render_denoised("gmupt_render_denoised", r, aov_samples, p, nullptr, out_rgba, bytes, info);
 }
 
 // ------------------------------------------------------------------------------------------------ temporal reuse
@@ -86,10 +101,11 @@ extern "C" int gmupt_temporal_reset(gmupt_temporal* t)
     return GMUPT_OK;
 }
 
-// gmupt_temporal_denoise_image (motion == nullptr: k_tp_integrate) and gmupt_temporal_denoise_image_motion (k_tp_integrate_mv)
-static int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
-                            const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
-                            const gmupt_temporal_params* p, float* out_rgba, size_t out_bytes, float* ms)
+// gmupt_temporal_denoise_image (motion == nullptr: k_tp_integrate) and gmupt_temporal_denoise_image_motion (k_tp_integrate_mv); with
+// `infill` gmupt_temporal_preview_image: the infill stage between the integration, which has written the records, and the filter
+int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
+                     const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
+                     const gmupt_temporal_params* p, const IfParams* infill, float* out_rgba, size_t out_bytes, float* ms)
 {
     if (ms) *ms = 0.0f;
     gmupt_temporal_params d;
@@ -107,6 +123,7 @@ static int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beau
     rc = t->last.rec.grow(r->stream, n * sizeof(gmupt_history));
     if (rc == GMUPT_OK) rc = t->integrated.grow(r->stream, n * 16);
     if (rc == GMUPT_OK) rc = r->dnScratch.grow(r->stream, n * kDnScratchBytes);
+    if (rc == GMUPT_OK && infill) rc = r->ifImage.grow(r->stream, n * 16);
     if (rc != GMUPT_OK) { t->last.present = false; return rc; }
     TpPrev prev{};
     if (t->frozen.present) {
@@ -125,6 +142,10 @@ static int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beau
         launch_temporal(reinterpret_cast<const float4*>(beauty_rgba), reinterpret_cast<const float4*>(aov), (int)width, (int)height, prev, tp, integrated,
                         t->last.rec.as<float4>(), r->stream);
     HIP_TRY(hipGetLastError());
+    if (infill) {
+        GMUPT_TRY(enqueue_infill(r, integrated, reinterpret_cast<const float4*>(aov), width, height, *infill, r->ifImage.as<float4>(), nullptr));
+        integrated = r->ifImage.as<float4>();
+    }
     launch_denoise(integrated, reinterpret_cast<const float4*>(aov), (int)width, (int)height, dn, r->dnScratch.ptr, reinterpret_cast<float4*>(out_rgba), r->stream);
     HIP_TRY(hipGetLastError());
     GMUPT_TRY(t->ev.stop(r->stream));
@@ -140,7 +161,7 @@ extern "C" int gmupt_temporal_denoise_image(gmupt_temporal* t, const float* beau
                                             uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
                                             const gmupt_temporal_params* p, float* out_rgba, size_t out_bytes, float* ms)
 {
-    return temporal_denoise("gmupt_temporal_denoise_image", t, beauty_rgba, aov, nullptr, cam, x0, y0, width, height, new_accumulation, p, out_rgba, out_bytes, ms);
+    return temporal_denoise("gmupt_temporal_denoise_image", t, beauty_rgba, aov, nullptr, cam, x0, y0, width, height, new_accumulation, p, nullptr, out_rgba, out_bytes, ms);
 }
 
 extern "C" int gmupt_temporal_denoise_image_motion(gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
@@ -149,12 +170,13 @@ extern "C" int gmupt_temporal_denoise_image_motion(gmupt_temporal* t, const floa
 {
     const char* fn = "gmupt_temporal_denoise_image_motion";
     if ((uintptr_t)motion & 15u) { if (ms) *ms = 0.0f; return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: misaligned motion plane (16 bytes)", fn); }
-    return temporal_denoise(fn, t, beauty_rgba, aov, motion, cam, x0, y0, width, height, new_accumulation, p, out_rgba, out_bytes, ms);
+    return temporal_denoise(fn, t, beauty_rgba, aov, motion, cam, x0, y0, width, height, new_accumulation, p, nullptr, out_rgba, out_bytes, ms);
 }
 
-// gmupt_render_denoised_temporal, and with `poses` gmupt_render_denoised_temporal_motion: the record sets keep their vertex pose
-static int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
-                                    float* out_rgba, size_t bytes, gmupt_trace_info* info)
+// gmupt_render_denoised_temporal, and with `poses` gmupt_render_denoised_temporal_motion: the record sets keep their vertex pose; with
+// `infill` gmupt_render_preview
+int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
+                             const IfParams* infill, float* out_rgba, size_t bytes, gmupt_trace_info* info)
 {
     if (info) std::memset(info, 0, sizeof(*info));
     if (!r || !t) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer or handle", fn);
@@ -199,7 +221,7 @@ static int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* 
         HIP_TRY(hipMemcpyAsync(nw.verts.ptr, r->p.scene.verts, (size_t)nv * 12, hipMemcpyDeviceToDevice, r->stream));
     }
     float ms = 0.0f;
-    rc = temporal_denoise(fn, t, beauty, aov, motion, &r->p.cam, r->tile_x0(), r->tile_y0(), W, H, fold ? 1 : 0, p, out_rgba, bytes, &ms);   // synchronises the stream
+    rc = temporal_denoise(fn, t, beauty, aov, motion, &r->p.cam, r->tile_x0(), r->tile_y0(), W, H, fold ? 1 : 0, p, infill, out_rgba, bytes, &ms);   // synchronises the stream
     if (info) info->ms = ai.ms + ms;
     if (rc != GMUPT_OK) return rc;
     t->seen = true; t->generation = r->accumGeneration;
@@ -210,11 +232,11 @@ static int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* 
 extern "C" int gmupt_render_denoised_temporal(gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
                                               float* out_rgba, size_t bytes, gmupt_trace_info* info)
 {
-    return render_denoised_temporal("gmupt_render_denoised_temporal", false, r, t, aov_samples, p, out_rgba, bytes, info);
+    return render_denoised_temporal("gmupt_render_denoised_temporal", false, r, t, aov_samples, p, nullptr, out_rgba, bytes, info);
 }
 
 extern "C" int gmupt_render_denoised_temporal_motion(gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
                                                      float* out_rgba, size_t bytes, gmupt_trace_info* info)
 {
-    return render_denoised_temporal("gmupt_render_denoised_temporal_motion", true, r, t, aov_samples, p, out_rgba, bytes, info);
+    return render_denoised_temporal("gmupt_render_denoised_temporal_motion", true, r, t, aov_samples, p, nullptr, out_rgba, bytes, info);
 }

@@ -102,6 +102,48 @@ extern "C" int gmupt_denoise_host(const float* beauty_rgba, const gmupt_aov* aov
     return GMUPT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ infill
+static_assert(sizeof(gmupt_infill_params) == 16 && offsetof(gmupt_infill_params, sigma_normal) == 4 && offsetof(gmupt_infill_params, sigma_plane) == 8 &&
+              offsetof(gmupt_infill_params, sigma_albedo) == 12, "gmupt_infill_params layout");
+static_assert(sizeof(gmupt_infill_info) == 24 && offsetof(gmupt_infill_info, filled) == 8 && offsetof(gmupt_infill_info, ms) == 16, "gmupt_infill_info layout");
+
+extern "C" void gmupt_infill_default_params(gmupt_infill_params* p)
+{
+    if (!p) return;
+    p->passes = 6; p->sigma_normal = 32.0f; p->sigma_plane = 0.02f; p->sigma_albedo = 0.1f;
+}
+
+int infill_params(const char* fn, const gmupt_infill_params* p, IfParams& out)
+{
+    gmupt_infill_params d;
+    if (!p) { gmupt_infill_default_params(&d); p = &d; }
+    if (p->passes < 1 || p->passes > GMUPT_INFILL_MAX_PASSES) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: infill passes = %u (1..%d)", fn, p->passes, GMUPT_INFILL_MAX_PASSES);
+    const float s[3] = { p->sigma_normal, p->sigma_plane, p->sigma_albedo };
+    const char* names[3] = { "sigma_normal", "sigma_plane", "sigma_albedo" };
+    for (int k = 0; k < 3; k++)
+        if (!(std::isfinite(s[k]) && s[k] > 0.0f)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: infill %s = %g (finite and > 0)", fn, names[k], (double)s[k]);
+    out.passes = (int)p->passes; out.sigmaNormal = s[0]; out.sigmaPlane = s[1]; out.sigmaAlbedo = s[2];
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_infill_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height, const gmupt_infill_params* p,
+                                 float* out_rgba, size_t out_bytes, gmupt_infill_info* info, uint32_t threads)
+{
+    DnParams unused; IfParams prm;
+    GMUPT_TRY(denoise_args("gmupt_infill_host", beauty_rgba, aov, width, height, nullptr, out_rgba, out_bytes, false, unused));   // pointers, size, overlap, bytes
+    GMUPT_TRY(infill_params("gmupt_infill_host", p, prm));
+    IfCounters c{};
+    try {
+        infill_host(beauty_rgba, aov, (int)width, (int)height, prm, out_rgba, &c, clamp_threads(threads));
+    } catch (const std::bad_alloc&) {
+        return fail(GMUPT_ERR_OUT_OF_MEMORY, "gmupt_infill_host: out of host memory for %ux%u pixels", width, height);
+    } catch (const std::exception& e) {
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_infill_host: %s", e.what());
+    }
+    if (info) { info->sources = c.sources; info->holes = c.holes; info->filled = c.filled; info->open_left = c.openLeft; info->ms = 0.0; }
+    return GMUPT_OK;
+}
+
 static_assert(sizeof(gmupt_temporal_params) == 32 && offsetof(gmupt_temporal_params, history_cap) == 20 && offsetof(gmupt_temporal_params, min_normal_cos) == 24 &&
               offsetof(gmupt_temporal_params, plane_dist) == 28, "gmupt_temporal_params layout");
 extern "C" void gmupt_temporal_default_params(gmupt_temporal_params* p)

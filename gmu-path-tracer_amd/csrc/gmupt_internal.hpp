@@ -3,6 +3,7 @@
 #pragma once
 #include "pt_shading.hpp"
 #include "pt_denoise.hpp"
+#include "pt_infill.hpp"
 #include "pt_temporal.hpp"
 #include "pt_motion.hpp"
 #include "pt_travtables.hpp"
@@ -122,6 +123,10 @@ struct gmupt_renderer {
     // the framebuffer copy (80 bytes per pixel); allocated on first use, grown when a larger image comes
     DevMem dnScratch, dnInput;
     EventPair dnEv;
+    // infill (gmupt_infill_image): the stage's scratch (256 bytes of counters, then kIfScratchBytes per pixel) and, for the chained entry
+    // points, the filled image the denoiser reads (16 bytes per pixel); allocated on first use, grown when a larger image comes
+    DevMem ifScratch, ifImage;
+    EventPair ifEv;
     // temporal reuse (gmupt_render_denoised_temporal): advanced by an iteration that clears the frame and by gmupt_resize (host only)
     uint64_t accumGeneration = 0;
     // motion (gmupt_render_denoised_temporal_motion): which binding the renderer has and how many refits it has seen (host only)
@@ -190,6 +195,17 @@ int denoise_params(const char* fn, const gmupt_denoise_params* p, DnParams& out)
 int denoise_args(const char* fn, const void* beauty, const void* aov, uint32_t W, uint32_t H, const gmupt_denoise_params* p, const void* out, size_t bytes,
                  bool device, DnParams& prm);
 int temporal_params(const char* fn, const gmupt_temporal_params* p, DnParams& dn, TpParams& tp);
+int infill_params(const char* fn, const gmupt_infill_params* p, IfParams& out);
+// gmupt_capi_denoise.hip: the chains behind the temporal entry points; infill == nullptr is the chain without the infill stage
+int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
+                     const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
+                     const gmupt_temporal_params* p, const IfParams* infill, float* out_rgba, size_t out_bytes, float* ms);
+int render_denoised(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, const IfParams* infill, float* out_rgba, size_t bytes,
+                    gmupt_trace_info* info);
+int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
+                             const IfParams* infill, float* out_rgba, size_t bytes, gmupt_trace_info* info);
+// gmupt_capi_infill.hip: grows the renderer's infill scratch for the image (the one place that does) and enqueues the stage
+int enqueue_infill(gmupt_renderer* r, const float4* beauty, const float4* aov, uint32_t W, uint32_t H, const IfParams& prm, float4* out, const IfCounters** counts);
 int lbvh_leaf_size(const char* fn, const gmupt_lbvh_params* params, uint32_t* L);
 void lbvh_fill_info(gmupt_lbvh_info* info, const LbResult& res, uint32_t numTris, double ms);
 int treeopt_passes(const char* fn, const gmupt_treeopt_params* params, uint32_t* passes);

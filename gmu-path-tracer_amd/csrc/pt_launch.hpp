@@ -8,7 +8,7 @@
 #include "../../include/gmupt.h"
 
 namespace gmupt {
-struct RenderParams; struct SceneView; struct DnParams; struct TpParams; struct TpPrev; struct RfArgs; struct LbStaging; struct NmLayout; struct NmArgs; struct TcPartial; struct PsLayout; struct PsArgs;   // pt_*.hpp
+struct RenderParams; struct SceneView; struct DnParams; struct IfParams; struct IfCounters; struct TpParams; struct TpPrev; struct RfArgs; struct LbStaging; struct NmLayout; struct NmArgs; struct TcPartial; struct PsLayout; struct PsArgs;   // pt_*.hpp
 
 void launch_clear(const RenderParams& p, hipStream_t s);
 void launch_logic(const RenderParams& p, hipStream_t s);
@@ -32,6 +32,9 @@ void launch_aov_resolve(const RenderParams& p, uint32_t npix, uint32_t samples, 
                         gmupt_aov* out, hipStream_t s);
 void launch_denoise(const float4* beauty, const float4* aov, int W, int H, const DnParams& prm, void* scratch, float4* out, hipStream_t s);
 void denoise_host(const float* beauty, const void* aov, int W, int H, const DnParams& prm, float* out, int threads);
+size_t infill_scratch_bytes(size_t npix);
+hipError_t launch_infill(const float4* beauty, const float4* aov, int W, int H, const IfParams& prm, void* scratch, float4* out, hipStream_t s,
+                         const IfCounters** countsOut);
 void launch_temporal(const float4* beauty, const float4* aov, int W, int H, const TpPrev& prev, const TpParams& prm, float4* out, float4* hist,
                      hipStream_t s);
 void launch_temporal_motion(const float4* beauty, const float4* aov, const float4* motion, int W, int H, const TpPrev& prev, const TpParams& prm,

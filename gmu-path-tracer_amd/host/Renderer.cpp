@@ -193,6 +193,33 @@ std::vector<float> Renderer::denoiseTemporal(unsigned aovSamples, const gmupt_te
 	return out;
 }
 
+gmupt_trace_info Renderer::preview(float* deviceOut, size_t bytes, bool temporal, bool motion, unsigned aovSamples, const gmupt_temporal_params* params,
+                                   const gmupt_infill_params* infill)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	if (temporal && !mTemporal) { gmupt_temporal* t = nullptr; check(gmupt_temporal_create(mRenderer.get(), &t)); mTemporal.reset(t); }
+	gmupt_trace_info info{};
+	check(gmupt_render_preview(mRenderer.get(), temporal ? mTemporal.get() : nullptr, temporal && motion ? GMUPT_PREVIEW_MOTION : 0u, aovSamples, params, infill,
+	                           deviceOut, bytes, &info));
+	return info;
+}
+
+std::vector<float> Renderer::preview(bool temporal, bool motion, unsigned aovSamples, const gmupt_temporal_params* params, const gmupt_infill_params* infill)
+{
+	const Resolution t = targetSize();
+	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
+	const size_t bytes = out.size() * sizeof(float);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("preview: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { preview(static_cast<float*>(d), bytes, temporal, motion, aovSamples, params, infill); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error("preview: cannot read the image back");
+	return out;
+}
+
 gmupt_refit_info Renderer::refitScene(bool keepHistory, bool smoothNormals)
 {
 	gmupt_refit_info info{};

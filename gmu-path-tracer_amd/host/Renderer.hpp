@@ -65,6 +65,14 @@ public:
 	// and after refitScene(true) the history is looked up where each surface point was.  Without a refit in between it is denoiseTemporal.
 	gmupt_trace_info denoiseTemporalMotion(float* deviceOut, size_t bytes, unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
 	std::vector<float> denoiseTemporalMotion(unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr);
+	// the preview in one call (gmupt_render_preview): AOVs -> the integration with this renderer's history (temporal; with motion the
+	// history follows refitted vertices) -> the guided infill (infill != nullptr: surface pixels without a sample take a colour from the
+	// sampled pixels of their surface; filled colour never enters the history) -> the filter.  Without a history only params->spatial
+	// is read.  infill == nullptr: denoise(), denoiseTemporal() or denoiseTemporalMotion() bit for bit.  The two forms as denoise().
+	gmupt_trace_info preview(float* deviceOut, size_t bytes, bool temporal, bool motion, unsigned aovSamples = 1,
+	                         const gmupt_temporal_params* params = nullptr, const gmupt_infill_params* infill = nullptr);
+	std::vector<float> preview(bool temporal, bool motion, unsigned aovSamples = 1, const gmupt_temporal_params* params = nullptr,
+	                           const gmupt_infill_params* infill = nullptr);
 	void resetHistory();
 	// after Scene::setVertices: the tree's boxes and this renderer's traversal tables recomputed on the GPU for the moved vertices
 	// (gmupt_renderer_refit; the topology of the tree stays), the accumulation restarted, the temporal history dropped -- or kept

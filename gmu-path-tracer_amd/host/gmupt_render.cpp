@@ -14,6 +14,8 @@
 //                [--denoise PREFIX [--aov-samples S]]     after the frames: the frame through the a-trous denoiser (gmupt_render_denoised, AOVs at
 //                                                         S samples per axis): PREFIX.pfm ("PF") and PREFIX.png (the capture's truncation, alpha 255)
 //                                                         (single process only)
+//                [--infill]                               with --denoise and / or --temporal: surface pixels without a sample take a colour from the sampled
+//                                                         pixels of their surface before the filter runs (Renderer::preview, gmupt_infill_default_params)
 //                [--vertices FILE]                        before the frames: moved positions for all vertices of the scene (raw little-endian float32,
 //                                                         3 per vertex) through Scene::setVertices + Renderer::refitScene; one JSON line with the
 //                                                         refit info; not with --ranks
@@ -121,6 +123,7 @@ int main(int argc, char** argv)
 	std::string aovPrefix; unsigned aovSamples = 1;
 	std::string denoisePrefix;
 	std::string temporalPrefix;
+	bool infill = false;
 	std::string builder = "sbvh", dumpTree; unsigned leaf = 4, optimize = 0;
 	bool treeCost = false;
 	for (int i = 1; i < argc; i++) {
@@ -152,6 +155,7 @@ int main(int argc, char** argv)
 		else if (a == "--rig") rigFile = next();
 		else if (a == "--pose") poseFile = next();
 		else if (a == "--temporal") temporalPrefix = next();
+		else if (a == "--infill") infill = true;
 		else if (a == "--builder") { builder = next(); if (builder != "sbvh" && builder != "lbvh") { std::fprintf(stderr, "--builder takes sbvh or lbvh\n"); return 2; } }
 		else if (a == "--leaf") { char* end = nullptr; const char* v = next(); leaf = std::strtoul(v, &end, 10); if (end == v || *end || leaf < 1 || leaf > 64) { std::fprintf(stderr, "--leaf takes a number in 1..64\n"); return 2; } }
 		else if (a == "--optimize") { char* end = nullptr; const char* v = next(); optimize = std::strtoul(v, &end, 10); if (end == v || *end || optimize > 8) { std::fprintf(stderr, "--optimize takes a number of passes in 0..8\n"); return 2; } }
@@ -178,6 +182,8 @@ int main(int argc, char** argv)
 			            "             [--optimize N]      with --builder lbvh: N = 1..8 passes of the treelet optimiser on the new tree before it is bound (0, the\n"
 			            "                                 default: none), one more JSON line with its info.  With --build-only: the host reference of the optimiser\n"
 			            "             [--dump-tree FILE]  with --build-only: the flattened tree, raw (48-byte nodes, then 16-byte triangle records)\n"
+			            "             [--infill]          with --denoise / --temporal: pixels without a sample are filled from the sampled pixels of their surface\n"
+			            "                                 before the filter (Renderer::preview); filled colour never enters the history\n"
 			            "             [--denoise PREFIX [--aov-samples S]]   after the frames: the frame through the a-trous denoiser guided by the AOV buffers\n"
 			            "                            (S samples per axis): PREFIX.pfm (PF) and PREFIX.png (8-bit, truncated like --capture); not with --ranks\n");
 			return 0;
@@ -253,6 +259,8 @@ int main(int argc, char** argv)
 		}
 		if (!aovPrefix.empty() && ranks > 1)
 			throw std::invalid_argument("--aov renders the AOV buffers of a single process: it cannot be combined with --ranks N > 1 (there is no multi-rank AOV gather)");
+		if (infill && denoisePrefix.empty() && temporalPrefix.empty())
+			throw std::invalid_argument("--infill fills the pixels of a preview: it needs --denoise PREFIX or --temporal PREFIX");
 		if (!temporalPrefix.empty() && ranks > 1)
 			throw std::invalid_argument("--temporal previews the frame of a single process: it cannot be combined with --ranks N > 1");
 		if (!denoisePrefix.empty() && ranks > 1)
@@ -357,7 +365,8 @@ int main(int argc, char** argv)
 			std::printf("aov %s: %ux%u, %u samples\n", aovPrefix.c_str(), w, h, aovSamples);
 		}
 		if (!denoisePrefix.empty()) {
-			const std::vector<float> img = renderer.denoise(aovSamples);
+			gmupt_infill_params ip; gmupt_infill_default_params(&ip);
+			const std::vector<float> img = infill ? renderer.preview(false, false, aovSamples, nullptr, &ip) : renderer.denoise(aovSamples);
 			writePfmFile(denoisePrefix + ".pfm", img, w, h);
 			std::vector<unsigned char> png(img.size());
 			for (size_t i = 0; i < img.size(); i += 4) // Renderer::captureScreen's conversion: float * 255 truncated, alpha 255
@@ -371,7 +380,8 @@ int main(int argc, char** argv)
 			std::printf("denoise %s: %ux%u, %u aov samples\n", denoisePrefix.c_str(), w, h, aovSamples);
 		}
 		if (!temporalPrefix.empty()) {
-			const std::vector<float> img = renderer.denoiseTemporalMotion(aovSamples);
+			gmupt_infill_params ip; gmupt_infill_default_params(&ip);
+			const std::vector<float> img = infill ? renderer.preview(true, true, aovSamples, nullptr, &ip) : renderer.denoiseTemporalMotion(aovSamples);
 			writePfmFile(temporalPrefix + ".pfm", img, w, h);
 			std::printf("temporal %s: %ux%u, %u aov samples\n", temporalPrefix.c_str(), w, h, aovSamples);
 		}

@@ -239,20 +239,28 @@ class ProgressiveSession:
         from . import capi
         return capi.aov_fields(self.renderer.aovs(samples))
 
-    def denoised(self, aov_samples=1, **params):
+    def denoised(self, aov_samples=1, infill=False, **params):
         """A clean preview of the session's current frame: capi.Renderer.denoise (gmupt_render_denoised) as an (H, W, 4) float32 numpy
         array -- rgb denoised, alpha the sample-count bits -- so to_rgba8 and the frame writers take it as they take a preview.  On a
-        tile renderer it is this rank's tile, denoised on its own (tile edges are image edges).  params: the gmupt_denoise_params fields."""
+        tile renderer it is this rank's tile, denoised on its own (tile edges are image edges).  params: the gmupt_denoise_params fields.
+        infill: True, or a dict of capi.infill_params fields -- surface pixels without a sample take a colour from the sampled pixels of
+        their surface before the filter runs (capi.Renderer.preview, gmupt_render_preview); False keeps today's bits."""
+        if infill is not None and infill is not False:
+            return self.renderer.preview(aov_samples=aov_samples, infill=infill, **params).cpu().numpy()
         return self.renderer.denoise(aov_samples, **params).cpu().numpy()
 
-    def denoised_temporal(self, aov_samples=1, **params):
+    def denoised_temporal(self, aov_samples=1, infill=False, **params):
         """A preview that survives camera motion: capi.Renderer.denoise_temporal (gmupt_render_denoised_temporal) with a history handle the
         session owns, as an (H, W, 4) float32 numpy array -- rgb denoised, alpha the effective sample-count bits.  Pixels the new
         accumulation has not reached yet show the reprojected history of the frames before the restart.  set_lights drops the history;
-        resize keeps it.  On a tile renderer each rank keeps its own tile's history.  params: the capi.temporal_params fields."""
+        resize keeps it.  On a tile renderer each rank keeps its own tile's history.  params: the capi.temporal_params fields.
+        infill: as denoised() -- the pixels without a sample that have no consistent history either (first frame, light edit,
+        disocclusion) are filled after the integration; filled colour never enters the history.  False keeps today's bits."""
         if self.temporal is None:
             from . import capi
             self.temporal = capi.Temporal(self.renderer)
+        if infill is not None and infill is not False:
+            return self.renderer.preview(self.temporal, motion=self.motion, aov_samples=aov_samples, infill=infill, **params).cpu().numpy()
         call = self.renderer.denoise_temporal_motion if self.motion else self.renderer.denoise_temporal
         return call(self.temporal, aov_samples, **params).cpu().numpy()
 

@@ -562,6 +562,86 @@ int gmupt_temporal_denoise_image_motion(gmupt_temporal* t, const float* beauty_r
 int gmupt_render_denoised_temporal_motion(gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
                                           float* out_rgba, size_t bytes, gmupt_trace_info* info /* may be NULL */);
 
+/* ---- Infill: surface pixels without a sample take a colour from the sampled pixels of the same surface, before the denoiser runs (a
+ * guided push of sparse samples: the a-trous taps and edge stops of the denoiser above, run over growing steps from the sampled pixels
+ * into the holes).  Opt-in: every entry point above behaves as before. ----
+ * Inputs per pixel: the beauty texel (rgb = running mean of tonemapped samples, a = sample count as uint bits) and its gmupt_aov record.
+ * All arithmetic is binary32 in the order stated here, no contraction; dpow / dexp2 / normalize3 as for the denoiser.
+ *
+ * Classes.  Surface pixel: aov.triangle != -1, aov.light == 0, sqrt(dot3(aov.normal, aov.normal)) > 0 (the denoiser's test without the
+ *   sample count).  SOURCE: a surface pixel with count > 0.  HOLE: a surface pixel with count == 0.  Every other pixel (miss, light
+ *   sphere, zero or NaN normal) is copied to the output bit for bit, is never a source and is never filled.  A surface pixel has
+ *   n = normalize3(aov.normal), x = aov.position, z = aov.depth, a = aov.albedo, m = aov.material.
+ * Pass k = 0 .. passes-1, step s = 1 << k.  A pixel is KNOWN in pass k when it is a source or was filled by a pass before k; a hole that
+ *   is not known is OPEN.  Per open hole p, taps q = p + s * (i, j), j = -2..2 outer, i = -2..2 inner; a tap counts when it lies inside
+ *   the image, is known in pass k, and m_q == m_p (the centre is open, so it never counts):
+ *     w   = ((h[i] * h[j]) * w_n) * E,  h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *     w_n = dpow(max(0, dot3(n_p, n_q)), sigma_normal)          (max(0, c) is 0 when c is NaN)
+ *     E   = dexp2(-(d_x + d_a) * 1.44269504f)
+ *     d_x = |dot3(n_p, x_q - x_p)| / (sigma_plane * z_p)
+ *     d_a = ((|a_q.r - a_p.r| + |a_q.g - a_p.g|) + |a_q.b - a_p.b|) / sigma_albedo
+ *   There is no luminance term: a hole has no luminance.  W = sum w, C = sum w * c_q (per channel), from 0.0f in tap order, c_q the
+ *   source's beauty rgb or the colour q was filled with.  If W > 0 (false for NaN) the hole is filled with C / W (one division per channel)
+ *   and is known from pass k+1 on; otherwise it stays open.  Pixels filled in pass k are not visible to pass k, so the result does not
+ *   depend on the order in which pixels are processed.  Sources and filled pixels never change again.
+ * Output: RGBA32F.  A filled pixel: its colour, alpha = the bits of sample count 1 (so that gmupt_denoise_image takes it as valid).
+ *   Every other pixel -- no surface, source, hole still open after the last pass -- is its input texel bit for bit.
+ *   Non-finite colours and guides are no error: they propagate through the sums, or leave the hole open, as the statements above say.
+ * Reach: a hole filled in pass k has a known pixel at most 2 * 2^k away per axis, which itself was known by a chain of earlier passes:
+ *   at most 2 * (2^0 + .. + 2^(passes-1)) = 2 * (2^passes - 1) pixels per axis from a source, 126 at passes = 6.  A hole farther than
+ *   that from every source stays open.
+ * Hence, bit for bit: (a) a frame without holes, and a frame without sources, come out as they went in; (b) filled colour never enters
+ *   a temporal history -- in the chains below the records are written by the integration, before the infill runs, so a later call's
+ *   output does not depend on whether an earlier call had the infill on; (c) every chained entry point equals the composition of its
+ *   parts: gmupt_denoise_image(gmupt_infill_image(beauty, aov), aov) without a history,
+ *   gmupt_denoise_image(gmupt_infill_image(integrated, aov), aov) with one (integrated: gmupt_temporal_integrate*_host's image).
+ * Parameters: passes 1..8, every sigma finite and > 0, else GMUPT_ERR_INVALID_ARGUMENT. */
+typedef struct {
+    uint32_t passes;      /* passes (steps 1, 2, 4, ..); default 6 */
+    float sigma_normal;   /* exponent of the normal cosine; default 32 */
+    float sigma_plane;    /* distance from p's tangent plane, relative to p's depth; default 0.02 */
+    float sigma_albedo;   /* L1 albedo difference; default 0.1 */
+} gmupt_infill_params;    /* 16 bytes */
+#define GMUPT_INFILL_MAX_PASSES 8
+void gmupt_infill_default_params(gmupt_infill_params* p);
+typedef struct {
+    uint32_t sources, holes;      /* of the input: surface pixels with / without a sample */
+    uint32_t filled, open_left;   /* holes that took a colour / that no pass reached (filled + open_left == holes) */
+    double ms;                    /* device time of the stage (gmupt_infill_host: 0) */
+} gmupt_infill_info;              /* 24 bytes */
+/* beauty_rgba, aov, out_rgba: caller-owned DEVICE memory as for gmupt_denoise_image (16-byte aligned, any image size; out must not
+ * overlap beauty; out_bytes >= width * height * 16).  Enqueued on the renderer's stream behind pending work: a 16-byte memset of the
+ * counters, k_if_prepare, then one k_if_pass per pass, no host synchronisation between them.  info == NULL: the call returns without
+ * waiting for the stream (later work on the renderer's stream is ordered behind it).  info != NULL: one synchronisation, then the four
+ * counts and the event time.  The counts are integer sums, the same whatever the order of the waves.  The stage's scratch (256 bytes +
+ * 76 per pixel) is allocated on first use, grown when a larger image comes (that waits for the stream) and kept until
+ * gmupt_renderer_destroy; the frame, path state, queues, counters and statistics are not touched.  p may be NULL (the defaults).
+ * Errors, nothing written: GMUPT_ERR_INVALID_ARGUMENT for a NULL or misaligned pointer, an overlapping output, too few out_bytes, an
+ * empty image or bad parameters. */
+int gmupt_infill_image(gmupt_renderer* r, const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height,
+                       const gmupt_infill_params* p, float* out_rgba, size_t out_bytes, gmupt_infill_info* info /* may be NULL */);
+/* The same rule on host arrays (the same binary32 sequence, bit for bit the device result, counts included), in row bands on up to
+ * `threads` std::threads (0 -> 1, at most 16); the result does not depend on the thread count.  Errors as gmupt_infill_image. */
+int gmupt_infill_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height, const gmupt_infill_params* p,
+                      float* out_rgba, size_t out_bytes, gmupt_infill_info* info /* may be NULL */, uint32_t threads);
+/* The chain integrate -> infill -> denoise on caller images: gmupt_temporal_denoise_image (motion == NULL) or
+ * gmupt_temporal_denoise_image_motion with the infill between the integration and the spatial filter, all on the renderer's stream
+ * without a host synchronisation in between.  infill == NULL: bit for bit those two calls (temporal params NULL: the defaults).  The
+ * history records are the integration's (consequence (b)).  Errors: theirs, and bad infill parameters. */
+int gmupt_temporal_preview_image(gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion /* may be NULL */,
+                                 const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                                 int new_accumulation, const gmupt_temporal_params* p, const gmupt_infill_params* infill /* may be NULL */,
+                                 float* out_rgba, size_t out_bytes, float* ms /* may be NULL */);
+/* The renderer's preview in one call: AOVs -> optional integration (t != NULL) -> optional infill (infill != NULL) -> denoise.
+ *   t == NULL:  gmupt_render_denoised with p->spatial (p == NULL: the defaults; nothing else of p is read); flags must be 0.
+ *   t != NULL:  gmupt_render_denoised_temporal, or with GMUPT_PREVIEW_MOTION gmupt_render_denoised_temporal_motion.
+ * With infill == NULL the call is one of those three, bit for bit.  Errors and info as theirs; unknown flag bits and bad infill
+ * parameters: GMUPT_ERR_INVALID_ARGUMENT.  info->ms includes the infill. */
+#define GMUPT_PREVIEW_MOTION 1u
+int gmupt_render_preview(gmupt_renderer* r, gmupt_temporal* t /* may be NULL */, uint32_t flags, uint32_t aov_samples,
+                         const gmupt_temporal_params* p, const gmupt_infill_params* infill /* may be NULL */, float* out_rgba, size_t bytes,
+                         gmupt_trace_info* info /* may be NULL */);
+
 /* ---- LBVH: a tree for new geometry built on the GPU (an extension; the reference builds once on the host) ----
  * A linear BVH (Lauterbach et al. 2009: Morton keys and a radix sort; Karras 2012: the hierarchy as a binary radix tree) over the
  * device-resident vertex buffer, in the node / triangle layout above: gmupt_renderer_bind_scene, gmupt_renderer_refit, the ray queries, the
