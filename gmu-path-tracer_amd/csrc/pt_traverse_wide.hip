@@ -28,6 +28,24 @@
 // (as k_cast_f).  A lane whose inner stack alone fills its LDS share gives the wide walk of that ray up and parks it as well (the exact
 // walk has a bounds-checked global overflow).  Drain: finished lanes take the BOTTOM inner entry of busy lanes (the largest subtree
 // left) and report their best hit back; results merge by "smaller t wins, equal t is a tie".
+//
+// The pushes of a step are branch-free: for the four slots in turn `sl[pa] = link; pa += (hit and inner)`, then for the four slots in
+// turn `sl[pb] = link; pb -= (hit and leaf)` -- eight unconditional LDS stores, each at the current top, the top advanced by the
+// predicate.  The next node is the LAST hit inner slot, taken from its register (the visit order is free, see above); its copy is the
+// entry on top of the inner stack, so `pa--` drops it and it is never read back.  Why no store destroys a live entry (pa0, pb0: the
+// tops before the step; cI, cL: inner and leaf hits of the step, cI + cL <= 4):
+//   - a lane steps only with pb0 - pa0 >= kWideRoom - 1 = 3: the slots pa0 .. pb0, at least four, are free, and every store of the step
+//     lands in pa0 .. pa0 + 3 or pb0 - 3 .. pb0, inside them (and inside the lane's LDS share);
+//   - the inner stores run first.  One that does not advance leaves garbage at the top, which is free: the next advancing store
+//     overwrites it, and at worst it is slot pa0 + 3 == pb0, which a later real leaf store overwrites or which stays free;
+//   - after the step the live inner entries end at pa0 + cI - 2 (the one at pa0 + cI - 1 is in the register, its copy is dead);
+//   - a leaf store that does not advance writes at pb0 - s, s <= cL leaf hits before it.  It would reach a live inner entry only with
+//     pb0 - cL <= pa0 + cI - 2, i.e. pb0 - pa0 <= cI + cL - 2 <= 2: not with the room a step requires.  Nor does it reach a live leaf
+//     entry: those are above pb0, or at pb0 - k, k < s, written earlier in this step;
+//   - an empty slot (NaN planes, link kDone) never hits, so it never advances; with no inner hit the pop reads sl[pa0 - 1], which no
+//     store of the step touches; the hand-over to a helper reads sl[bottom], live and below pa0; the reset of an occluded shadow ray
+//     (pa = bottom, pb = S - 1) declares everything dead.
+// The argument uses the room condition only, not kWideStack: it holds for the 8-word test build as for the shipped 24 words.
 #include "pt_traverse_deferred.hpp"
 #include "pt_travtables.hpp"
 #include "pt_launch.hpp"
@@ -559,8 +577,9 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
         if (STATS && lane == 0u) { itersAll++; if (generalSlabs) itersGeneral++; }
 #pragma unroll
         for (int rep = 0; rep < REPS; rep++) {
-            // the four slab tests of the node in q0 .. lk, then: the first hit inner slot is the next node, the other hits are pushed (inner nodes from the
-            // bottom, leaves from the top) -- ranks by prefix counts, one predicated LDS store per slot and stack (nested regions per slot: the same time)
+            // the four slab tests of the node in q0 .. lk, then: the hits are pushed (inner nodes from the bottom, leaves from the top) by
+            // "store at the top, advance the top by the predicate" -- eight unconditional LDS stores, no region and no rank per slot -- and
+            // the LAST hit inner slot, still in its register, is the next node (why no store destroys a live entry: the head of this file)
 #define GMUPT_WIDE_NODE_COMPUTE(INTOP) \
             { if (STATS) { if (kind == 0) tcE.inner++; else tcS.inner++; if (prefix_rank(__ballot(1)) == 0) { if (phase == 0) wInE++; else wInS++; } \
                            if (INTOP) { if (kind == 0) topE++; else topS++; } boxes += (uint32_t)ts.wnodes[cur].aux[1]; } \
@@ -568,19 +587,19 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
               slab_hits4(q0, q1, q2, q3, q4, q5, ray, h0, h1, h2, h3, generalSlabs); \
               const bool i0 = h0 & (lk.x >= 0), i1 = h1 & (lk.y >= 0), i2 = h2 & (lk.z >= 0), i3 = h3 & (lk.w >= 0); \
               const bool f0 = h0 & (lk.x < 0), f1 = h1 & (lk.y < 0), f2 = h2 & (lk.z < 0), f3_ = h3 & (lk.w < 0); \
-              const uint32_t r1 = i0 ? 1u : 0u, r2 = r1 + (i1 ? 1u : 0u), r3 = r2 + (i2 ? 1u : 0u), cI = r3 + (i3 ? 1u : 0u);   /* inner hits before slot k */ \
-              const uint32_t s1 = f0 ? 1u : 0u, s2 = s1 + (f1 ? 1u : 0u), s3 = s2 + (f2 ? 1u : 0u), cL = s3 + (f3_ ? 1u : 0u);  /* leaf hits before slot k */ \
-              int nxt = i0 ? lk.x : (i1 ? lk.y : (i2 ? lk.z : (i3 ? lk.w : kDone)));                                            /* the first hit inner slot is the next node */ \
-              if (i1 & (r1 != 0u)) sl[(pa + r1 - 1u) * kDefBlock] = lk.y; \
-              if (i2 & (r2 != 0u)) sl[(pa + r2 - 1u) * kDefBlock] = lk.z; \
-              if (i3 & (r3 != 0u)) sl[(pa + r3 - 1u) * kDefBlock] = lk.w; \
-              if (f0) sl[pb * kDefBlock] = lk.x; \
-              if (f1) sl[(pb - s1) * kDefBlock] = lk.y; \
-              if (f2) sl[(pb - s2) * kDefBlock] = lk.z; \
-              if (f3_) sl[(pb - s3) * kDefBlock] = lk.w; \
-              pa += cI != 0u ? cI - 1u : 0u; pb -= cL; \
-              if (STATS) { if (kind == 0) tcE.leaves += cL; else tcS.leaves += cL; } \
-              if (nxt < 0) { if (pa > bottom) { pa--; nxt = sl[pa * kDefBlock]; } else { pa = 0; bottom = 0; } }   /* (an empty inner stack frees its dead entries) */ \
+              const uint32_t pa0 = pa, pb0 = pb; \
+              sl[pa * kDefBlock] = lk.x; pa += i0 ? 1u : 0u; \
+              sl[pa * kDefBlock] = lk.y; pa += i1 ? 1u : 0u; \
+              sl[pa * kDefBlock] = lk.z; pa += i2 ? 1u : 0u; \
+              sl[pa * kDefBlock] = lk.w; pa += i3 ? 1u : 0u; \
+              sl[pb * kDefBlock] = lk.x; pb -= f0 ? 1u : 0u; \
+              sl[pb * kDefBlock] = lk.y; pb -= f1 ? 1u : 0u; \
+              sl[pb * kDefBlock] = lk.z; pb -= f2 ? 1u : 0u; \
+              sl[pb * kDefBlock] = lk.w; pb -= f3_ ? 1u : 0u; \
+              if (STATS) { const uint32_t cL = pb0 - pb; if (kind == 0) tcE.leaves += cL; else tcS.leaves += cL; } \
+              int nxt = i3 ? lk.w : (i2 ? lk.z : (i1 ? lk.y : lk.x));                                                            /* the last hit inner slot is the next node */ \
+              if (pa != pa0) pa--;                                                                                               /* (it is the entry on top: never read back) */ \
+              else if (pa > bottom) { pa--; nxt = sl[pa * kDefBlock]; } else { pa = 0; bottom = 0; nxt = kDone; }               /* (an empty inner stack frees its dead entries) */ \
               cur = nxt; }
             vec4f q0, q1, q2, q3, q4, q5; vec4i lk;
             // fetch phase
