@@ -336,6 +336,22 @@ int gmupt_aov_ray(const gmupt_camera_buffer* cam, uint32_t x, uint32_t y, uint32
  *   (W > 0 whenever the centre weight is: with sane sigmas always.  If W is not > 0 the pixel keeps c_p and v_p.)
  * Output: RGBA32F, rgb = the last pass's colour of a valid pixel, alpha = the input alpha bits; an invalid pixel is its input texel.
  *   The PNG / PFM writers and progressive.to_rgba8 take it unchanged.
+ * Non-finite and extreme input is no error: pixels are not validated, the arithmetic above decides, on the device and on the host alike.
+ *   A colour channel that is +-inf: the pixel keeps its texel at every pass (its centre tap has d_l = NaN, so W is NaN and not > 0), and
+ *   every valid pixel with a chain of taps back to it takes a NaN in THAT channel (d_l = inf, E = 0, w = 0, C += 0 * inf): the poison
+ *   reaches 2 * (2^passes - 1) pixels per axis, 62 at five passes.  A NaN colour channel, position or albedo poisons nobody:
+ *   whoever taps such a pixel (the pixel itself included) has a NaN W in that pass and keeps its previous colour and variance.  A NaN
+ *   or zero depth (read for the centre only; 0 / 0 at the centre tap) makes the pixel's own W NaN and is invisible to others.  An
+ *   infinite albedo difference weighs 0 (d_a = inf, E = 0).  An infinite position component gives an infinite d_x, which weighs 0, or
+ *   a NaN d_x where the centre normal's component on that axis is exactly 0 (0 * inf), which freezes the tapping pixel for that pass;
+ *   the pixel that holds it has inf - inf = NaN at its own centre tap and keeps its colour.  A negative depth makes d_x negative
+ *   and weights above 1.  A normal
+ *   with a NaN component, or whose dot3 underflows to 0, makes the pixel invalid (copied bit for bit); one whose dot3 overflows
+ *   normalises to 0 and one with an infinite component to (NaN, 0, 0): max(0, .) drops the NaN, all its weights are 0 or NaN and it keeps
+ *   its colour.  Denormal colours and guides are kept, never flushed.  Sample-count and alpha words are opaque bits: any non-zero word
+ *   counts as sampled (0x80000000, NaN patterns) and comes through bit for bit.  The sign and payload of a NaN that the arithmetic
+ *   generates are not part of the rule (x86 and gfx950 differ there); which words are NaN, every finite word, every infinity and every
+ *   zero with its sign are.
  * Parameters: passes 1..5, every sigma finite and > 0, else GMUPT_ERR_INVALID_ARGUMENT. */
 typedef struct {
     uint32_t passes;      /* a-trous passes (steps 1, 2, 4, ..); default 5 */
@@ -407,6 +423,15 @@ int gmupt_denoise_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t 
  *   pointer swap); every call integrates against FROZEN and then replaces LAST with its own records.  The samples drawn between the last
  *   call of an accumulation and its restart are not in the history.  The previous rectangle may have any size and origin (reprojection
  *   needs no matching size), so a resize keeps the history.
+ * Non-finite and extreme input is no error; neither pixels, records nor cameras are validated.  The guard -1 <= fu <= W - 1 (fv likewise)
+ *   is false for NaN and +-inf, so a projection that is NaN, infinite or far outside (lambda 0, NaN or so small that d / lambda
+ *   overflows; dot3(F, F) = 0; pixelSize = 0; a NaN or infinite position) takes no history: N_h = 0, the beauty texel bit for bit,
+ *   count = nf.  fu = -1 with fx = 0 is inside the guard, but all weight lies on the column outside: Sw = 0, no history.  A tap whose
+ *   count is NaN or not > 0, whose valid word is not 1, or whose normal or position makes a test NaN does not count.  Non-finite colours
+ *   of counted taps propagate into the integrated texel and the new record (w * inf, and NaN where w is 0); a count of +inf gives
+ *   N_h = history_cap (min drops a NaN).  n is an integer word: nf = (float)n, and n + (uint32_t)ceilf(N_h) wraps modulo 2^32.  A
+ *   normal with a NaN component, or whose dot3 underflows to 0, makes the pixel no surface pixel.  The denoiser's paragraph holds for
+ *   the filter that follows, for generated NaNs and for alpha words.
  * Parameters: the spatial ones as gmupt_denoise_params; history_cap in [0, 65536]; min_normal_cos finite and <= 1; plane_dist finite
  *   and >= 0; else GMUPT_ERR_INVALID_ARGUMENT. */
 typedef struct {
@@ -519,6 +544,10 @@ int gmupt_renderer_refit(gmupt_renderer* r, gmupt_refit_info* info /* may be NUL
  *     flags  = 1
  *   Every other pixel (miss, light sphere): all zero.  The displacement form makes a triangle whose vertices did not move give
  *   prev_position == aov.position bit for bit (the ?: also keeps a -0.0f component): an unmoved scene takes exactly the existing path.
+ *   Non-finite and extreme input is no error: previous vertices are not validated.  A NaN in b_prev fails b_prev == b_now and propagates
+ *   into that component of prev_position; an infinite one gives +-inf, or NaN where a barycentric weight is 0 (0 * inf).  The sign and
+ *   payload of such a NaN are not part of the rule.  In the integration a record counts as moved only when its flags word is exactly 1;
+ *   with a non-finite prev_position the projection is NaN or outside the guard and the pixel takes no history.
  * gmupt_render_aovs_motion: gmupt_render_aovs (k_aov_raygen, the ray cast, k_aov_resolve, all unchanged; aov_out is bit for bit that
  *   call's output) plus k_mv_resolve per chunk on the same hits.  prev_verts: DEVICE memory, 3 floats per vertex, 4-byte aligned; num_verts
  *   must equal the bound vertex count.  motion_out: DEVICE memory, 16-byte aligned, motion_bytes >= width * height * 16.  Errors follow

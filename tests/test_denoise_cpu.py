@@ -113,7 +113,20 @@ def shifted(a, dy, dx):
 
 
 def reference(beauty, aov, passes=5, sigma_color=4.0, sigma_normal=128.0, sigma_plane=0.02, sigma_albedo=0.1):
-    """The filter of include/gmupt.h in float64 numpy (exp / pow / sqrt of numpy, sums in any order)."""
+    """The filter of include/gmupt.h in float64 numpy (exp / pow / sqrt of numpy, sums in any order), with the rule's IEEE behaviour on
+    non-finite values: max(0, .) drops a NaN (np.fmax), dexp2 is 0 at or below 2^-150 and inf above 2^128, and no denominator of a
+    valid pixel is masked."""
+    with np.errstate(all="ignore"):
+        return _reference(beauty, aov, passes, sigma_color, sigma_normal, sigma_plane, sigma_albedo)
+
+
+def _exp(d):
+    """exp(-d) as the rule's dexp2(-d * log2(e)): 0 for an exponent at or below -150, inf above 128, NaN kept."""
+    y = -d * 1.4426950408889634
+    return np.where(y > 128.0, np.inf, np.where(y > -150.0, np.exp2(np.clip(y, -150.0, 128.0)), np.where(np.isnan(y), np.nan, 0.0)))
+
+
+def _reference(beauty, aov, passes, sigma_color, sigma_normal, sigma_plane, sigma_albedo):
     u = aov.view(np.uint32)
     count = beauty[..., 3].view(np.uint32)
     nraw = aov[..., 4:7].astype(np.float64)
@@ -132,7 +145,7 @@ def reference(beauty, aov, passes=5, sigma_color=4.0, sigma_normal=128.0, sigma_
             m = ins & vq
             s1 += np.where(m, lq, 0); s2 += np.where(m, lq * lq, 0); cnt += m
     cnt = np.maximum(cnt, 1)
-    v = np.maximum(0.0, s2 / cnt - (s1 / cnt) ** 2)
+    v = np.fmax(0.0, s2 / cnt - (s1 / cnt) ** 2)
     h3 = {-1: 0.25, 0: 0.5, 1: 0.25}
     h5 = {-2: 1 / 16, -1: 0.25, 0: 0.375, 1: 0.25, 2: 1 / 16}
     for k in range(passes):
@@ -153,12 +166,12 @@ def reference(beauty, aov, passes=5, sigma_color=4.0, sigma_normal=128.0, sigma_
                 m = ins & ok & valid
                 nq = shifted(n, s * j, s * i)[0]; lq = shifted(l, s * j, s * i)[0]; xq = shifted(x, s * j, s * i)[0]
                 aq = shifted(a, s * j, s * i)[0]; cq = shifted(c, s * j, s * i)[0]; vq = shifted(v, s * j, s * i)[0]
-                cos = np.maximum(0.0, (n * nq).sum(-1))
+                cos = np.fmax(0.0, (n * nq).sum(-1))
                 wn = np.where(cos > 0, cos, 0) ** sigma_normal
                 dl = np.abs(l - lq) / den_l
                 dxp = np.abs((n * (xq - x)).sum(-1)) / den_x
                 da = np.abs(aq - a).sum(-1) / sigma_albedo
-                w = np.where(m, h5[i] * h5[j] * wn * np.exp(-(dl + dxp + da)), 0.0)
+                w = np.where(m, h5[i] * h5[j] * wn * _exp(dl + dxp + da), 0.0)
                 sw += w; sc += w[..., None] * np.where(m[..., None], cq, 0); sv += w * w * np.where(m, vq, 0)
         ok = valid & (sw > 0)
         c = np.where(ok[..., None], sc / np.where(sw > 0, sw, 1)[..., None], c)

@@ -209,12 +209,13 @@ def reference(beauty, aov, prev, prev_cam, prev_origin, history_cap=32.0, min_no
         has = sw > 0
         with np.errstate(invalid="ignore", divide="ignore"):
             hc = np.where(has[..., None], sc / sw[..., None], 0.0)
-            nh = np.where(has, np.minimum(history_cap, sn / sw), 0.0)
+            nh = np.where(has, np.fmin(history_cap, sn / sw), 0.0)          # the rule's min drops a NaN
     n = beauty[..., 3].view(np.uint32).astype(np.int64)
     nf = n.astype(np.float64)
     B = beauty[..., :3].astype(np.float64)
     use = surface & (nh > 0)
-    rgb = np.where(use[..., None], (nh[..., None] * hc + nf[..., None] * B) / np.maximum(nh + nf, 1e-30)[..., None], B)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        rgb = np.where(use[..., None], (nh[..., None] * hc + nf[..., None] * B) / (nh + nf)[..., None], B)
     ceil = np.ceil(nh).astype(np.int64)
     amb |= use & (np.abs(nh - np.round(nh)) < 1e-4)
     alpha = np.where(use, n + ceil, n).astype(np.uint32)
