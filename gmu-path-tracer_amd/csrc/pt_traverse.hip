@@ -7,7 +7,7 @@
 // are resolved by visit order, `t < distance` strict, :64-74), the Moeller-Trumbore operation order (:38-77), and the
 // shadow acceptance rule t in (1e-8, 1e8), |d t| < lightDistance (shadowRayCast.hlsl:16-47,88-91).
 // What is free: memory layout, loop structure, scheduling of the triangle tests, and -- for the any-hit shadow ray -- the visit order.
-#include "pt_traverse_deferred.hpp"
+#include "pt_cast_plumbing.hpp"
 #include "pt_launch.hpp"
 
 namespace gmupt {
@@ -228,13 +228,8 @@ __global__ __launch_bounds__(kDefBlock) void k_shadow_d(RenderParams p)
 // fetch of the walking lanes AND the triangle fetch of the lanes with a pending leaf, then does the slab tests and the triangle test.
 // A burst therefore costs no memory round trips of its own (REPS per loop iteration instead of REPS + BURST); what is tested, and in which
 // order per ray, is unchanged: leaves leave the per-lane FIFO in visit order.  BURST is unused here (one triangle record per step).
-#ifdef GMUPT_CAST_WAVES_PER_EU
-#define GMUPT_CAST_OCCUPANCY __attribute__((amdgpu_waves_per_eu(GMUPT_CAST_WAVES_PER_EU, GMUPT_CAST_WAVES_PER_EU)))
-#else
-#define GMUPT_CAST_OCCUPANCY
-#endif
 template <bool STATS, bool OVF, bool TOP, int REPS, int BURST>
-__global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(RenderParams p)
+__global__ __launch_bounds__(kDefBlock) void k_cast_f(RenderParams p)
 {
     GMUPT_DEF_LDS(TOP)
     shadow_counter_epilogue(p);
@@ -249,13 +244,9 @@ __global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(Rende
     const uint32_t* qSh = p.queues + (size_t)Q_SHADOW_RAY * p.P;
     const __amdgpu_buffer_rsrc_t rNodes = make_rsrc(ts.nodes, ts.triBase * 64u);              // ts.triBase = number of packed nodes
     const __amdgpu_buffer_rsrc_t rTris = make_rsrc(ts.tris, (p.scene.numTris + 1u) * 48u);    // + the sentinel record
-    uint32_t next = 0, end = 0, lastBase = 0;
-    uint32_t chunkBase = 0, qe0 = kQueueHole, qe1 = kQueueHole;  // the current chunk of queue entries, lane l holds entries l and 64 + l
+    GMUPT_CHUNK_CURSOR            // the current chunk of queue entries
     int phase = 0;
-#ifndef GMUPT_DRAIN_TIMING
-#define GMUPT_DRAIN_TIMING 0   // 1 (diagnostic build only): the plain kernel stamps its start, the moment a wave finds both queues empty, and its exit
-#endif
-    const unsigned long long tStart = (STATS || GMUPT_DRAIN_TIMING) ? wall_clock64() : 0ull;
+    const unsigned long long tStart = STATS ? wall_clock64() : 0ull;
     unsigned long long tDrain = 0ull; uint32_t drainIters = 0, drainBusy = 0;
     uint32_t rayInner = 0, census0 = 0, census1 = 0, census2 = 0, census3 = 0, topE = 0, topS = 0, helped = 0, nested = 0;
 
@@ -269,10 +260,9 @@ __global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(Rende
     int cur = kDone;
     uint32_t qHead = 0, qCount = 0;
     int ti = -1;
-    // ---- the drain (both queues exhausted): a wave is as slow as its longest ray, so the lanes that have finished HELP the ones still
-    // walking.  Boxes are never pruned, so a deferred subtree can be walked by another lane; the BOTTOM entry of a ray's stack is the
-    // subtree the ray would visit last, hence its hits only count if they are strictly closer than everything the owner finds itself
-    // (ties go to the earlier test, extensionRayCast.hlsl:64) -- and among helpers the later donated subtree is visited earlier.
+    // ---- the drain (pt_cast_plumbing.hpp): finished lanes HELP the ones still walking.  The BOTTOM entry of a ray's stack is the subtree
+    // the ray would visit last, hence its hits only count if they are strictly closer than everything the owner finds itself (ties go to the
+    // earlier test, extensionRayCast.hlsl:64) -- and among helpers the later donated subtree is visited earlier.
     int owner = -1;               // >= 0: this lane walks a subtree donated by lane `owner` (same ray, own stack, own leaf FIFO)
     uint32_t bottom = 1;          // lowest live entry of this lane's stack (entries below it were donated; the slot under it holds the sentinel)
     uint32_t outstanding = 0;     // owner: helpers that have not reported yet
@@ -281,25 +271,9 @@ __global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(Rende
     float tT = kFltMax, uT = 0.0f, vT = 0.0f; int refT = -1; uint32_t dT = 0;   // owner: best helper result so far (by t, then by LATER donation)
     const uint32_t lane = threadIdx.x & 63u;
 
-    // Watchdog: a persistent kernel must end whatever happens.  A wave of the bench scene runs ~150 loop iterations per launch, one of the
-    // 10 M-triangle scene ~600; a wave that reaches the limit has met a bug in the hand-over protocol of the drain: it flags the launch
-    // (GMUPT_STAT_CAST_ABORTED: results invalid) and leaves.  -DGMUPT_LOOP_DUMP also records the state of its lanes (debugging aid).
     uint32_t loopCount = 0;
     for (;;) {
-        if (++loopCount > p.castLoopCap) {   // (2^20 by default; GMUPT_CAST_LOOP_CAP)
-            if (lane == 0u) atomicOr(&p.stats->stackOverflow, 2u);
-#ifdef GMUPT_LOOP_DUMP
-            const unsigned long long mHave = __ballot(haveRay), mHelper = __ballot(haveRay && owner >= 0), mOut = __ballot(outstanding != 0u),
-                                     mWalk = __ballot(cur >= 0), mLeaf = __ballot(cur < 0 && cur != kDone), mPend = __ballot(qCount > 0 || ti >= 0);
-            if (lane == 0u && atomicAdd(&p.stats->castWaveEndHist[31], 1ull) == 0ull) {
-                p.stats->castWaveEndHist[0] = mHave; p.stats->castWaveEndHist[1] = mHelper; p.stats->castWaveEndHist[2] = mOut;
-                p.stats->castWaveEndHist[3] = mWalk; p.stats->castWaveEndHist[4] = mLeaf; p.stats->castWaveEndHist[5] = mPend;
-                p.stats->castWaveEndHist[6] = (unsigned long long)phase; p.stats->castWaveEndHist[7] = (unsigned long long)blockIdx.x * 100ull + (threadIdx.x >> 6);
-            }
-            if (mHave >> lane & 1ull) { p.stats->castWaveEndHist[8 + (lane & 15u)] = ((unsigned long long)(uint32_t)owner << 32) | (outstanding << 16) | (stk.ptr << 8) | bottom; }
-#endif
-            break;
-        }
+        GMUPT_WATCHDOG()
         if (phase == 2) { // wave-uniform: drain service
             // (a) helpers that have finished their subtree report to their owner
             const bool reports = haveRay && owner >= 0 && outstanding == 0u && cur == kDone && qCount == 0 && ti < 0;
@@ -310,17 +284,13 @@ __global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(Rende
             unsigned long long fin = __ballot(reports);
             while (fin) {
                 const int hl = __builtin_ctzll(fin); fin &= fin - 1ull;
-                const int ol = __builtin_amdgcn_readlane(owner, hl);
-                const float th = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, distance), hl));
-                const float uh = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hu), hl));
-                const float vh = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hv), hl));
-                const int rh = __builtin_amdgcn_readlane(hitRef, hl);
+                GMUPT_HELPER_REPORT()
                 const uint32_t dh = (uint32_t)__builtin_amdgcn_readlane((int)dno, hl);
                 if ((int)lane == ol) {
                     outstanding--;
                     if (rh >= 0) {
                         if (kind == 1) refT = rh;                                                       // any occluder decides a shadow ray
-                        else if (th < tT || (th == tT && dh > dT)) { tT = th; uT = uh; vT = vh; refT = rh; dT = dh; }
+                        else if (th < tT || (th == tT && dh > dT)) { tT = th; uT = uh; vT = vh; refT = rh; dT = dh; }   // later donation wins a tie
                     }
                 }
                 if ((int)lane == hl) { haveRay = false; owner = -1; tT = kFltMax; refT = -1; dT = 0; }
@@ -336,30 +306,22 @@ __global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(Rende
                 } else stu(p, F_IN_SHADOW, index, (hitRef >= 0 || refT >= 0) ? 1u : 0u);
                 haveRay = false; tT = kFltMax; refT = -1; dT = 0;
             }
-            // (c) free lanes take the bottom stack entry of lanes that still have deferred subtrees: the k-th free lane pairs with the k-th
-            //     donor, all pairs of the wave at once (the donors post their lane number to lane k, the takers fetch the ray from there)
+            // (c) free lanes take the bottom stack entry of lanes that still have deferred subtrees (drain_pair)
             const unsigned long long freeLanes = __ballot(!haveRay);
             if (wantHelp != 0ull && freeLanes != 0ull) {
-                const uint32_t nDonors = (uint32_t)__popcll(wantHelp), nFree = (uint32_t)__popcll(freeLanes);
-                const uint32_t nPairs = nDonors < nFree ? nDonors : nFree;
-                const bool isDonor = ((wantHelp >> lane) & 1ull) != 0ull;
-                const uint32_t dRank = prefix_rank(wantHelp), fRank = prefix_rank(freeLanes);
-                const bool gives = isDonor && dRank < nPairs, takes = !haveRay && fRank < nPairs;
+                const DrainPair pr = drain_pair(wantHelp, freeLanes, lane, haveRay);
                 int node = 0;
-                if (gives) {
+                if (pr.gives) {
                     int* slot = s_stack + bottom * kDefBlock + threadIdx.x;
                     node = *slot; *slot = kDone;           // the slot becomes the sentinel of what is left of the owner's stack
                     bottom++; outstanding++; donations++;
                     if (STATS) { helped++; if (owner >= 0) nested++; }   // nested: a helper gives a part of ITS subtree away
                 }
-                // lane k learns which lane the k-th donor is; a taker with rank k reads that number from lane k, then the ray from the donor
-                const int donorOfRank = __builtin_amdgcn_ds_permute((int)((gives ? dRank : 63u) << 2), gives ? (int)lane : 0);
-                const int src = __shfl(donorOfRank, takes ? (int)fRank : 0);
-                const int sl = takes ? src : (int)lane;
+                GMUPT_DRAIN_SOURCE(pr, sl)
                 const int node2 = __shfl(node, sl), k2 = __shfl(kind, sl), i2 = __shfl((int)index, sl), n2 = __shfl((int)donations, sl);
                 const float ox = __shfl(o.x, sl), oy = __shfl(o.y, sl), oz = __shfl(o.z, sl), dx = __shfl(d.x, sl), dy = __shfl(d.y, sl), dz = __shfl(d.z, sl);
                 const float lim = __shfl(distance, sl);
-                if (takes) {
+                if (pr.takes) {
                     haveRay = true; owner = src; kind = k2; index = (uint32_t)i2; dno = (uint32_t)n2; donations = 0;
                     o = mk3(ox, oy, oz); d = mk3(dx, dy, dz); invdir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
                     distance = k2 == 1 ? lim : kFltMax;     // shadow: the distance of the light; extension: no hit yet
@@ -375,50 +337,17 @@ __global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(Rende
         const unsigned long long idleMask = __ballot(idle);
         const int nIdle = __popcll(idleMask);
         if (nIdle == 64 || (nIdle >= (int)p.tuneRefill && phase < 2)) { // wave-uniform
-            while (next >= end && phase < 2) { // next chunk of the current queue, or the first one of the next queue
-                uint32_t base = 0;
-                const uint32_t count = phase == 0 ? countExt : countSh;
-                // towards the end of the LAST queue the chunks shrink: the waves then run dry within half the time of each other
-                // (the position is estimated from this wave's previous chunk: every other wave has taken about one since)
-                const uint32_t gridWaves = gridDim.x * (uint32_t)(kDefBlock / 64);
-#ifndef GMUPT_TAIL_CHUNKS
-#define GMUPT_TAIL_CHUNKS 2
-#endif
-                const bool tail = GMUPT_TAIL_CHUNKS && phase == 1 && lastBase + (uint32_t)GMUPT_TAIL_CHUNKS * gridWaves * p.raysPerWave > count;
-                const uint32_t req = tail ? (p.raysPerWave > 64u ? p.raysPerWave / 2u : p.raysPerWave) : p.raysPerWave;
-                if ((threadIdx.x & 63) == 0) base = atomicAdd(&p.travCounters[phase], req);
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                if (base < count) {
-                    lastBase = base;
-                    next = base; end = (base + req < count) ? base + req : count;
-                    // the whole chunk of queue entries goes into two registers per lane (two coalesced loads): a refill then takes
-                    // its entry from a neighbour's register instead of starting with a dependent queue read
-                    chunkBase = base;
-                    const uint32_t* q = phase == 0 ? qExt : qSh;
-                    qe0 = (base + lane < end) ? q[base + lane] : kQueueHole;
-                    qe1 = (base + 64u + lane < end) ? q[base + 64u + lane] : kQueueHole;
-                }
-                else { phase++; next = end = 0; lastBase = 0; }
-            }
-#ifndef GMUPT_KNOCKOUT
-#define GMUPT_KNOCKOUT 0   // timing experiments only (tools/knockout.py; results are wrong): 1 no result stores, 3 no triangle tests
-#endif
-            // queue entry of every idle lane, out of the chunk registers (all lanes execute the two shuffles: a lane that sits out
-            // would not lend its registers)
-            const uint32_t my = next + prefix_rank(idleMask);
-            const uint32_t entry = idle ? ((my - chunkBase) & 127u) : 0u;
-            const uint32_t entryLo = (uint32_t)__shfl((int)qe0, (int)(entry & 63u)), entryHi = (uint32_t)__shfl((int)qe1, (int)(entry & 63u));
+            GMUPT_CLAIM_CHUNK(GMUPT_PLAIN_ENTRY, false)
+            GMUPT_CHUNK_SHUFFLE()
             if (idle) {
                 // the next ray first: its loads are in flight while the finished ray is written back
-                const bool take = my < end;
-                const uint32_t newIndex = take ? (entry < 64u ? entryLo : entryHi) : kQueueHole;   // extensionRayCast.hlsl:210 / shadowRayCast.hlsl:159
+                GMUPT_CHUNK_ENTRY()
                 const bool newRay = take && (phase != 0 || newIndex != kQueueHole); // holes only exist in the extension queue
                 f3 newO = mk3(0, 0, 0), newD = mk3(0, 0, 1); float newDist = kFltMax;
                 if (newRay) {
                     if (phase == 0) { newO = ld3(p, F_RAY_OX, newIndex); newD = ld3(p, F_RAY_DX, newIndex); }                 // :213-214
                     else { newO = ld3(p, F_SH_OX, newIndex); newD = ld3(p, F_SH_DX, newIndex); newDist = ldf(p, F_LIGHT_DIST, newIndex); } // :162-164
                 }
-                if (haveRay && GMUPT_KNOCKOUT == 1) haveRay = false;
                 if (haveRay) {
                     if (STATS && kind == 0) { atomicAdd(&p.stats->rayInnerHist[rayInner / 16u < 31u ? rayInner / 16u : 31u], 1ull); rayInner = 0; }
                     if (kind == 0) {
@@ -442,10 +371,9 @@ __global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(Rende
                 }
             }
             if (nIdle == 64 && phase == 2) break; // nothing in flight and both queues are exhausted (wave-uniform)
-            next = (next + (uint32_t)nIdle < end) ? next + (uint32_t)nIdle : end;
+            GMUPT_CHUNK_ADVANCE()
         }
 
-        if (GMUPT_DRAIN_TIMING && !STATS && phase == 2) { if (tDrain == 0ull) tDrain = wall_clock64(); drainIters++; }
         if (STATS) { // lane census: where do the 64 lanes of a wave spend the loop iterations?
             const bool pendingNow = (qCount > 0) || (ti >= 0);
             if (phase == 2) { if (tDrain == 0ull) tDrain = wall_clock64(); drainIters++; drainBusy += __popcll(__ballot(haveRay && !(cur == kDone && !pendingNow))); }
@@ -473,8 +401,7 @@ __global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(Rende
                              if (TOP && (uint32_t)cur < top_count<OVF>(ts)) { if (kind == 0) topE++; else topS++; } }
                 cur = inner_compute_flat<OVF>(na, nb, nc, nd, o, invdir, stk, p.stats);
             }
-            if (GMUPT_KNOCKOUT == 3) { if (cur < 0 && cur != kDone) cur = stk.pop(); }
-            else if (cur < 0 && cur != kDone && qCount < (uint32_t)kFifo) {
+            if (cur < 0 && cur != kDone && qCount < (uint32_t)kFifo) {
                 if (STATS) { if (kind == 0) tcE.leaves++; else tcS.leaves++; }
                 fifo[((qHead + qCount) & (kFifo - 1)) * kDefBlock] = ~cur;
                 qCount++;
@@ -496,25 +423,11 @@ __global__ __launch_bounds__(kDefBlock) GMUPT_CAST_OCCUPANCY void k_cast_f(Rende
             }
         }
     }
-    if (GMUPT_DRAIN_TIMING && !STATS && (threadIdx.x & 63) == 0) {
-        const unsigned long long tEnd = wall_clock64();
-        atomicAdd(&p.stats->castDrainClocks, tDrain ? tEnd - tDrain : 0ull); atomicAdd(&p.stats->castDrainIters, (unsigned long long)drainIters);
-        atomicAdd(&p.stats->castWaves, 1ull); atomicAdd(&p.stats->castWaveClocks, tEnd - tStart); atomicMax(&p.stats->castWaveClocksMax, tEnd - tStart);
-        const unsigned long long life = tEnd - tStart, bucket = life / 4000ull;    // 40-us buckets of the wave lifetimes (all waves start together)
-        atomicAdd(&p.stats->castWaveEndHist[bucket < 31ull ? bucket : 31ull], 1ull);
-    }
-    if (STATS) { flush_counts(p.stats, tcE, raysE, true); flush_wave_iters(p.stats, wInE, wTrE, true);
-                 flush_counts(p.stats, tcS, raysS, false); flush_wave_iters(p.stats, wInS, wTrS, false);
-                 flush_sum(&p.stats->extTopInner, topE); flush_sum(&p.stats->shTopInner, topS); flush_sum(&p.stats->castHelperSubtrees, helped); flush_sum(&p.stats->castNestedHelpers, nested);
-                 if ((threadIdx.x & 63) == 0) {
+    if (STATS) { flush_cast_counts(p.stats, tcE, raysE, wInE, wTrE, tcS, raysS, wInS, wTrS, topE, topS, helped, nested);
+                 if (lane == 0u) {
                      const unsigned long long tEnd = wall_clock64();
-                     const unsigned long long life = tEnd - tStart;
-                     atomicAdd(&p.stats->castDrainClocks, tDrain ? tEnd - tDrain : 0ull); atomicAdd(&p.stats->castDrainIters, (unsigned long long)drainIters);
-                     atomicAdd(&p.stats->castDrainBusyLanes, (unsigned long long)drainBusy);
-                     atomicAdd(&p.stats->castWaves, 1ull); atomicAdd(&p.stats->castWaveClocks, life); atomicMax(&p.stats->castWaveClocksMax, life);
-                     atomicAdd(&p.stats->castWaveEndHist[life / 5000ull < 31ull ? life / 5000ull : 31ull], 1ull);
-                     atomicAdd(&p.stats->laneCensus[0], (unsigned long long)census0); atomicAdd(&p.stats->laneCensus[1], (unsigned long long)census1);
-                     atomicAdd(&p.stats->laneCensus[2], (unsigned long long)census2); atomicAdd(&p.stats->laneCensus[3], (unsigned long long)census3);
+                     flush_drain_share(p.stats, tEnd, tDrain, drainIters, drainBusy); atomicAdd(&p.stats->castWaves, 1ull);
+                     flush_wave_life(p.stats, tEnd - tStart, census0, census1, census2, census3);
                  } }
 }
 

@@ -267,9 +267,6 @@ __device__ __forceinline__ int inner_step(const TravScene& ts, int cur, f3 o, f3
     const float4* n = reinterpret_cast<const float4*>(ts.nodes + cur);
     const float4 a = n[0], b = n[1], c = n[2];
     const int4 d = *reinterpret_cast<const int4*>(n + 3);
-#ifdef GMUPT_EXPERIMENT_EXTRA_LOAD
-    { const volatile float4* vn = reinterpret_cast<const volatile float4*>(n); float ex = vn[0].x; float ey = vn[2].y; asm volatile("" :: "v"(ex), "v"(ey)); }
-#endif
     const float leftHit = ray_box(a.x, a.y, a.z, a.w, b.x, b.y, o, invdir);
     const float rightHit = ray_box(b.z, b.w, c.x, c.y, c.z, c.w, o, invdir);
     if (leftHit > 0.0f && rightHit > 0.0f) {

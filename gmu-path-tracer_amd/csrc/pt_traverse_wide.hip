@@ -25,7 +25,7 @@
 // nodes still to visit from the bottom up, leaves still to test from the top down.  A step fetches one WNode (seven 16-byte pieces:
 // six planes x four slots, four links), does the four slab tests, keeps one hit inner slot as the next node and pushes the other
 // hits.  Leaves are tested in wave-wide bursts, one triangle record per step, fetched together with the node of the walking lanes
-// (as k_cast_f).  A lane whose inner stack alone fills its LDS share gives the wide walk of that ray up and parks it as well (the exact
+// (everything around the walk is pt_cast_plumbing.hpp).  A lane whose inner stack alone fills its LDS share gives the wide walk of that ray up and parks it as well (the exact
 // walk has a bounds-checked global overflow).  Drain: finished lanes take the BOTTOM inner entry of busy lanes (the largest subtree
 // left) and report their best hit back; results merge by "smaller t wins, equal t is a tie".
 //
@@ -46,7 +46,7 @@
 //     store of the step touches; the hand-over to a helper reads sl[bottom], live and below pa0; the reset of an occluded shadow ray
 //     (pa = bottom, pb = S - 1) declares everything dead.
 // The argument uses the room condition only, not kWideStack: it holds for the 8-word test build as for the shipped 24 words.
-#include "pt_traverse_deferred.hpp"
+#include "pt_cast_plumbing.hpp"
 #include "pt_travtables.hpp"
 #include "pt_launch.hpp"
 
@@ -335,8 +335,7 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
     const __amdgpu_buffer_rsrc_t rTris = make_rsrc(ts.tris, (p.scene.numTris + 1u) * 48u);    // + the sentinel record (the exact walk; the source-triangle numbers)
     const __amdgpu_buffer_rsrc_t rPairs = make_rsrc(ts.pairs, ts.numPairs * 80u);
     const uint32_t topCount = ts.wideTopCount;
-    uint32_t next = 0, end = 0, lastBase = 0;
-    uint32_t chunkBase = 0, qe0 = kQueueHole, qe1 = kQueueHole;  // the current chunk of queue entries, lane l holds entries l and 64 + l
+    GMUPT_CHUNK_CURSOR            // the current chunk of queue entries
     int phase = 0;
     uint32_t census0 = 0, census1 = 0, census2 = 0, census3 = 0, topE = 0, topS = 0, helped = 0, nested = 0, boxes = 0, pairFetches = 0, itersAll = 0, itersGeneral = 0;
 
@@ -372,12 +371,11 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
          else IO::finish_any(p, index, hitRef >= 0 ? 1u : 0u); \
          haveRay = false; redo = false; } while (0)
 
-    // Watchdog: a persistent kernel must end whatever happens (see k_cast_f)
     uint32_t loopCount = 0;
     const unsigned long long tStart = STATS ? wall_clock64() : 0ull;   // (collect_stats: wave lifetimes, share of the drain)
     unsigned long long tDrain = 0ull; uint32_t drainIters = 0, drainBusy = 0;
     for (;;) {
-        if (++loopCount > p.castLoopCap) { if (lane == 0u) atomicOr(&p.stats->stackOverflow, 2u); break; }
+        GMUPT_WATCHDOG()
         const bool leavesEmpty = pb == (uint32_t)(S - 1);
         if (STATS && phase == 2) { if (tDrain == 0ull) tDrain = wall_clock64(); drainIters++; drainBusy += (uint32_t)__popcll(__ballot(haveRay)); }
         if (phase == 2) { // wave-uniform: drain service
@@ -387,11 +385,7 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
             unsigned long long fin = __ballot(reports);
             while (fin) {
                 const int hl = __builtin_ctzll(fin); fin &= fin - 1ull;
-                const int ol = __builtin_amdgcn_readlane(owner, hl);
-                const float th = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, distance), hl));
-                const float uh = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hu), hl));
-                const float vh = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hv), hl));
-                const int rh = __builtin_amdgcn_readlane(hitRef, hl);
+                GMUPT_HELPER_REPORT()
                 const int redoh = __builtin_amdgcn_readlane((int)redo, hl);
                 if ((int)lane == ol) {
                     outstanding--;
@@ -399,7 +393,7 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
                     if (rh >= 0) {
                         if (kind == 1) refT = rh;                                                       // any occluder decides a shadow ray
                         else if (th < tT) { tT = th; uT = uh; vT = vh; refT = rh; }
-                        else if (th == tT) redoT = true;
+                        else if (th == tT) redoT = true;                                                // a tie parks the ray
                     }
                 }
                 if ((int)lane == hl) { haveRay = false; owner = -1; tT = kFltMax; refT = -1; redoT = false; redo = false; }
@@ -416,27 +410,21 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
             // (a lane whose walk has ended never gives: an occluded shadow ray leaves its stack behind, and those subtrees no longer matter)
             const unsigned long long wantHelp = __ballot(haveRay && cur != kDone && pa > bottom && donations < 12u);
             if (wantHelp != 0ull && done) GMUPT_WIDE_FINISH();
-            // (c) free lanes take the bottom inner entry of lanes that still have some: the k-th free lane pairs with the k-th donor
+            // (c) free lanes take the bottom inner entry of lanes that still have some (drain_pair)
             const unsigned long long freeLanes = __ballot(!haveRay);
             if (wantHelp != 0ull && freeLanes != 0ull) {
-                const uint32_t nDonors = (uint32_t)__popcll(wantHelp), nFree = (uint32_t)__popcll(freeLanes);
-                const uint32_t nPairs = nDonors < nFree ? nDonors : nFree;
-                const bool isDonor = ((wantHelp >> lane) & 1ull) != 0ull;
-                const uint32_t dRank = prefix_rank(wantHelp), fRank = prefix_rank(freeLanes);
-                const bool gives = isDonor && dRank < nPairs, takes = !haveRay && fRank < nPairs;
+                const DrainPair pr = drain_pair(wantHelp, freeLanes, lane, haveRay);
                 int node = 0;
-                if (gives) {
+                if (pr.gives) {
                     node = sl[bottom * kDefBlock];
                     bottom++; outstanding++; donations++;
                     if (STATS) { helped++; if (owner >= 0) nested++; }
                 }
-                const int donorOfRank = __builtin_amdgcn_ds_permute((int)((gives ? dRank : 63u) << 2), gives ? (int)lane : 0);
-                const int src = __shfl(donorOfRank, takes ? (int)fRank : 0);
-                const int srcLane = takes ? src : (int)lane;
+                GMUPT_DRAIN_SOURCE(pr, srcLane)
                 const int node2 = __shfl(node, srcLane), k2 = __shfl(kind, srcLane), i2 = __shfl((int)index, srcLane);
                 const float ox = __shfl(ray.oxy.x, srcLane), oy = __shfl(ray.oxy.y, srcLane), oz = __shfl(ray.ozi.x, srcLane), dx = __shfl(ray.dxy.x, srcLane), dy = __shfl(ray.dxy.y, srcLane), dz = __shfl(ray.dzz.x, srcLane);
                 const float lim = __shfl(distance, srcLane);
-                if (takes) {
+                if (pr.takes) {
                     haveRay = true; owner = src; kind = k2; index = (uint32_t)i2; donations = 0;
                     ray_set(ray, mk3(ox, oy, oz), mk3(dx, dy, dz));
                     distance = k2 == 1 ? lim : kFltMax;     // shadow: the distance of the light; extension: no hit yet
@@ -510,32 +498,11 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
             }
         }
         if (nIdle == 64 || (nIdle >= (int)p.tuneRefill && phase < 2)) { // wave-uniform
-            while (next >= end && phase < 2) { // next chunk of the current queue, or the first one of the next queue
-                uint32_t base = 0;
-                const uint32_t count = phase == 0 ? countExt : countSh;
-                const uint32_t gridWaves = gridDim.x * (uint32_t)(kDefBlock / 64);
-                const bool tail = phase == 1 && lastBase + 2u * gridWaves * p.raysPerWave > count;   // towards the end of the last queue the chunks shrink
-                const bool tail2 = p.wideQuarterTail && phase == 1 && lastBase + gridWaves * p.raysPerWave / 2u > count;            // the last half round: quarter chunks (large tables only)
-                const uint32_t req = tail2 ? (p.raysPerWave > 32u ? p.raysPerWave / 4u : p.raysPerWave) : tail ? (p.raysPerWave > 64u ? p.raysPerWave / 2u : p.raysPerWave) : p.raysPerWave;
-                if (lane == 0u) base = atomicAdd(&p.travCounters[phase], req);
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                if (base < count) {
-                    lastBase = base;
-                    next = base; end = (base + req < count) ? base + req : count;
-                    chunkBase = base;
-                    const uint32_t* q = phase == 0 ? qExt : qSh;
-                    qe0 = (base + lane < end) ? IO::entry(q, base + lane) : kQueueHole;
-                    qe1 = (base + 64u + lane < end) ? IO::entry(q, base + 64u + lane) : kQueueHole;
-                }
-                else { phase++; next = end = 0; lastBase = 0; }
-            }
-            const uint32_t my = next + prefix_rank(idleMask);
-            const uint32_t entry = idle ? ((my - chunkBase) & 127u) : 0u;
-            const uint32_t entryLo = (uint32_t)__shfl((int)qe0, (int)(entry & 63u)), entryHi = (uint32_t)__shfl((int)qe1, (int)(entry & 63u));
+            GMUPT_CLAIM_CHUNK(IO::entry, p.wideQuarterTail)   // (the last half round in quarter chunks: large tables only)
+            GMUPT_CHUNK_SHUFFLE()
             if (idle) {
                 // the next ray first: its loads are in flight while the finished ray is written back
-                const bool take = my < end;
-                const uint32_t newIndex = take ? (entry < 64u ? entryLo : entryHi) : kQueueHole;   // extensionRayCast.hlsl:210 / shadowRayCast.hlsl:159
+                GMUPT_CHUNK_ENTRY()
                 const bool newRay = take && (phase != 0 || newIndex != kQueueHole); // holes only exist in the extension queue
                 f3 newO = mk3(0, 0, 0), newD = mk3(0, 0, 1); float newDist = kFltMax;
                 if (newRay) {
@@ -555,7 +522,7 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
                 }
             }
             if (nIdle == 64 && phase == 2) break; // nothing in flight and both queues are exhausted (wave-uniform)
-            next = (next + (uint32_t)nIdle < end) ? next + (uint32_t)nIdle : end;
+            GMUPT_CHUNK_ADVANCE()
         }
 
         // ---- REPS steps; a burst (wave-uniform, decided once per iteration) adds one triangle test per step to the lanes with leaves pending
@@ -649,19 +616,12 @@ __global__ __launch_bounds__(kDefBlock) void k_cast_w(typename IO::Params p)
 #undef GMUPT_WIDE_MERGE_OWN
 #undef GMUPT_WIDE_FINISH
 #undef GMUPT_WIDE_NODE_COMPUTE
-    if (STATS) { flush_counts(p.stats, tcE, raysE, true); flush_wave_iters(p.stats, wInE, wTrE, true);
-                 flush_counts(p.stats, tcS, raysS, false); flush_wave_iters(p.stats, wInS, wTrS, false);
-                 flush_sum(&p.stats->extTopInner, topE); flush_sum(&p.stats->shTopInner, topS); flush_sum(&p.stats->castHelperSubtrees, helped);
-                 flush_sum(&p.stats->castNestedHelpers, nested); flush_sum(&p.stats->wideBoxTests, boxes); flush_sum(&p.stats->wideIters, itersAll); flush_sum(&p.stats->wideGeneralIters, itersGeneral); flush_sum(&p.stats->widePairFetches, pairFetches);
+    if (STATS) { flush_cast_counts(p.stats, tcE, raysE, wInE, wTrE, tcS, raysS, wInS, wTrS, topE, topS, helped, nested);
+                 flush_sum(&p.stats->wideBoxTests, boxes); flush_sum(&p.stats->wideIters, itersAll); flush_sum(&p.stats->wideGeneralIters, itersGeneral); flush_sum(&p.stats->widePairFetches, pairFetches);
                  if (lane == 0u) {
-                     atomicAdd(&p.stats->castWaves, 1ull);
-                     { const unsigned long long tEnd = wall_clock64(), life = tEnd - tStart;     // 100 MHz ticks
-                       atomicAdd(&p.stats->castDrainClocks, tDrain ? tEnd - tDrain : 0ull); atomicAdd(&p.stats->castDrainIters, (unsigned long long)drainIters);
-                       atomicAdd(&p.stats->castDrainBusyLanes, (unsigned long long)drainBusy);
-                       atomicAdd(&p.stats->castWaveClocks, life); atomicMax(&p.stats->castWaveClocksMax, life);
-                       atomicAdd(&p.stats->castWaveEndHist[life / 5000ull < 31ull ? life / 5000ull : 31ull], 1ull); }
-                     atomicAdd(&p.stats->laneCensus[0], (unsigned long long)census0); atomicAdd(&p.stats->laneCensus[1], (unsigned long long)census1);
-                     atomicAdd(&p.stats->laneCensus[2], (unsigned long long)census2); atomicAdd(&p.stats->laneCensus[3], (unsigned long long)census3);
+                     atomicAdd(&p.stats->castWaves, 1ull); const unsigned long long tEnd = wall_clock64();
+                     flush_drain_share(p.stats, tEnd, tDrain, drainIters, drainBusy);
+                     flush_wave_life(p.stats, tEnd - tStart, census0, census1, census2, census3);
                  } }
 }
 

@@ -1,5 +1,5 @@
-"""Timing experiment: the fused ray-cast launch repeated on a FIXED set of queues (snapshot of the steady state), for builds with
-parts of the kernel knocked out (GMUPT_KNOCKOUT builds give wrong results; only their time is of interest)."""
+"""Timing experiment: the fused ray-cast launch repeated on a FIXED set of queues (snapshot of the steady state), without the shading
+stages: the kernel GMUPT_TRAVERSAL selects, or the one of another build of the library (GMUPT_LIB)."""
 import os, sys, time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import numpy as np, gmupt_pkg
