@@ -231,6 +231,27 @@ class TreeoptInfo(C.Structure):
 assert C.sizeof(TreeoptInfo) == 40
 
 
+class ConvergeParams(C.Structure):
+    """gmupt_converge_params: 12 bytes (threshold not a NaN; min_batches >= 2)."""
+    _fields_ = [("threshold", C.c_float), ("min_batches", C.c_uint32), ("allow_pixels", C.c_uint32)]
+
+
+class ConvergeInfo(C.Structure):
+    """gmupt_converge_info: 56 bytes."""
+    _fields_ = [("pixels", C.c_uint32), ("unsampled", C.c_uint32), ("known", C.c_uint32), ("nonfinite", C.c_uint32), ("below", C.c_uint32),
+                ("converged", C.c_uint32), ("max_error", C.c_float), ("pad", C.c_uint32), ("sum_error", C.c_double), ("mean_error", C.c_double),
+                ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {"pixels": int(self.pixels), "unsampled": int(self.unsampled), "known": int(self.known), "nonfinite": int(self.nonfinite),
+                "below": int(self.below), "converged": bool(self.converged), "max_error": float(self.max_error),
+                "sum_error": float(self.sum_error), "mean_error": float(self.mean_error), "ms": float(self.ms)}
+
+
+converge_pixel_dtype = np.dtype([("n", "<u4"), ("k", "<u4"), ("w", "<u4"), ("pad", "<u4"), ("s", "<f8"), ("mean", "<f8"), ("m2", "<f8")])
+assert C.sizeof(ConvergeParams) == 12 and C.sizeof(ConvergeInfo) == 56 and converge_pixel_dtype.itemsize == 40
+
+
 class GmuptError(RuntimeError):
     def __init__(self, msg, code=0):
         super().__init__(msg)
@@ -325,6 +346,15 @@ SYMBOLS = {
     "gmupt_pose_update": (C.c_int, [_P, _P, _P, C.POINTER(PoseInfo)]),
     "gmupt_pose_update_device": (C.c_int, [_P, _P, _P, C.POINTER(PoseInfo)]),
     "gmupt_pose_destroy": (None, [_P]),
+    "gmupt_converge_default_params": (None, [C.POINTER(ConvergeParams)]),
+    "gmupt_converge_host": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(ConvergeParams), _P, C.POINTER(ConvergeInfo)]),
+    "gmupt_converge_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "gmupt_converge_destroy": (None, [_P]),
+    "gmupt_converge_reset": (C.c_int, [_P]),
+    "gmupt_converge_update": (C.c_int, [_P, C.POINTER(ConvergeParams), _P, C.POINTER(ConvergeInfo)]),
+    "gmupt_converge_update_image": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(ConvergeParams), _P, C.POINTER(ConvergeInfo)]),
+    "gmupt_converge_read_state": (C.c_int, [_P, _P, C.c_size_t]),
+    "gmupt_render_until": (C.c_int, [_P, _P, _P, C.POINTER(ConvergeParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(ConvergeInfo)]),
     "gmupt_debug_read_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_write_path_state": (C.c_int, [_P, _P, C.c_size_t]),
     "gmupt_debug_read_queues": (C.c_int, [_P, _P, C.c_size_t]),
@@ -613,6 +643,7 @@ class Renderer:
         self._temporals = []   # history handles of this renderer: closed before it
         self._normals = []     # Normals handles of this renderer: closed before it
         self._poses = []       # Pose handles of this renderer: closed before it
+        self._converges = []   # Converge handles of this renderer: closed before it
 
     def bind_scene(self, sb):
         self._scene = sb  # keep the buffers alive
@@ -682,6 +713,24 @@ class Renderer:
         it = C.c_uint32(0)
         _check(lib().gmupt_render_budget(self.h, camera.h, max_iterations, C.byref(it)))
         return it.value
+
+    def converge(self):
+        """A new convergence monitor of this renderer (Converge); closed with the renderer at the latest."""
+        return Converge(self)
+
+    def render_until(self, camera, converge, check_every=8, max_iterations=1 << 20, **params):
+        """gmupt_render_until: the loop of render_budget with converge.update() after every check_every iterations; ends on `converged`
+        or after max_iterations.  params: the converge_params fields (threshold, min_batches, allow_pixels).  Returns the last check's
+        info dict (all zero when no check ran) with "iterations" added."""
+        cp = converge_params(**params)
+        it = C.c_uint32(0)
+        ci = ConvergeInfo()
+        _check(lib().gmupt_render_until(self.h, camera.h, converge.h, C.byref(cp), check_every, max_iterations, C.byref(it), C.byref(ci)))
+        out = ci.as_dict()
+        if out["pixels"]:                            # a check ran: the monitor holds the state of this frame
+            converge._size = (self.height, self.width)
+        out["iterations"] = it.value
+        return out
 
     # ray queries (gmupt_trace_rays / gmupt_pick)
     def trace(self, closest=None, any=None, light_count=0, info=None):
@@ -870,7 +919,7 @@ class Renderer:
 
     def close(self):
         if self.h:
-            for t in self._temporals + self._normals + self._poses:
+            for t in self._temporals + self._normals + self._poses + list(self._converges):
                 t.close()
             lib().gmupt_renderer_destroy(self.h)
             self.h = _P()
@@ -894,6 +943,99 @@ class Temporal:
         if self.h:
             lib().gmupt_temporal_destroy(self.h)
             self.h = _P()
+
+
+def converge_params(**params):
+    """gmupt_converge_default_params with the given fields replaced (threshold, min_batches, allow_pixels)."""
+    cp = ConvergeParams()
+    lib().gmupt_converge_default_params(C.byref(cp))
+    for k, v in params.items():
+        if k not in ("threshold", "min_batches", "allow_pixels"):
+            raise TypeError("unknown convergence parameter %r" % k)
+        setattr(cp, k, v)
+    return cp
+
+
+class Converge:
+    """gmupt_converge: the convergence monitor of one renderer (include/gmupt.h "Convergence"): a per-pixel batch-mean state from which
+    every update estimates the standard error of the pixel's tone-mapped luminance mean.  It uses the renderer's device and stream and
+    is closed with it at the latest."""
+
+    def __init__(self, renderer):
+        self.renderer = renderer
+        self.h = _P()
+        self._size = None   # (H, W) of the state, once an update has run
+        _check(lib().gmupt_converge_create(renderer.h, C.byref(self.h)))
+        renderer._converges.append(self)
+
+    def _device(self):
+        import torch
+        return torch.device("cuda", getattr(self.renderer.dev, "index", 0))
+
+    def update(self, error=False, **params):
+        """gmupt_converge_update on the renderer's accumulation target, behind its pending iterations.  Returns the info dict; with
+        error=True (info, error plane), the plane an (H, W) float32 torch tensor on the renderer's GPU (-1 = unknown)."""
+        cp = converge_params(**params)
+        ci = ConvergeInfo()
+        H, W = self.renderer.height, self.renderer.width
+        err = None
+        if error:
+            import torch
+            err = torch.empty((H, W), dtype=torch.float32, device=self._device())
+            torch.cuda.current_stream(err.device).synchronize()
+        _check(lib().gmupt_converge_update(self.h, C.byref(cp), C.c_void_p(err.data_ptr()) if error else None, C.byref(ci)))
+        self._size = (H, W)
+        return (ci.as_dict(), err) if error else ci.as_dict()
+
+    def update_image(self, tensor, error=False, **params):
+        """gmupt_converge_update_image on an (H, W, 4) float32 torch tensor on the renderer's GPU (a = sample-count bits), e.g. a
+        gathered frame.  torch's current stream is synchronised first.  Returns as update()."""
+        import torch
+        if not isinstance(tensor, torch.Tensor) or tensor.dim() != 3 or tensor.shape[2] != 4 or tensor.dtype != torch.float32 or tensor.device != self._device():
+            raise GmuptError("update_image: an (H, W, 4) float32 tensor on %s" % self._device(), ERR_INVALID_ARGUMENT)
+        tensor = tensor.contiguous()
+        H, W = int(tensor.shape[0]), int(tensor.shape[1])
+        cp = converge_params(**params)
+        ci = ConvergeInfo()
+        err = torch.empty((H, W), dtype=torch.float32, device=tensor.device) if error else None
+        torch.cuda.current_stream(tensor.device).synchronize()
+        _check(lib().gmupt_converge_update_image(self.h, C.c_void_p(tensor.data_ptr()), W, H, C.byref(cp),
+                                                 C.c_void_p(err.data_ptr()) if error else None, C.byref(ci)))
+        self._size = (H, W)
+        return (ci.as_dict(), err) if error else ci.as_dict()
+
+    def state(self):
+        """gmupt_converge_read_state: the per-pixel state as an (H, W) array of converge_pixel_dtype (empty before the first update)."""
+        if self._size is None:
+            return np.zeros((0, 0), converge_pixel_dtype)
+        out = np.zeros(self._size, converge_pixel_dtype)
+        _check(lib().gmupt_converge_read_state(self.h, _ptr(out), out.nbytes))
+        return out
+
+    def reset(self):
+        """Every pixel back to the initial state: the next update starts the estimate afresh."""
+        _check(lib().gmupt_converge_reset(self.h))
+
+    def close(self):
+        if self.h:
+            lib().gmupt_converge_destroy(self.h)
+            self.h = _P()
+            if self in self.renderer._converges:
+                self.renderer._converges.remove(self)
+
+
+def converge_host(state, rgba, error=False, **params):
+    """gmupt_converge_host: the convergence rule on the CPU, bit for bit what Converge.update() computes.  state: an (H, W) array of
+    converge_pixel_dtype, updated in place (np.zeros is the initial state); rgba: (H, W, 4) float32.  Returns the info dict; with
+    error=True (info, (H, W) float32 error plane)."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+    if rgba.ndim != 3 or rgba.shape[2] != 4 or state.dtype != converge_pixel_dtype or state.shape != rgba.shape[:2] or not state.flags.c_contiguous:
+        raise GmuptError("converge_host: rgba must be (H, W, 4) float32 and state a contiguous (H, W) array of converge_pixel_dtype", ERR_INVALID_ARGUMENT)
+    cp = converge_params(**params)
+    ci = ConvergeInfo()
+    err = np.empty(rgba.shape[:2], np.float32) if error else None
+    _check(lib().gmupt_converge_host(_ptr(state), _ptr(rgba), rgba.shape[1], rgba.shape[0], C.byref(cp), _ptr(err) if error else None, C.byref(ci)))
+    return (ci.as_dict(), err) if error else ci.as_dict()
 
 
 class Normals:

@@ -343,6 +343,48 @@ extern "C" int gmupt_tree_cost_host(const gmupt_bvh_node* nodes, uint32_t n, gmu
     return GMUPT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ convergence: parameters and the host reference (pt_converge.cpp) of gmupt_converge_update
+static_assert(sizeof(gmupt_converge_pixel) == 40 && offsetof(gmupt_converge_pixel, s) == 16 && offsetof(gmupt_converge_pixel, m2) == 32, "gmupt_converge_pixel layout");
+static_assert(sizeof(gmupt_converge_params) == 12 && offsetof(gmupt_converge_params, allow_pixels) == 8, "gmupt_converge_params layout");
+static_assert(sizeof(gmupt_converge_info) == 56 && offsetof(gmupt_converge_info, max_error) == 24 && offsetof(gmupt_converge_info, sum_error) == 32 &&
+              offsetof(gmupt_converge_info, ms) == 48, "gmupt_converge_info layout");
+
+extern "C" void gmupt_converge_default_params(gmupt_converge_params* p)
+{
+    if (!p) return;
+    p->threshold = 0.0f; p->min_batches = 2; p->allow_pixels = 0;
+}
+
+int converge_params(const char* fn, const gmupt_converge_params* p, CvParams& out)
+{
+    gmupt_converge_params d;
+    if (!p) { gmupt_converge_default_params(&d); p = &d; }
+    if (p->min_batches < 2) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: min_batches = %u (at least 2)", fn, p->min_batches);
+    if (std::isnan(p->threshold)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: the threshold is a NaN", fn);
+    out.threshold = p->threshold; out.minBatches = p->min_batches; out.allowPixels = p->allow_pixels;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_converge_host(gmupt_converge_pixel* state, const float* rgba, uint32_t width, uint32_t height, const gmupt_converge_params* params,
+                                   float* error_or_null, gmupt_converge_info* info)
+{
+    const char* fn = "gmupt_converge_host";
+    if (!state || !rgba || !info) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null state, image or info", fn);
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0 || n > 0xFFFFFFFFull) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: image of %ux%u (1 .. 2^32 - 1 pixels)", fn, width, height);
+    CvParams prm;
+    GMUPT_TRY(converge_params(fn, params, prm));
+    CvPartial total;
+    try {
+        total = converge_host(state, rgba, (size_t)n, prm, error_or_null);
+    } catch (const std::bad_alloc&) {
+        return fail(GMUPT_ERR_OUT_OF_MEMORY, "%s: out of host memory for %ux%u pixels", fn, width, height);
+    }
+    cv_fill_info(total, (uint32_t)n, prm, info);
+    info->ms = 0.0;
+    return GMUPT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ pose: the host reference (pt_pose.cpp) of gmupt_pose_update
 extern "C" int gmupt_pose_host(const float* rest, uint32_t num_verts, const uint16_t* joints, const float* weights, uint32_t influences, const float* joint_mats,
                                uint32_t num_joints, const float* deltas, const float* target_weights, uint32_t num_targets, float* verts_out, uint32_t threads)

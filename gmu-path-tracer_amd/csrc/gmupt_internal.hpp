@@ -12,6 +12,7 @@
 #include "pt_treecost.hpp"
 #include "pt_treeopt.hpp"
 #include "pt_pose.hpp"
+#include "pt_converge.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
@@ -186,6 +187,16 @@ struct gmupt_pose {
     EventPair ev;
 };
 
+// the convergence monitor of one renderer (gmupt_converge_*): the state planes and partial summaries of a W x H image in one
+// allocation (converge_carve, pt_converge.hip), and which accumulation of the renderer the state belongs to
+struct gmupt_converge {
+    gmupt_renderer* r = nullptr;
+    uint32_t W = 0, H = 0;
+    DevMem mem; CvPlanes pl{};
+    bool seen = false; uint64_t generation = 0;   // the renderer's accumulation generation at the last gmupt_converge_update
+    EventPair ev;
+};
+
 // ------------------------------------------------------------------------------------------------ shared between units
 size_t kind_stride(gmupt_buffer_kind k);                                                                        // gmupt_capi.hip
 gmupt_buffer* buffer_alloc(gmupt_device* dev, gmupt_buffer_kind kind, size_t elems, size_t bytes, hipError_t* e);
@@ -196,6 +207,7 @@ int denoise_args(const char* fn, const void* beauty, const void* aov, uint32_t W
                  bool device, DnParams& prm);
 int temporal_params(const char* fn, const gmupt_temporal_params* p, DnParams& dn, TpParams& tp);
 int infill_params(const char* fn, const gmupt_infill_params* p, IfParams& out);
+int converge_params(const char* fn, const gmupt_converge_params* p, CvParams& out);
 // gmupt_capi_denoise.hip: the chains behind the temporal entry points; infill == nullptr is the chain without the infill stage
 int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
                      const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,

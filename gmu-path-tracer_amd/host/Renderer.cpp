@@ -283,6 +283,26 @@ gmupt_tree_cost_info Renderer::treeCost()
 	return info;
 }
 
+gmupt_converge_info Renderer::renderUntil(const gmupt_converge_params* params, unsigned checkEvery, unsigned maxIterations, float* deviceErrorOrNull,
+                                          unsigned* iterations)
+{
+	if (checkEvery == 0) throw std::invalid_argument("Renderer::renderUntil: checkEvery == 0");
+	if (!mConverge) { gmupt_converge* c = nullptr; check(gmupt_converge_create(mRenderer.get(), &c)); mConverge.reset(c); }
+	gmupt_converge_info info{};
+	unsigned k = 0;
+	while (k < maxIterations)
+	{
+		update(0.f); draw(); // Window::loop
+		k++;
+		if (k % checkEvery) continue;
+		check(gmupt_converge_update(mConverge.get(), params, deviceErrorOrNull, &info)); // behind the frames on the renderer's stream; synchronises
+		check(gmupt_synchronize(mRenderer.get()));                                       // the sticky ray-cast flags
+		if (info.converged) break;
+	}
+	if (iterations) *iterations = k;
+	return info;
+}
+
 gmupt_lbvh_info Renderer::rebuildScene(unsigned maxLeafSize, const std::vector<int32_t>* indices, unsigned optimizePasses, gmupt_treeopt_info* optimizeInfo)
 {
 	const gmupt_lbvh_info info = mScene.rebuildOnDevice(maxLeafSize, indices, optimizePasses, optimizeInfo);

@@ -90,6 +90,14 @@ public:
 	// "Tree cost"): after a refitScene it tells how far the refitted tree has degraded against its value at bind time, i.e. when
 	// rebuildScene pays.  Binds the scene on first use; touches neither the frame nor the accumulation.
 	gmupt_tree_cost_info treeCost();
+	// frames until the image is done (include/gmupt.h "Convergence"): update(0); draw(); as Window::loop does, and after every checkEvery
+	// frames the convergence monitor of this renderer (gmupt_converge_update through its own handle, created on first use) estimates the
+	// standard error of every pixel's tone-mapped luminance mean.  Ends at the first check that reports converged, or after maxIterations
+	// frames.  params == nullptr: gmupt_converge_default_params (reports only: runs to maxIterations).  deviceErrorOrNull: targetSize()
+	// floats of caller-owned device memory that every check fills with the per-pixel error (-1: unknown); it holds the last check's.
+	// *iterations = frames run by this call.  Returns the last check's info, all zero when no check ran.  checkEvery == 0 throws.
+	gmupt_converge_info renderUntil(const gmupt_converge_params* params, unsigned checkEvery, unsigned maxIterations, float* deviceErrorOrNull = nullptr,
+	                                unsigned* iterations = nullptr);
 	// geometry a refit does not cover (after Scene::setVertices with vertices that moved far, or with another triangle list): a new tree
 	// from the GPU LBVH builder (Scene::rebuildOnDevice) bound in place of the old one, the accumulation restarted and the temporal history
 	// dropped -- a new binding is a new geometry.  The host pass of the bind (the traversal tables) runs as for any bind.
@@ -109,6 +117,7 @@ private:
 	struct TemporalDeleter { void operator()(gmupt_temporal* t) const { gmupt_temporal_destroy(t); } };
 	struct NormalsDeleter { void operator()(gmupt_normals* n) const { gmupt_normals_destroy(n); } };
 	struct PoseDeleter { void operator()(gmupt_pose* p) const { gmupt_pose_destroy(p); } };
+	struct ConvergeDeleter { void operator()(gmupt_converge* c) const { gmupt_converge_destroy(c); } };
 
 	void* mHwnd;
 	std::unique_ptr<gmupt_device, DeviceDeleter> mDevice;
@@ -116,6 +125,7 @@ private:
 	std::unique_ptr<gmupt_temporal, TemporalDeleter> mTemporal; // history of denoiseTemporal (declared after mRenderer: destroyed before it)
 	std::unique_ptr<gmupt_normals, NormalsDeleter> mNormals;    // adjacency of refitScene(.., smoothNormals) (declared after mRenderer: destroyed before it)
 	std::unique_ptr<gmupt_pose, PoseDeleter> mPose;             // the rig of poseScene on the device (declared after mRenderer: destroyed before it)
+	std::unique_ptr<gmupt_converge, ConvergeDeleter> mConverge; // the monitor of renderUntil (declared after mRenderer: destroyed before it)
 	Scene mScene;
 	Resolution mResolution;
 	RowBand mBand;

@@ -28,6 +28,13 @@
 //                [--tree-cost]                            the surface-area cost of the bound tree (Renderer::treeCost), once after bind and once more
 //                                                         after --vertices is applied: one JSON line each with the gmupt_tree_cost_info fields, the
 //                                                         doubles as hex bit patterns; not with --ranks
+//                [--until-error T [--check-every N] [--allow-pixels M] [--error-map FILE.pfm]]
+//                                                         the frames run until the image is done (Renderer::renderUntil, include/gmupt.h "Convergence"):
+//                                                         after every N frames (default 8) the per-pixel standard error of the tone-mapped luminance
+//                                                         mean is estimated, and the loop ends when all but M pixels (default 0) lie at or below T, or
+//                                                         after --frames frames; one JSON line with the gmupt_converge_info fields of the last check
+//                                                         and the iterations run, the floats as hex bit patterns; FILE.pfm ("Pf") receives the
+//                                                         last check's error per pixel (-1: unknown); not with --ranks
 //                [--builder sbvh|lbvh [--leaf L]]         lbvh: before the frames (after --vertices) the tree is rebuilt on the GPU from the resident
 //                                                         vertices (Renderer::rebuildScene: Scene::rebuildOnDevice + bind), leaves of at most L
 //                                                         triangles (default 4); one JSON line with the build info; not with --ranks.
@@ -98,6 +105,24 @@ std::vector<float> readFloats(const std::string& path)   // a raw float32 file
 	std::fclose(f);
 	return v;
 }
+// one float per pixel as a "Pf" PFM: little-endian, bottom row first
+void writePlanePfm(const std::string& path, const std::vector<float>& plane, unsigned w, unsigned h)
+{
+	std::FILE* f = std::fopen(path.c_str(), "wb");
+	if (!f) throw std::runtime_error("Failed to write " + path);
+	std::fprintf(f, "Pf\n%u %u\n-1.0\n", w, h);
+	for (unsigned y = h; y-- > 0;) std::fwrite(&plane[static_cast<size_t>(y) * w], sizeof(float), w, f);
+	std::fclose(f);
+}
+// the gmupt_converge_info fields of the last check and the iterations run as one JSON line; the floats as hex bit patterns (ms as a decimal)
+void printConverge(unsigned iterations, const gmupt_converge_info& c)
+{
+	auto bits = [](double d) { unsigned long long u; std::memcpy(&u, &d, sizeof(u)); return u; };
+	unsigned m; std::memcpy(&m, &c.max_error, sizeof(m));
+	std::printf("{\"converge\": {\"iterations\": %u, \"converged\": %u, \"pixels\": %u, \"unsampled\": %u, \"known\": %u, \"nonfinite\": %u, \"below\": %u, "
+	            "\"max_error\": \"%08x\", \"sum_error\": \"%016llx\", \"mean_error\": \"%016llx\", \"ms\": %.6g}}\n",
+	            iterations, c.converged, c.pixels, c.unsampled, c.known, c.nonfinite, c.below, m, bits(c.sum_error), bits(c.mean_error), c.ms);
+}
 // the gmupt_tree_cost_info fields as one JSON line; the doubles as the hex bit patterns of their binary64 values (ms as a decimal: it is a time)
 void printTreeCost(const char* when, const gmupt_tree_cost_info& c)
 {
@@ -126,6 +151,7 @@ int main(int argc, char** argv)
 	bool infill = false;
 	std::string builder = "sbvh", dumpTree; unsigned leaf = 4, optimize = 0;
 	bool treeCost = false;
+	bool untilError = false, checkEveryGiven = false, allowPixelsGiven = false; float untilThreshold = 0.f; unsigned checkEvery = 8, allowPixels = 0; std::string errorMap;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
 		auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -161,6 +187,10 @@ int main(int argc, char** argv)
 		else if (a == "--optimize") { char* end = nullptr; const char* v = next(); optimize = std::strtoul(v, &end, 10); if (end == v || *end || optimize > 8) { std::fprintf(stderr, "--optimize takes a number of passes in 0..8\n"); return 2; } }
 		else if (a == "--dump-tree") dumpTree = next();
 		else if (a == "--tree-cost") treeCost = true;
+		else if (a == "--until-error") { char* end = nullptr; const char* v = next(); untilThreshold = std::strtof(v, &end); untilError = true; if (end == v || *end || untilThreshold != untilThreshold || untilThreshold < 0.f) { std::fprintf(stderr, "--until-error takes a threshold >= 0\n"); return 2; } }
+		else if (a == "--check-every") { char* end = nullptr; const char* v = next(); checkEvery = std::strtoul(v, &end, 10); checkEveryGiven = true; if (end == v || *end || checkEvery < 1) { std::fprintf(stderr, "--check-every takes a number of frames >= 1\n"); return 2; } }
+		else if (a == "--allow-pixels") { char* end = nullptr; const char* v = next(); allowPixels = std::strtoul(v, &end, 10); allowPixelsGiven = true; if (end == v || *end) { std::fprintf(stderr, "--allow-pixels takes a number of pixels\n"); return 2; } }
+		else if (a == "--error-map") errorMap = next();
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -177,6 +207,10 @@ int main(int argc, char** argv)
 			            "                                 weight per morph target), then refitted; --smooth-normals and --temporal as with --vertices; not with --vertices or --ranks\n"
 			            "             [--tree-cost]       the surface-area cost of the bound tree, measured on the GPU, after bind and again after --vertices is applied:\n"
 			            "                                 one JSON line each, the doubles as hex bit patterns; not with --ranks\n"
+			            "             [--until-error T [--check-every N] [--allow-pixels M] [--error-map FILE.pfm]]   the frames run until the image is done: every N frames\n"
+			            "                                 (default 8) the per-pixel standard error of the tone-mapped luminance mean is estimated; ends when all but M pixels\n"
+			            "                                 (default 0) are at or below T, or after --frames; one JSON line with the last check's info and the iterations run,\n"
+			            "                                 floats as hex bit patterns; FILE.pfm (Pf): the error per pixel, -1 = unknown; not with --ranks\n"
 			            "             [--builder sbvh|lbvh [--leaf L]]   lbvh: the tree rebuilt on the GPU before the frames (linear BVH, leaves of at most L triangles,\n"
 			            "                                 default 4), one JSON line with the build info; not with --ranks.  With --build-only: the host reference of that build\n"
 			            "             [--optimize N]      with --builder lbvh: N = 1..8 passes of the treelet optimiser on the new tree before it is bound (0, the\n"
@@ -277,6 +311,10 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--pose moves the geometry of a single process: it cannot be combined with --ranks N > 1");
 		if (smoothNormals && verticesFile.empty() && poseFile.empty())
 			throw std::invalid_argument("--smooth-normals recomputes the normals of moved vertices: it needs --vertices FILE or --rig FILE --pose FILE");
+		if (!untilError && (checkEveryGiven || allowPixelsGiven || !errorMap.empty()))
+			throw std::invalid_argument("--check-every, --allow-pixels and --error-map belong to the convergence loop: they need --until-error T");
+		if (untilError && ranks > 1)
+			throw std::invalid_argument("--until-error judges the frame of a single process: it cannot be combined with --ranks N > 1");
 		if (treeCost && ranks > 1)
 			throw std::invalid_argument("--tree-cost measures the tree of a single process: it cannot be combined with --ranks N > 1");
 		if (optimize && builder != "lbvh")
@@ -342,7 +380,27 @@ int main(int argc, char** argv)
 				std::printf("{\"optimize\": {\"passes\": %u, \"num_nodes\": %u, \"depth_before\": %u, \"depth_after\": %u, \"treelets_rewritten\": %u, \"cost_before\": %.17g, \"cost_after\": %.17g, \"ms\": %.6g}}\n",
 				            optimize, oinfo.num_nodes, oinfo.depth_before, oinfo.depth_after, oinfo.treelets_rewritten, oinfo.cost_before, oinfo.cost_after, oinfo.ms);
 		}
-		for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
+		if (untilError) {
+			gmupt_converge_params cp; gmupt_converge_default_params(&cp);
+			cp.threshold = untilThreshold; cp.allow_pixels = allowPixels;
+			const size_t pixels = static_cast<size_t>(w) * h;
+			struct DeviceFree { void operator()(float* p) const { (void)hipFree(p); } };
+			std::unique_ptr<float, DeviceFree> deviceError;   // the error plane on the device, freed on every way out
+			if (!errorMap.empty()) {
+				void* mem = nullptr;
+				if (hipMalloc(&mem, pixels * sizeof(float)) != hipSuccess) throw std::runtime_error("cannot allocate the error plane");
+				deviceError.reset(static_cast<float*>(mem));
+			}
+			unsigned ran = 0;
+			const gmupt_converge_info ci = renderer.renderUntil(&cp, checkEvery, frames, deviceError.get(), &ran);
+			printConverge(ran, ci);
+			if (deviceError) {
+				std::vector<float> plane(pixels, -1.0f);   // no check ran: every pixel unknown
+				if (ci.pixels && hipMemcpy(plane.data(), deviceError.get(), pixels * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("cannot read the error plane");
+				writePlanePfm(errorMap, plane, w, h);
+			}
+		}
+		else for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
 		if (capture) { renderer.requestCapture(); renderer.update(0.f); std::printf("capture %s\n", renderer.lastCapturePath().c_str()); }
 		if (doPick) {
 			const Renderer::Pick pk = renderer.pick(pickX, pickY);

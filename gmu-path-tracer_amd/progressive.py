@@ -29,6 +29,7 @@ class ProgressiveSession:
         self.frames = 0
         self.previews = 0
         self.temporal = None   # the history handle of denoised_temporal, created on first use
+        self.converge = None   # the convergence monitor of run_until, created on first use
         self.motion = bool(motion)   # denoised_temporal goes through the motion entry point (also set by set_vertices(keep_history=True))
         self.lbvh = None       # the GPU tree builder of rebuild(), created on first use
         self._indices = None   # the index list of the last rebuild()
@@ -46,6 +47,7 @@ class ProgressiveSession:
         self.camera.reset_accumulation()
         if self.temporal is not None:
             self.temporal.reset()                    # the history was lit by the old lights
+        self._reset_converge()
 
     def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False, indices=None, rebuild_above=None, optimize=0):
         """The geometry moved (same vertex count, same triangles): upload the vertices, and `normals` (when given) into the property
@@ -136,6 +138,7 @@ class ProgressiveSession:
             self.motion = True
         elif not keep_history and self.temporal is not None:
             self.temporal.reset()
+        self._reset_converge()                       # the batches seen so far are of the old geometry
         if rebuild_above is None:
             return info
         cost = self.renderer.tree_cost()["sah"]                  # on the renderer's stream, behind the refit
@@ -186,6 +189,7 @@ class ProgressiveSession:
         self.camera.reset_accumulation()
         if self.temporal is not None:
             self.temporal.reset()
+        self._reset_converge()
 
     def rebuild(self, scene_buffers, verts=None, indices=None, vertex_material=None, max_leaf_size=4, optimize=0):
         """The geometry changed beyond what a refit covers -- vertices that moved far, or another triangle list (a cut, a spawn, an LOD
@@ -204,9 +208,15 @@ class ProgressiveSession:
         self.baseline = None                         # of the tree that is gone
         return info
 
+    def _reset_converge(self):
+        if self.converge is not None:
+            self.converge.reset()
+
     def close(self):
-        """Releases what the session itself created: the tree builder of rebuild(), the Normals of set_vertices(normals="smooth") and the
-        history handle of denoised_temporal()."""
+        """Releases what the session itself created: the tree builder of rebuild(), the Normals of set_vertices(normals="smooth"), the
+        history handle of denoised_temporal() and the convergence monitor of run_until()."""
+        if self.converge is not None:
+            self.converge.close(); self.converge = None
         if self.normals is not None:
             self.normals.close(); self.normals = None
         if self.lbvh is not None:
@@ -219,6 +229,7 @@ class ProgressiveSession:
         self.width, self.height = width, height
         self.renderer.resize(width, rows if rows is not None else height)
         self.camera.update_resolution(width, height)
+        self._reset_converge()
 
     def pick(self, px, py):
         """What lies under whole-frame pixel (px, py) for the GUI's light / material editor: the un-jittered primary ray of the current
@@ -280,6 +291,42 @@ class ProgressiveSession:
             out = self.frame(dt)
             last = out if out is not None else last
         return last
+
+    def run_until(self, threshold, check_every=8, max_frames=4096, min_batches=2, allow_pixels=0, dt=0.0):
+        """Frames until the image is done: after every `check_every` frames the session's convergence monitor (capi.Converge,
+        include/gmupt.h "Convergence", created on first use and kept until close()) estimates the standard error of every pixel's
+        tone-mapped luminance mean, and the loop ends at the first check at which all but `allow_pixels` pixels have seen
+        `min_batches` batches and lie at or below `threshold` (display units: 1 / 255 is one 8-bit step) -- or after max_frames.
+        Returns the last check's info dict with "frames", the frames this call ran, added (no check ran: only "frames" and
+        converged = False).  Light, geometry and resolution events reset the monitor as they reset the temporal history.
+        With dist and world > 1 every rank judges its own tile, and the ranks agree through one all_reduce (MAX of "not converged")
+        per check, so that all of them leave in the same frame: a rank that stopped alone would hang the next tile gather.  The
+        returned `converged` is the agreed one; the other fields are this rank's.
+        The monitor comes from renderer.converge() (capi.Renderer has it; a stand-in returns anything with update(**params), reset()
+        and close())."""
+        if check_every < 1:
+            raise ValueError("run_until: check_every=%r (at least 1)" % (check_every,))
+        if self.converge is None:
+            self.converge = self.renderer.converge()
+        info = {"converged": False}
+        ran = 0
+        while ran < max_frames:
+            self.frame(dt)
+            ran += 1
+            if ran % check_every:
+                continue
+            info = dict(self.converge.update(threshold=threshold, min_batches=min_batches, allow_pixels=allow_pixels))
+            if self.dist is not None and self.world > 1:
+                import torch
+                flag = torch.tensor([0 if info["converged"] else 1], dtype=torch.int32)
+                if self.dist.get_backend() == "nccl":
+                    flag = flag.cuda()
+                self.dist.all_reduce(flag, op=self.dist.ReduceOp.MAX)
+                info["converged"] = int(flag.item()) == 0
+            if info["converged"]:
+                break
+        info["frames"] = ran
+        return info
 
     def preview(self):
         """Gathers the tiles; rank 0 gets the assembled float frame (and calls on_preview), the other ranks None."""

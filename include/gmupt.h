@@ -945,6 +945,99 @@ int gmupt_pose_update(gmupt_pose* p, const float* joint_mats, const float* targe
 int gmupt_pose_update_device(gmupt_pose* p, const float* device_joint_mats, const float* device_target_weights, gmupt_pose_info* info /* may be NULL */);
 void gmupt_pose_destroy(gmupt_pose* p);
 
+/* ---- Convergence: a per-pixel error estimate of the accumulation and a stop rule built on it (an extension; the reference's Window::loop
+ * renders until the window closes).  The accumulation keeps a running mean and a sample count per pixel and no second moment, and the
+ * monitor does not change that: from two read-outs of a pixel the samples that arrived between them can be recovered -- n1*mean1 -
+ * n0*mean0 is their sum -- so a sequence of read-outs gives BATCH MEANS.  Their weighted spread estimates the per-sample variance, and
+ * with it the standard error of the pixel's mean.  Opt-in everywhere: no kernel of the renderer is changed or reads the monitor.
+ *
+ * The rule (gmupt_converge_host and the kernels run the same statements, csrc/pt_converge.hpp).  All arithmetic is IEEE, nothing
+ * contracted, binary64 except where marked.
+ *   State of a pixel: gmupt_converge_pixel, 40 bytes; all zero is the initial state.  n = the count at the last update that saw new
+ *     samples, k = batches seen, w = samples in them, s = n * luminance then, mean / m2 = weighted mean of the batch means and the
+ *     weighted sum of their squared deviations.
+ *   Update of one pixel from its RGBA32F value (r, g, b, a):
+ *     1. n1 = bits(a).  y = (0.2126f*r + 0.7152f*g) + 0.0722f*b in binary32: the denoiser's luminance.
+ *     2. n1 < n: the accumulation restarted.  The state becomes all zero; continue.
+ *     3. bsz = n1 - n.  bsz == 0: the state is unchanged.
+ *     4. Otherwise, in this order:  s1 = (double)n1 * (double)y;  t = s1 - s;  B = t / (double)bsz;  w1 = w + bsz;  d = B - mean;
+ *        mean1 = mean + ((double)bsz / (double)w1) * d;  m2 = m2 + ((double)bsz * d) * (B - mean1);
+ *        then mean = mean1, s = s1, n = n1, w = w1, k = k + 1.
+ *     5. Error.  k < 2: err = -1.0f, "unknown".  Otherwise v = (m2 / (double)(k - 1)) / (double)w;  if (v < 0) v = 0 (a NaN stays a
+ *        NaN);  err = sqrtf((float)v), the correctly rounded binary32 root.  The sign and payload of a NaN -- in s, mean, m2 or err -- are
+ *        not part of the rule.
+ *   Summary (gmupt_converge_info) under gmupt_converge_params { threshold, min_batches >= 2, allow_pixels }:
+ *     pixels      the pixels of the image
+ *     unsampled   pixels with n1 == 0
+ *     known       pixels with k >= 2 after the update
+ *     nonfinite   known pixels whose err is NaN or inf
+ *     below       pixels with k >= min_batches, err finite and err <= threshold
+ *     max_error   the largest finite err of a known pixel; 0 when there is none
+ *     sum_error   the binary64 sum of the finite err values of the known pixels in pixel order, every other pixel contributing +0.0.
+ *                 Order of the sum: the one "Tree cost" states -- the entries padded with +0.0 to a multiple of 256, every run of 256
+ *                 reduced by stride halving (s = 128 .. 1: x[i] = x[i] + x[i+s] for i < s), the results in run order being the entries
+ *                 of the next level, until one value is left.
+ *     mean_error  sum_error / (known - nonfinite); 0 when that count is 0
+ *     converged   1 when pixels - below <= allow_pixels, else 0
+ *     ms          device time of the launches (hipEvents); 0 from gmupt_converge_host
+ *   Defaults (gmupt_converge_default_params): threshold = 0, min_batches = 2, allow_pixels = 0 -- with these a call only reports;
+ *     there is no default threshold.
+ *   Meaning.  err estimates the standard error of the mean of the pixel's tone-mapped, gamma-encoded luminance -- the samples are
+ *     tone-mapped before they are averaged (logic.hlsl:49-73), so a threshold is in display units ("below one 8-bit step" = 1/255) --
+ *     and nothing more: not the error of the radiance, not the bias of a clamped sample, not what a denoiser leaves.  A pixel whose
+ *     batches were all equal has err == 0; unsampled pixels never become known and so never count as below.
+ *   Noise floor.  The target holds the mean in binary32, so n1*y carries a relative error of about 2^-24 of the SUM; a batch mean
+ *     recovered from two such sums is off by about (n / bsz) * 2^-24 relative.  Short batches late in a long accumulation measure that
+ *     rounding, not the renderer: keep bsz a fixed fraction of n (check less often as the count grows) when thresholds near 1e-5 matter.
+ *   Missed restart.  A restart followed by re-accumulation PAST the old count between two updates cannot be told from the counts
+ *     alone (n1 >= n).  gmupt_converge_update does not rely on the counts for it, see below; gmupt_converge_update_image and
+ *     gmupt_converge_host have step 2 only, and their caller calls gmupt_converge_reset (or zeroes the state) after such a restart.
+ * gmupt_converge_host: the rule on host arrays, no device: state = width*height records the call updates, rgba = as many RGBA32F
+ *   texels, error_or_null = as many floats.  ms = 0.
+ * gmupt_converge: a handle of a renderer: it uses the renderer's device and stream and must not outlive the renderer.  The state is
+ *   a structure of arrays in device memory (36 bytes per pixel) together with the partial summaries (32 bytes per 256 pixels),
+ *   allocated zeroed by the first update and again when the image size changes.
+ * gmupt_converge_update: the rule on the renderer's accumulation target (the tile of a tile renderer), on the renderer's stream behind
+ *   pending gmupt_iterate work and without a host wait before the launches: one thread per pixel, one block per run (k_cv_update), then
+ *   one launch per further level over the partial summaries (k_cv_reduce); no atomics.  Then ONE readback of 32 bytes and a
+ *   synchronise.  Every pixel restarts (the state is zeroed on the stream first) when the renderer's accumulation generation -- advanced
+ *   by an iteration that clears the frame and by gmupt_resize -- differs from the one the previous gmupt_converge_update saw, when the
+ *   frame size changed, and on the first gmupt_converge_update after a gmupt_converge_update_image.  device_error_or_null: width*height
+ *   floats of device memory, 4-byte aligned, that receive err per pixel.
+ * gmupt_converge_update_image: the same on caller-owned device memory (16-byte aligned, finished by the caller), e.g. a gathered frame
+ *   or a torch tensor; 1 <= width*height < 2^32.  Restarts are step 2's and a changed image size only: called after a
+ *   gmupt_converge_update of the same size it CONTINUES the state of the renderer's target.  Do not feed one handle from both sources
+ *   without a gmupt_converge_reset in between, or use a handle per source.
+ * gmupt_converge_reset: zeroes the state on the stream.  gmupt_converge_read_state: the state as width*height 40-byte records (pad = 0)
+ *   for tests; 0 records before the first update; synchronises.
+ * gmupt_render_until: the loop of gmupt_render_budget (camera update, upload, iterate) with gmupt_converge_update after every
+ *   check_every iterations; ends when a check reports converged, after max_iterations (the last iteration is followed by a check
+ *   only when it completes a group of check_every), or on an error; GMUPT_ERR_CAST_FAULT is checked at every check and at the end.
+ *   *iters = iterations run.  *info = the last check's summary; it is written only when a check ran.  A path_budget is not needed.
+ * Errors: GMUPT_ERR_INVALID_ARGUMENT for a NULL handle, info, state or image, min_batches < 2, a NaN threshold, a misaligned device
+ *   pointer, an empty or too large image, bytes too small, check_every == 0.  No error path allocates anything or writes *info.  The
+ *   frame, path state, queues, counters, statistics and traversal tables are never written. */
+typedef struct { uint32_t n, k, w, pad; double s, mean, m2; } gmupt_converge_pixel;   /* 40 bytes */
+typedef struct { float threshold; uint32_t min_batches, allow_pixels; } gmupt_converge_params;   /* 12 bytes */
+typedef struct {
+    uint32_t pixels, unsampled, known, nonfinite, below, converged;
+    float max_error; uint32_t pad;
+    double sum_error, mean_error, ms;
+} gmupt_converge_info;   /* 56 bytes */
+void gmupt_converge_default_params(gmupt_converge_params* p);
+int gmupt_converge_host(gmupt_converge_pixel* state, const float* rgba, uint32_t width, uint32_t height, const gmupt_converge_params* params /* may be NULL */,
+                        float* error_or_null, gmupt_converge_info* info);
+typedef struct gmupt_converge gmupt_converge;
+int gmupt_converge_create(gmupt_renderer* r, gmupt_converge** out);
+void gmupt_converge_destroy(gmupt_converge* c);
+int gmupt_converge_reset(gmupt_converge* c);
+int gmupt_converge_update(gmupt_converge* c, const gmupt_converge_params* params /* may be NULL */, float* device_error_or_null, gmupt_converge_info* info);
+int gmupt_converge_update_image(gmupt_converge* c, const float* device_rgba, uint32_t width, uint32_t height, const gmupt_converge_params* params /* may be NULL */,
+                                float* device_error_or_null, gmupt_converge_info* info);
+int gmupt_converge_read_state(gmupt_converge* c, gmupt_converge_pixel* dst, size_t bytes);
+int gmupt_render_until(gmupt_renderer* r, gmupt_camera* camera, gmupt_converge* c, const gmupt_converge_params* params /* may be NULL */,
+                       uint32_t check_every, uint32_t max_iterations, uint32_t* iters /* may be NULL */, gmupt_converge_info* info);
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);

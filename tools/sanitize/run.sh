@@ -22,4 +22,7 @@ ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_treecost_asan"
 # the host treelet optimiser (csrc/pt_treeopt.cpp), the same way
 "$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_treeopt_asan" treeopt_main.cpp ../../gmu-path-tracer_amd/csrc/pt_treeopt.cpp
 ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_treeopt_asan"
+# the host convergence rule (csrc/pt_converge.cpp), the same way
+"$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_converge_asan" converge_main.cpp ../../gmu-path-tracer_amd/csrc/pt_converge.cpp
+ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_converge_asan"
 echo "sanitizers: clean"
