@@ -1,5 +1,7 @@
 """gmupt_converge_host, the reference of the device convergence monitor (include/gmupt.h "Convergence"), against the independent numpy
-restatement of the rule in converge_util.py -- state, error plane and info bit for bit over chained updates of crafted frames -- the
+restatement of the rule in converge_util.py -- state, error plane and info bit for bit over chained updates of crafted frames and of
+the wide-range frames, whose preconditions (the order of the sum shows in the bits, the specials and the maximum sit at the seams of the
+reduction) are checked on the restatement alone -- the
 estimator's unbiasedness on synthetic samples, the argument errors, the stop rule at its boundaries, and ProgressiveSession.run_until on
 stand-in renderers, alone and as two gloo ranks.  No device."""
 import ctypes as C
@@ -44,6 +46,130 @@ def test_host_rule_equals_the_restatement_bit_for_bit(pkg, size):
     assert np.isnan(e[5]) and np.isnan(e[6]) and np.isnan(e[7]) and np.isinf(e[8]) and info["nonfinite"] >= 4
     assert got[3][0].reshape(-1)["n"][9] == 0xFFFFFFFF and flat["n"][9] == 12 and flat["k"][9] == 1
     assert (e[flat["k"] < 2] == -1.0).all() and info["known"] == int((flat["k"] >= 2).sum())
+
+
+_SEAM_IDS = dict(ids=lambda s: "%dx%d" % s if isinstance(s, tuple) else s)
+
+
+@pytest.fixture(scope="module")
+def restated(pkg):
+    """(size, variant) -> (frames, [(state copy, error plane, info)] per update) of a wide-range sequence by the numpy restatement."""
+    cache = {}
+
+    def get(size, variant):
+        if (size, variant) not in cache:
+            frames = CU.wide_sequence(size, variant)
+            state = np.zeros((size[1], size[0]), pkg.capi.converge_pixel_dtype)
+            out = []
+            for u, f in enumerate(frames):
+                info, err = CU.rule(state, f, **CU.PARAMS[u % len(CU.PARAMS)])
+                out.append((state.copy(), err, info))
+            cache[(size, variant)] = (frames, out)
+        return cache[(size, variant)]
+    return get
+
+
+def _same_bits(a, b):
+    return bool(CU.bits(np.float64(a)) == CU.bits(np.float64(b)))
+
+
+@pytest.mark.parametrize("variant", CU.VARIANTS)
+@pytest.mark.parametrize("size", CU.SEAM_SIZES, **_SEAM_IDS)
+def test_wide_range_frames_show_the_order_and_the_seams(restated, size, variant):
+    """The preconditions of the host and device comparisons on the wide-range sequences, on the numpy restatement alone, so that those
+    comparisons cannot pass vacuously.  The crafted frames' sum has the same bits in any order; here the rule's sum differs from each
+    order of other_orders() at three or more of the five updates with known pixels, from all of them at once at one update or more.
+    Void for the single pixel (one entry has one order).  "flat_levels" is left out for one run (it is the rule) and for two: the
+    rule's second level pads two partials to a run, and the only addition of that run that is not x + 0.0 is p0 + p1."""
+    W, H = size
+    N = W * H
+    frames, want = restated(size, variant)
+    differs, at_once = {}, 0
+    for u in range(1, CU.UPDATES):
+        _, err, info = want[u]
+        x = CU.error_entries(err)
+        assert info["known"] > info["nonfinite"] or N == 1
+        assert _same_bits(CU.reduce_runs(x), info["sum_error"]), "the entries are those of the sum"
+        others = CU.other_orders(x)
+        assert len(others) == 5
+        if CU._runs(N) <= 2:
+            del others["flat_levels"]
+        d = {name: not _same_bits(v, info["sum_error"]) for name, v in others.items()}
+        for name, v in d.items():
+            differs[name] = differs.get(name, 0) + int(v)
+        at_once += all(d.values())
+    print(size, variant, differs, at_once)
+    if N == 1:
+        assert not any(differs.values())
+    else:
+        assert min(differs.values()) >= 3 and at_once >= 1, (differs, at_once)
+    # the special pixels are where placed_specials() says; no ordinary pixel is non-finite
+    kinds = CU.special_kinds(N)
+    assert sorted(kinds) == CU.placed_specials(N).tolist() and set(kinds.values()) <= set(CU.KINDS)
+    carriers = CU.carrier_pixels(N, CU.WIDE_SEQUENCES[size][2]) if variant == "carrier" else []
+    state, err, info = want[-1]
+    flat, e = state.reshape(-1), err.reshape(-1)
+    nonfinite = np.flatnonzero((flat["k"] >= 2) & ~np.isfinite(e))
+    assert info["nonfinite"] == len(nonfinite) and set(nonfinite.tolist()) <= set(kinds) | set(carriers)
+    if variant == "specials":
+        assert nonfinite.tolist() == sorted(p for p, kind in kinds.items() if kind in CU.NONFINITE_KINDS)
+        if N >= 255:
+            # the nine places of one run hold all seven kinds, six pixels of them non-finite; three runs or more are placed from 1 273 pixels on
+            assert set(kinds.values()) == set(CU.KINDS) and info["nonfinite"] >= 6 and (info["nonfinite"] > 8 or N <= 257)
+            assert {63, 64, 127, 128} <= set(nonfinite.tolist()), "both sides of the strides that go through LDS"
+            assert (N - 1) in kinds and (CU._runs(N) - 1) * 256 in kinds
+        if CU._runs(N) > 256:
+            assert {255 * 256 + 255, 256 * 256} <= set(nonfinite.tolist()), "the last entry of a run of the second level, the first of the next"
+        for p, kind in kinds.items():
+            if kind == "zero":   # 5, 9, 0, 0, 4, 8
+                for u in (2, 3):
+                    assert CU.bits(frames[u].reshape(-1, 4)[p, 3]) == 0, "counted as unsampled"
+                    assert not want[u][0].reshape(-1)[p:p + 1].view(np.uint8).any() and want[u][1].reshape(-1)[p] == -1.0
+                assert (flat["n"][p], flat["k"][p], flat["w"][p]) == (8, 2, 8) and e[p] >= 0, "it recovers"
+            if kind == "denormal":
+                rgb = frames[-1].reshape(-1, 4)[p, :3]
+                assert (rgb != 0).all() and (np.abs(rgb) < np.float32(2.0 ** -126)).all() and flat["s"][p] != 0 and e[p] == 0
+            if kind == "count":
+                assert want[3][0].reshape(-1)["n"][p] == 0xFFFFFFFF and (flat["n"][p], flat["k"][p]) == (12, 1)
+    else:
+        # max_error is held by one pixel, the carrier of the update
+        for u in range(1, CU.UPDATES):
+            _, err_u, info_u = want[u]
+            eu = err_u.reshape(-1)
+            finite = np.isfinite(eu) & (eu != -1.0)
+            top = eu[finite].max()
+            assert np.flatnonzero(finite & (eu == top)).tolist() == [carriers[u]], (u, carriers)
+            assert np.float32(info_u["max_error"]) == top and top >= np.float32(2.0 ** 20)
+        assert len(set(carriers)) == (1 if N == 1 else CU.UPDATES)
+
+
+def test_every_carrier_place_occurs(pkg):
+    """Over the seam sizes the maximum travels from each of the eight places, at an update with known pixels."""
+    seen = set()
+    for size in CU.SEAM_SIZES:
+        n = size[0] * size[1]
+        if n > 1:
+            held = CU.carrier_pixels(n, CU.WIDE_SEQUENCES[size][2])[1:]
+            seen |= {j for j, p in enumerate(CU.carrier_places(n, raw=True)) if p in held}
+    assert seen == set(range(CU.CARRIER_PLACES))
+    assert CU.carrier_places(66049, raw=True) == [0, 63 * 257, 64 * 257, 127 * 257, 128 * 257, 255 * 257, 66048, 66048]
+    assert CU.carrier_places(1273) == [256, 319, 320, 383, 384, 511, 1024, 1272] and CU.carrier_places(255) == [0, 63, 64, 127, 128, 254]
+    assert CU.placed_specials(257).tolist() == [0, 31, 32, 63, 64, 127, 128, 191, 255, 256] and CU.placed_specials(1).tolist() == [0]
+    assert CU.special_runs(66049) == [0, 129, 255, 256, 258] and CU.special_runs(65536) == [0, 128, 255]
+
+
+@pytest.mark.parametrize("variant", CU.VARIANTS)
+@pytest.mark.parametrize("size", CU.SEAM_SIZES, **_SEAM_IDS)
+def test_host_rule_equals_the_restatement_on_wide_range_frames(pkg, restated, size, variant):
+    """As test_host_rule_equals_the_restatement_bit_for_bit, on frames on which a host reference that summed in another order fails."""
+    frames, want = restated(size, variant)
+    got = CU.host_chain(pkg.capi, frames)
+    for u in range(CU.UPDATES):
+        state, err, info = got[u]
+        want_state, want_err, want_info = want[u]
+        bad = CU.differing(state, err, info, want_state, want_err, want_info, fence=True)
+        assert not bad, (size, variant, u, bad, info, want_info)
+        assert info["ms"] == 0.0
 
 
 def test_the_estimate_is_unbiased(pkg):

@@ -1,6 +1,7 @@
 """GPU tests of the convergence monitor (gmupt_converge_*, csrc/pt_converge.hip): the device against its host reference
 gmupt_converge_host bit for bit -- on the crafted frame sequences of the CPU test, written into the accumulation target and given as
-torch tensors, and on real renders with both shipped ray casts --, restart detection, the renderer left untouched, and the loops that
+torch tensors, on the wide-range sequences that show the order of the sum and the seams of the reduction (one run, 256 partials, a
+second level of one entry, four levels), and on real renders with both shipped ray casts --, restart detection, the renderer left untouched, and the loops that
 stop on the estimate (gmupt_render_until, ProgressiveSession.run_until).  A word that is NaN on the host may be any NaN on the device,
 fenced per field to the same words (the shade_util.compare convention)."""
 import ctypes as C
@@ -79,6 +80,107 @@ def test_device_equals_host_on_crafted_frames(pkg, device, chains, size):
     assert not a.state().view(np.uint8).any()
     info = a.update()
     assert info["known"] == 0 and (a.state()["k"] <= 1).all()
+    r.close()
+
+
+@pytest.mark.parametrize("variant", CU.VARIANTS)
+@pytest.mark.parametrize("size", CU.SEAM_SIZES, ids=lambda s: "%dx%d" % s)
+def test_device_equals_host_at_the_seams(pkg, device, size, variant):
+    """The wide-range sequences (converge_util.py): the errors span 40 binades, so a sum in another order than the rule's -- atomics,
+    wave first, neighbours first -- has other bits; the special pixels sit on both sides of every stride of the block reduction in
+    the first, a middle and the last run and around the seam of the second level; in the "carrier" variant max_error is held by one
+    pixel at such a place, another one at every update.  test_converge_cpu.py checks on the numpy restatement that the frames do show
+    all this, and the host reference against the restatement on the same frames."""
+    W, H = size
+    frames = CU.wide_sequence(size, variant)
+    want = CU.host_chain(pkg.capi, frames)
+    r = pkg.capi.Renderer(device, 8, 8, pool_paths=1024)
+    c = pkg.capi.Converge(r)
+    for u, f in enumerate(frames):
+        prm = CU.PARAMS[u % len(CU.PARAMS)]
+        t = torch.from_numpy(f).cuda()
+        if u % 2:
+            info, err = c.update_image(t, error=True, **prm)
+            err = err.cpu().numpy()
+        else:
+            info, err = c.update_image(t, **prm), want[u][1]
+        check(c.state(), err, info, want[u], "%s %dx%d update %d" % (variant, W, H, u))
+    assert info["pixels"] == W * H and (W * H == 1 or info["known"] > info["nonfinite"] > 0)
+    r.close()
+
+
+def test_four_levels_equal_host(pkg, device):
+    """4097 x 4096 = 16 781 312 pixels = 256^3 + 4 096: 65 552 partials, then 257, then 2, then 1 -- the smallest frames with a fourth
+    level are just above 256^3 pixels, and an 8K frame (33 M) has one.  Two successive read-outs of the 257 x 257 wide-range sequence,
+    tiled and cropped; the special pixels of a run of that sequence are copied to the last run (65 551: entry 15 of the last run of the
+    second level, entry 0 of the last run of the third) and to runs 65 535 and 65 536 (the two sides of the seam of the second AND of
+    the third level); the pixel before the last one holds the largest error.  Device against gmupt_converge_host; the numpy restatement
+    is not run at this size."""
+    import time
+    t0 = time.time()
+    W, H = 4097, 4096
+    N = W * H
+    tile = CU.wide_sequence((257, 257), "specials")[1:3]     # update 1 -> 2: the NaN and inf colours, 0xFFFFFFFE and the drop to 0 arrive
+    source = CU.run_places(257 * 257, 0)
+    frames = []
+    for v, f in enumerate(tile):
+        big = np.ascontiguousarray(np.tile(f, (16, 16, 1))[:H, :W])
+        flat = big.reshape(-1, 4)
+        for shift, run in ((0, 65535), (3, 65536), (6, 65551)):
+            assert (run + 1) * 256 <= N
+            for q, p in enumerate(CU.run_places(N, run)):
+                flat[p] = f.reshape(-1, 4)[source[(q + shift) % len(source)]]
+        flat[N - 2, :3] = np.array((0.25, 0.5, 0.75) if v else (0.75, 0.5, 0.25), np.float32) * np.float32(2.0 ** 44)
+        flat[N - 2, 3:] = np.array([3 * (v + 1)], np.uint32).view(np.float32)
+        frames.append(big)
+    state = np.zeros((H, W), pkg.capi.converge_pixel_dtype)
+    r = pkg.capi.Renderer(device, 8, 8, pool_paths=1024)
+    c = pkg.capi.Converge(r)
+    t1 = time.time()
+    for v, f in enumerate(frames):
+        prm = CU.PARAMS[1 + v]
+        want_info, want_err = pkg.capi.converge_host(state, f, error=True, **prm)
+        t = torch.from_numpy(f).cuda()
+        if v:
+            info, err = c.update_image(t, error=True, **prm)
+            err = err.cpu().numpy()
+        else:
+            info, err = c.update_image(t, **prm), want_err
+        del t
+        bad = CU.differing(c.state() if v else state, err, info, state, want_err, want_info, fence=True)   # the state once, after both updates
+        print("four levels, update %d: known %d nonfinite %d max %.6g sum %.17g ms %.4f" % (v, info["known"], info["nonfinite"], info["max_error"],
+                                                                                      info["sum_error"], info["ms"]))
+        assert not bad, (v, bad, info, want_info)
+    e = want_err.reshape(-1)
+    finite = np.isfinite(e) & (e != -1.0)
+    assert info["pixels"] == 16781312 and info["known"] > 0
+    assert int(np.argmax(np.where(finite, e, -1.0))) == N - 2 and int((e == e[N - 2]).sum()) == 1 and info["max_error"] == e[N - 2]
+    assert not np.isfinite(e[[65535 * 256 + 255, 65536 * 256, N - 1]]).any() and info["nonfinite"] > 8
+    print("four levels: %.2f s building the frames, %.2f s host rule, device and comparison" % (t1 - t0, time.time() - t1))
+    r.close()
+
+
+def test_a_count_that_drops_to_zero_through_the_target(pkg, device):
+    """Counts 5, 9, 0, 0, 4, 8 through gmupt_debug_write_framebuffer + gmupt_converge_update: at the drop the pixel restarts and has no
+    new samples (bsz == 0), and its zeroed state must still be stored although nothing was folded in."""
+    pixels = [0, 20, 63]
+    frames = CU.wide_range_frames(8, 8, 3, kinds={p: "zero" for p in pixels})
+    want = CU.host_chain(pkg.capi, frames)
+    r = pkg.capi.Renderer(device, 8, 8, pool_paths=1024)
+    c = pkg.capi.Converge(r)
+    for u, f in enumerate(frames):
+        r.write_framebuffer(f)
+        info, err = c.update(error=True, **CU.PARAMS[u % len(CU.PARAMS)])
+        state = c.state()
+        check(state, err.cpu().numpy(), info, want[u], "zero count, update %d" % u)
+        rec = state.reshape(-1)[pixels]
+        if u == 1:
+            assert (rec["n"] == 9).all() and (rec["k"] == 2).all() and (rec["m2"] > 0).all()
+        if u in (2, 3):
+            assert not rec.view(np.uint8).any() and (err.cpu().numpy().reshape(-1)[pixels] == -1.0).all()
+            assert info["unsampled"] == int((np.arange(64) % 11 == 0).sum()) + 2       # pixel 0 never has a sample in the plain frames either
+        if u == 5:
+            assert (rec["n"] == 8).all() and (rec["k"] == 2).all() and (rec["w"] == 8).all()
     r.close()
 
 
