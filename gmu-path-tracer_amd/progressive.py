@@ -5,7 +5,7 @@ A session iterates continuously; between frames it applies the events the refere
 accumulation-reset hysteresis of Camera.cpp:72-83, implemented in the host camera), light edits (buffer re-upload + restart,
 GUI.cpp:125-130), resolution switches (Renderer.cpp:408-413) -- and every `preview_every` frames it gathers the row-band tiles of all
 ranks to rank 0 (tiles.gather_tiles: RCCL over xGMI with the "nccl" backend, gloo in the CPU tests) and hands the frame to a callback.
-The renderer / camera objects are the C-ABI wrappers of capi.py (or anything with the same methods).
+The renderer / camera objects are the C-ABI wrappers of capi (or anything with the same methods).
 """
 import numpy as np
 
