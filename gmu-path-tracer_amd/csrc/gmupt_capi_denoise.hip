@@ -7,9 +7,10 @@ extern "C" int gmupt_denoise_image(gmupt_renderer* r, const float* beauty_rgba, 
     if (ms) *ms = 0.0f;
     if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_denoise_image: null renderer");
     DnParams prm;
-    GMUPT_TRY(denoise_args("gmupt_denoise_image", beauty_rgba, aov, width, height, p, out_rgba, out_bytes, true, prm));
+    GMUPT_TRY(image_args("gmupt_denoise_image", beauty_rgba, aov, width, height, out_rgba, out_bytes, true));
+    GMUPT_TRY(denoise_params("gmupt_denoise_image", p, prm));
     HIP_TRY(hipSetDevice(r->dev->id));
-    GMUPT_TRY(r->dnScratch.grow(r->stream, (size_t)width * height * kDnScratchBytes));
+    GMUPT_TRY(r->dnScratch.grow(r->stream, (size_t)width * height * kGdScratchBytes));
     GMUPT_TRY(r->dnEv.start(r->stream));
     launch_denoise(reinterpret_cast<const float4*>(beauty_rgba), reinterpret_cast<const float4*>(aov), (int)width, (int)height, prm, r->dnScratch.ptr,
                    reinterpret_cast<float4*>(out_rgba), r->stream);
@@ -22,6 +23,22 @@ extern "C" int gmupt_denoise_image(gmupt_renderer* r, const float* beauty_rgba, 
     return GMUPT_OK;
 }
 
+// What the render_denoised* chains check once they have a renderer, in this order: the output, the caller's parameters (`params`, which
+// has called fail() itself), then what gmupt_render_aovs would refuse, before the scratch is grown for it.  Leaves the device set.
+template <class P> static int render_args(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const float* out_rgba, size_t bytes, const P& params)
+{
+    const uint32_t W = r->p.fbW, H = r->p.fbH;
+    if (!out_rgba || ((uintptr_t)out_rgba & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned output (16 bytes)", fn);
+    if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu output bytes for %ux%u RGBA32F texels", fn, bytes, W, H);
+    GMUPT_TRY(params());
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
+    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "%s: no camera set", fn);
+    GMUPT_TRY(aov_sample_plan(fn, "aov_samples", W, aov_samples, nullptr));
+    GMUPT_TRY(query_supported(r, fn));
+    HIP_TRY(hipSetDevice(r->dev->id));
+    return GMUPT_OK;
+}
+
 // gmupt_render_denoised; with `infill` gmupt_render_preview without a history: the infill stage between the framebuffer copy and the filter
 int render_denoised(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, const IfParams* infill, float* out_rgba, size_t bytes,
                     gmupt_trace_info* info)
@@ -29,16 +46,8 @@ int render_denoised(const char* fn, gmupt_renderer* r, uint32_t aov_samples, con
     if (info) std::memset(info, 0, sizeof(*info));
     if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer", fn);
     const uint32_t W = r->p.fbW, H = r->p.fbH;
-    if (!out_rgba || ((uintptr_t)out_rgba & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned output (16 bytes)", fn);
-    if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu output bytes for %ux%u RGBA32F texels", fn, bytes, W, H);
     DnParams prm;
-    GMUPT_TRY(denoise_params(fn, p, prm));
-    // what gmupt_render_aovs would refuse, before the scratch is grown for it
-    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
-    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "%s: no camera set", fn);
-    GMUPT_TRY(aov_sample_plan(fn, "aov_samples", W, aov_samples, nullptr));
-    GMUPT_TRY(query_supported(r, fn));
-    HIP_TRY(hipSetDevice(r->dev->id));
+    GMUPT_TRY(render_args(fn, r, aov_samples, out_rgba, bytes, [&] { return denoise_params(fn, p, prm); }));
     GMUPT_TRY(r->dnInput.grow(r->stream, (size_t)W * H * (sizeof(gmupt_aov) + 16)));
     if (infill) GMUPT_TRY(r->ifImage.grow(r->stream, (size_t)W * H * 16));
     gmupt_aov* aov = r->dnInput.as<gmupt_aov>();
@@ -108,21 +117,18 @@ int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba
                      const gmupt_temporal_params* p, const IfParams* infill, float* out_rgba, size_t out_bytes, float* ms)
 {
     if (ms) *ms = 0.0f;
-    gmupt_temporal_params d;
-    if (!p) { gmupt_temporal_default_params(&d); p = &d; }
     DnParams dn; TpParams tp;
-    int rc = denoise_args(fn, beauty_rgba, aov, width, height, &p->spatial, out_rgba, out_bytes, true, dn);   // needs no device: checked first
-    if (rc == GMUPT_OK) rc = temporal_params(fn, p, dn, tp);
-    if (rc != GMUPT_OK) return rc;
+    GMUPT_TRY(image_args(fn, beauty_rgba, aov, width, height, out_rgba, out_bytes, true));   // needs no device: checked first
+    GMUPT_TRY(temporal_params(fn, p, dn, tp));                                               // the spatial parameters first
     if (!cam) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null camera", fn);
     if (!t) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null handle", fn);
     gmupt_renderer* r = t->r;
     const size_t n = (size_t)width * height;
     HIP_TRY(hipSetDevice(r->dev->id));
     if (new_accumulation) std::swap(t->frozen, t->last);   // the records of the accumulation that ended become the history
-    rc = t->last.rec.grow(r->stream, n * sizeof(gmupt_history));
+    int rc = t->last.rec.grow(r->stream, n * sizeof(gmupt_history));
     if (rc == GMUPT_OK) rc = t->integrated.grow(r->stream, n * 16);
-    if (rc == GMUPT_OK) rc = r->dnScratch.grow(r->stream, n * kDnScratchBytes);
+    if (rc == GMUPT_OK) rc = r->dnScratch.grow(r->stream, n * kGdScratchBytes);
     if (rc == GMUPT_OK && infill) rc = r->ifImage.grow(r->stream, n * 16);
     if (rc != GMUPT_OK) { t->last.present = false; return rc; }
     TpPrev prev{};
@@ -182,16 +188,8 @@ int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* r, gmup
     if (!r || !t) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer or handle", fn);
     if (t->r != r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: the handle belongs to another renderer", fn);
     const uint32_t W = r->p.fbW, H = r->p.fbH;
-    if (!out_rgba || ((uintptr_t)out_rgba & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned output (16 bytes)", fn);
-    if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu output bytes for %ux%u RGBA32F texels", fn, bytes, W, H);
     DnParams dn; TpParams tp;
-    GMUPT_TRY(temporal_params(fn, p, dn, tp));
-    // what gmupt_render_aovs would refuse, before the scratch is grown for it
-    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
-    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "%s: no camera set", fn);
-    GMUPT_TRY(aov_sample_plan(fn, "aov_samples", W, aov_samples, nullptr));
-    GMUPT_TRY(query_supported(r, fn));
-    HIP_TRY(hipSetDevice(r->dev->id));
+    GMUPT_TRY(render_args(fn, r, aov_samples, out_rgba, bytes, [&] { return temporal_params(fn, p, dn, tp); }));
     const bool fold = !t->seen || t->generation != r->accumGeneration;
     // the record sets as they will be once the fold has swapped them: `fz` is integrated against, `nw` receives this call's records
     TpSlot& fz = fold ? t->last : t->frozen;

@@ -72,9 +72,8 @@ int denoise_params(const char* fn, const gmupt_denoise_params* p, DnParams& out)
     return GMUPT_OK;
 }
 
-// the arguments every denoiser entry checks; device pointers must be 16-byte aligned
-int denoise_args(const char* fn, const void* beauty, const void* aov, uint32_t W, uint32_t H, const gmupt_denoise_params* p, const void* out, size_t bytes,
-                 bool device, DnParams& prm)
+// the image arguments every denoiser and infill entry checks; device pointers must be 16-byte aligned
+int image_args(const char* fn, const void* beauty, const void* aov, uint32_t W, uint32_t H, const void* out, size_t bytes, bool device)
 {
     if (!beauty || !aov || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null beauty, aov or output", fn);
     if (device && (((uintptr_t)beauty | (uintptr_t)aov | (uintptr_t)out) & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: misaligned pointer (16 bytes)", fn);
@@ -84,14 +83,15 @@ int denoise_args(const char* fn, const void* beauty, const void* aov, uint32_t W
         if (o0 < b0 + n && b0 < o0 + n) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: the output overlaps the beauty image", fn);
     }
     if (bytes < (size_t)W * H * 16) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu output bytes for %ux%u RGBA32F texels", fn, bytes, W, H);
-    return denoise_params(fn, p, prm);
+    return GMUPT_OK;
 }
 
 extern "C" int gmupt_denoise_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height, const gmupt_denoise_params* p,
                                   float* out_rgba, size_t out_bytes, uint32_t threads)
 {
     DnParams prm;
-    GMUPT_TRY(denoise_args("gmupt_denoise_host", beauty_rgba, aov, width, height, p, out_rgba, out_bytes, false, prm));
+    GMUPT_TRY(image_args("gmupt_denoise_host", beauty_rgba, aov, width, height, out_rgba, out_bytes, false));
+    GMUPT_TRY(denoise_params("gmupt_denoise_host", p, prm));
     try {
         denoise_host(beauty_rgba, aov, (int)width, (int)height, prm, out_rgba, clamp_threads(threads));
     } catch (const std::bad_alloc&) {
@@ -129,8 +129,8 @@ int infill_params(const char* fn, const gmupt_infill_params* p, IfParams& out)
 extern "C" int gmupt_infill_host(const float* beauty_rgba, const gmupt_aov* aov, uint32_t width, uint32_t height, const gmupt_infill_params* p,
                                  float* out_rgba, size_t out_bytes, gmupt_infill_info* info, uint32_t threads)
 {
-    DnParams unused; IfParams prm;
-    GMUPT_TRY(denoise_args("gmupt_infill_host", beauty_rgba, aov, width, height, nullptr, out_rgba, out_bytes, false, unused));   // pointers, size, overlap, bytes
+    IfParams prm;
+    GMUPT_TRY(image_args("gmupt_infill_host", beauty_rgba, aov, width, height, out_rgba, out_bytes, false));
     GMUPT_TRY(infill_params("gmupt_infill_host", p, prm));
     IfCounters c{};
     try {

@@ -13,8 +13,8 @@ extern "C" int gmupt_infill_image(gmupt_renderer* r, const float* beauty_rgba, c
 {
     const char* fn = "gmupt_infill_image";
     if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer", fn);
-    DnParams unused; IfParams prm;
-    GMUPT_TRY(denoise_args(fn, beauty_rgba, aov, width, height, nullptr, out_rgba, out_bytes, true, unused));   // pointers, alignment, size, overlap, bytes
+    IfParams prm;
+    GMUPT_TRY(image_args(fn, beauty_rgba, aov, width, height, out_rgba, out_bytes, true));
     GMUPT_TRY(infill_params(fn, p, prm));
     HIP_TRY(hipSetDevice(r->dev->id));
     if (info) GMUPT_TRY(r->ifEv.start(r->stream));

@@ -120,11 +120,11 @@ struct gmupt_renderer {
     EventPair queryEv;
     // AOV buffers (gmupt_render_aovs): rays and hits of one chunk (GMUPT_AOV_CHUNK_RAYS each, 128 MiB), allocated on first use
     DevMem aovRays, aovHits;
-    // denoiser (gmupt_denoise_image): the filter's scratch (kDnScratchBytes per pixel) and, for gmupt_render_denoised, the AOV records and
+    // denoiser (gmupt_denoise_image): the filter's scratch (kGdScratchBytes per pixel) and, for gmupt_render_denoised, the AOV records and
     // the framebuffer copy (80 bytes per pixel); allocated on first use, grown when a larger image comes
     DevMem dnScratch, dnInput;
     EventPair dnEv;
-    // infill (gmupt_infill_image): the stage's scratch (256 bytes of counters, then kIfScratchBytes per pixel) and, for the chained entry
+    // infill (gmupt_infill_image): the stage's scratch (256 bytes of counters, then kGdScratchBytes per pixel) and, for the chained entry
     // points, the filled image the denoiser reads (16 bytes per pixel); allocated on first use, grown when a larger image comes
     DevMem ifScratch, ifImage;
     EventPair ifEv;
@@ -203,8 +203,7 @@ gmupt_buffer* buffer_alloc(gmupt_device* dev, gmupt_buffer_kind kind, size_t ele
 int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, const gmupt_buffer* trisB, const gmupt_buffer* vertsB);   // gmupt_capi_accel.hip
 int query_supported(gmupt_renderer* r, const char* fn);                                                         // gmupt_capi_query.hip
 int denoise_params(const char* fn, const gmupt_denoise_params* p, DnParams& out);                               // gmupt_capi_host.cpp
-int denoise_args(const char* fn, const void* beauty, const void* aov, uint32_t W, uint32_t H, const gmupt_denoise_params* p, const void* out, size_t bytes,
-                 bool device, DnParams& prm);
+int image_args(const char* fn, const void* beauty, const void* aov, uint32_t W, uint32_t H, const void* out, size_t bytes, bool device);
 int temporal_params(const char* fn, const gmupt_temporal_params* p, DnParams& dn, TpParams& tp);
 int infill_params(const char* fn, const gmupt_infill_params* p, IfParams& out);
 int converge_params(const char* fn, const gmupt_converge_params* p, CvParams& out);

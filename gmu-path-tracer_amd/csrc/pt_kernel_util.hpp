@@ -1,4 +1,4 @@
-// Small device helpers shared by the shading kernels (pt_kernels.hip) and the ray-cast kernels (pt_traverse.hip).
+// Small device helpers shared by the shading kernels (pt_kernels.hip) and the ray-cast kernels (pt_traverse.hip), and the image stages' pixel tile.
 #pragma once
 #include "pt_device.hpp"
 #include "detmath.hpp"
@@ -30,5 +30,16 @@ __device__ __forceinline__ uint32_t pixel_index(const RenderParams& p, uint32_t 
     return ly * p.fbW + lx;
 }
 
+// The pixel tile of the image stages (pt_denoise.hip, pt_infill.hip, pt_temporal.hip): a wave is a row segment of 64 pixels, so every tap
+// load of a wave is contiguous (1 KiB for a float4 plane) and threadIdx.x is the lane; four rows to a block
+constexpr int kTileX = 64, kTileY = 4;
+struct TileDims { dim3 grid, block; };
+inline TileDims tile_dims(int W, int H) { return { dim3((W + kTileX - 1) / kTileX, (H + kTileY - 1) / kTileY), dim3(kTileX, kTileY) }; }
+// this thread's pixel of a W x H image; false when it lies outside
+__device__ __forceinline__ bool tile_pixel(int W, int H, int& x, int& y)
+{
+    x = blockIdx.x * kTileX + threadIdx.x; y = blockIdx.y * kTileY + threadIdx.y;
+    return x < W && y < H;
+}
 
 } // namespace gmupt

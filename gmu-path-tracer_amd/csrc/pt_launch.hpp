@@ -1,7 +1,6 @@
-// Host-side entry points of the kernel files and of the host workers next to them, as the C-API units (gmupt_capi*.hip) call them.
-// Every file that defines one of these includes this header, so that the compiler checks the definition against the declaration
-// (lbvh_build_host of pt_lbvh.cpp is declared in pt_lbvh.hpp, normals_host of pt_normals.cpp in pt_normals.hpp, tree_cost_host of
-// pt_treecost.cpp in pt_treecost.hpp, pose_host of pt_pose.cpp in pt_pose.hpp).
+// Host-side entry points of the kernel files, as the C-API units (gmupt_capi*.hip) call them.  Every file that defines one of these
+// includes this header, so that the compiler checks the definition against the declaration.  (The host rules, the *_host functions of
+// the pt_*.cpp files, are each declared in their feature's pt_*.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -31,7 +30,6 @@ void launch_aov_raygen(const gmupt_camera_buffer& cam, uint32_t x0, uint32_t y0,
 void launch_aov_resolve(const RenderParams& p, uint32_t npix, uint32_t samples, uint32_t R, const gmupt_ray* rays, const gmupt_hit* hits,
                         gmupt_aov* out, hipStream_t s);
 void launch_denoise(const float4* beauty, const float4* aov, int W, int H, const DnParams& prm, void* scratch, float4* out, hipStream_t s);
-void denoise_host(const float* beauty, const void* aov, int W, int H, const DnParams& prm, float* out, int threads);
 size_t infill_scratch_bytes(size_t npix);
 hipError_t launch_infill(const float4* beauty, const float4* aov, int W, int H, const IfParams& prm, void* scratch, float4* out, hipStream_t s,
                          const IfCounters** countsOut);
@@ -39,15 +37,11 @@ void launch_temporal(const float4* beauty, const float4* aov, int W, int H, cons
                      hipStream_t s);
 void launch_temporal_motion(const float4* beauty, const float4* aov, const float4* motion, int W, int H, const TpPrev& prev, const TpParams& prm,
                             float4* out, float4* hist, hipStream_t s);
-void temporal_host(const float* beauty, const void* aov, const void* motion, int W, int H, const void* prev, const gmupt_camera_buffer* prevCam, int px0, int py0,
-                   int pW, int pH, const TpParams& prm, float* out, void* outHist, int threads);
 void launch_mv_resolve(const SceneView& scene, const float* prevVerts, uint32_t npix, uint32_t R, const gmupt_hit* hits, const gmupt_aov* aov,
                        gmupt_motion* out, hipStream_t s);
-void motion_host(const gmupt_hit* hits, const gmupt_aov* aov, size_t n, const gmupt_triangle* tris, const float* now, const float* prev, gmupt_motion* out);
 void launch_refit_check(const RfArgs& a, hipStream_t s);
 uint32_t launch_refit_boxes(const RfArgs& a, const std::vector<uint32_t>& levelOff, hipStream_t s);
 void launch_refit_tables(const RfArgs& a, hipStream_t s);
-void refit_host(gmupt_bvh_node* nodes, size_t N, const gmupt_triangle* tris, const float* verts, int threads);
 hipError_t lbvh_sort_temp_bytes(uint32_t n, size_t* bytes);
 size_t lbvh_scratch_bytes(uint32_t cap, size_t sortTemp);
 hipError_t launch_lbvh(void* scratch, uint32_t cap, size_t sortTemp, const float* verts, uint32_t numVerts, const int32_t* indices, uint32_t n,

@@ -1,16 +1,14 @@
-// The motion plane (gmupt_render_aovs_motion, gmupt_motion_host; include/gmupt.h states it)
+// The motion plane (gmupt_render_aovs_motion; include/gmupt.h states it)
 //
 //   k_mv_resolve   one thread per pixel of an AOV chunk, after k_aov_resolve on the same hits: the centre ray's gmupt_hit (ray pixel * R of
 //                  the chunk scratch), the triangle record, its three vertices now and in the caller's previous pose, the position the
 //                  AOV resolve has just written -> one 16-byte gmupt_motion record.  No LDS.
 //
-// The per-pixel arithmetic is pt_motion.hpp, which the host function below runs too.
+// The per-pixel arithmetic is pt_motion.hpp, which the host function (pt_motion.cpp) runs too.
 #include "pt_device.hpp"
 #include "detmath.hpp"
 #include "pt_motion.hpp"
 #include "pt_launch.hpp"
-
-#include <cstring>
 
 namespace gmupt {
 
@@ -55,22 +53,6 @@ void launch_mv_resolve(const SceneView& scene, const float* prevVerts, uint32_t 
     a.R = R; a.npix = npix;
     a.out = reinterpret_cast<float4*>(out);
     if (npix) hipLaunchKernelGGL(k_mv_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, s, a);
-}
-
-// ---- the host function (gmupt_motion_host): the caller has validated every index.  Any alignment (records are copied in and out).
-void motion_host(const gmupt_hit* hits, const gmupt_aov* aov, size_t n, const gmupt_triangle* tris, const float* now, const float* prev, gmupt_motion* out)
-{
-    for (size_t i = 0; i < n; i++) {
-        gmupt_hit h; gmupt_aov a;
-        std::memcpy(&h, (const char*)hits + i * sizeof(h), sizeof(h)); std::memcpy(&a, (const char*)aov + i * sizeof(a), sizeof(a));
-        float4 rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (h.triangle >= 0 && h.light == 0u) {
-            gmupt_triangle T;
-            std::memcpy(&T, (const char*)tris + (size_t)h.triangle * sizeof(T), sizeof(T));
-            rec = mv_pixel(h.triangle, h.u, h.v, h.light, T.v, now, prev, mk3(a.position[0], a.position[1], a.position[2]));
-        }
-        std::memcpy((char*)out + i * 16, &rec, 16);
-    }
 }
 
 } // namespace gmupt

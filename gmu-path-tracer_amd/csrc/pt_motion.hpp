@@ -1,4 +1,4 @@
-// The motion plane's per-pixel arithmetic (include/gmupt.h states it), shared by k_mv_resolve (pt_motion.hip) and gmupt_motion_host: one
+// The motion plane's per-pixel arithmetic (include/gmupt.h states it), shared by k_mv_resolve (pt_motion.hip) and motion_host (pt_motion.cpp): one
 // copy of the barycentric sums and the displacement, so that both run one binary32 sequence (build.py flags: no contraction).
 //
 // Record layout: the public gmupt_motion, 16 bytes = one float4 per pixel, row-major:  prev_position xyz, flags bits.
@@ -29,5 +29,7 @@ GM_HD float4 mv_pixel(int32_t tri, float u, float v, uint32_t light, const int32
     const f3 bp = mv_bary(w, u, v, prev + i0, prev + i1, prev + i2);
     return make_float4(mv_move(pos.x, bp.x, bn.x), mv_move(pos.y, bp.y, bn.y), mv_move(pos.z, bp.z, bn.z), u2f(1u));
 }
+
+void motion_host(const gmupt_hit* hits, const gmupt_aov* aov, size_t n, const gmupt_triangle* tris, const float* now, const float* prev, gmupt_motion* out);   // pt_motion.cpp
 
 } // namespace gmupt

@@ -3,7 +3,7 @@
 // vector to its vertex IS the summation order of the rule; with threads, every thread runs that loop over all corners and keeps the
 // vertices of its own band, so the order per vertex -- and with it every bit of the result -- does not depend on the thread count.
 #include "pt_normals.hpp"
-#include "pt_denoise.hpp"      // dn_bands
+#include "pt_bands.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -15,13 +15,13 @@ void normals_host(const float* verts, uint32_t numVerts, const int32_t* indices,
     constexpr size_t kChunk = 4096;
     const size_t V = numVerts, T = numTris;
     std::vector<float> faces(3 * T);
-    dn_bands((int)((T + kChunk - 1) / kChunk), threads, [&](int c0, int c1) {
+    host_bands((int)((T + kChunk - 1) / kChunk), threads, [&](int c0, int c1) {
         for (size_t t = (size_t)c0 * kChunk; t < std::min(T, (size_t)c1 * kChunk); t++) {
             const int32_t* i = indices + 3 * t;
             nm_face(verts + 3 * (size_t)i[0], verts + 3 * (size_t)i[1], verts + 3 * (size_t)i[2], &faces[3 * t]);
         }
     });
-    dn_bands((int)((V + kChunk - 1) / kChunk), threads, [&](int c0, int c1) {
+    host_bands((int)((V + kChunk - 1) / kChunk), threads, [&](int c0, int c1) {
         const size_t v0 = (size_t)c0 * kChunk, v1 = std::min(V, (size_t)c1 * kChunk);
         std::vector<float> sum(3 * (v1 - v0), 0.0f);
         for (size_t c = 0; c < 3 * T; c++) {

@@ -2,7 +2,7 @@
 // pt_pose.hpp, shared with the kernel.  A vertex depends on no other vertex, so the bands of the threads are independent and the result
 // cannot depend on the thread count.
 #include "pt_pose.hpp"
-#include "pt_denoise.hpp"      // dn_bands
+#include "pt_bands.hpp"
 
 #include <algorithm>
 
@@ -21,7 +21,7 @@ void pose_host(const float* rest, uint32_t numVerts, const uint16_t* joints, con
 {
     constexpr size_t kChunk = 4096;
     const size_t V = numVerts, K = influences;
-    dn_bands((int)((V + kChunk - 1) / kChunk), threads, [&](int c0, int c1) {
+    host_bands((int)((V + kChunk - 1) / kChunk), threads, [&](int c0, int c1) {
         for (size_t v = (size_t)c0 * kChunk; v < std::min(V, (size_t)c1 * kChunk); v++) {
             PsVec m = { rest[3 * v], rest[3 * v + 1], rest[3 * v + 2] };
             for (size_t t = 0; t < numTargets; t++) {

@@ -1,4 +1,4 @@
-// Refit (gmupt_renderer_refit, gmupt_bvh_refit_host; include/gmupt.h states it): the boxes of the bound tree and every traversal table
+// Refit (gmupt_renderer_refit; include/gmupt.h states it): the boxes of the bound tree and every traversal table
 // of the renderer recomputed in place for moved vertices, topology kept.  Streaming kernels, one record (or 16 bytes of one) per thread:
 //
 //   k_rf_finite  one thread per triangle record: its three vertices are inside the vertex array and finite, else a flag bit
@@ -10,9 +10,8 @@
 //   k_rf_wide    eight threads per WNode, 16 bytes each: the six plane rows through the map slot -> reference node (NaN slots kept), the
 //                link and aux rows not written; the first numOpened threads also run the flat-child test of one opened node
 //
-// All arithmetic is pt_refit.hpp, which the host refit below runs too.  Indices are size_t: a table may pass 2 GiB.
+// All arithmetic is pt_refit.hpp, which the host refit (pt_refit.cpp) runs too.  Indices are size_t: a table may pass 2 GiB.
 #include "pt_refit.hpp"
-#include "pt_denoise.hpp"
 #include "pt_launch.hpp"
 #include "pt_scratch.hpp"
 
@@ -180,24 +179,6 @@ void launch_refit_tables(const RfArgs& a, hipStream_t s)
     if (a.wnodes && a.numPairs) hipLaunchKernelGGL(k_rf_pairs, dim3(grid_for(a.numPairs, kRfBlock)), dim3(kRfBlock), 0, s, a);
     if (a.numPacked) hipLaunchKernelGGL(k_rf_nodes, dim3(grid_for(a.numPacked, kRfBlock)), dim3(kRfBlock), 0, s, a);
     if (a.wnodes && a.wideCount) hipLaunchKernelGGL(k_rf_wide, dim3(grid_for(std::max((size_t)a.wideCount * 8, (size_t)a.numOpened), kRfBlock)), dim3(kRfBlock), 0, s, a);
-}
-
-// ---- the host refit (gmupt_bvh_refit_host) on a validated tree: leaves in chunks on up to `threads` std::threads (every leaf reads only
-// the inputs), then the inner nodes by falling index on the calling thread (children have larger indices than their parent)
-void refit_host(gmupt_bvh_node* nodes, size_t N, const gmupt_triangle* tris, const float* verts, int threads)
-{
-    constexpr size_t kChunk = 4096;
-    auto store = [&](gmupt_bvh_node& n, const RfBox& b) { for (int k = 0; k < 3; k++) { n.min[k] = b.mn[k]; n.max[k] = b.mx[k]; } };
-    dn_bands((int)((N + kChunk - 1) / kChunk), threads, [&](int c0, int c1) {
-        for (size_t i = (size_t)c0 * kChunk; i < std::min(N, (size_t)c1 * kChunk); i++)
-            if (nodes[i].isLeaf && nodes[i].right > nodes[i].left) store(nodes[i], rf_leaf_box(tris, verts, nodes[i].left, nodes[i].right));
-    });
-    for (size_t i = N; i-- > 0;) {
-        if (nodes[i].isLeaf) continue;
-        const gmupt_bvh_node& l = nodes[(size_t)nodes[i].left];
-        const gmupt_bvh_node& r = nodes[(size_t)nodes[i].right];
-        store(nodes[i], rf_union(l.min, l.max, r.min, r.max));
-    }
 }
 
 } // namespace gmupt

@@ -1,4 +1,4 @@
-// Refit's arithmetic (include/gmupt.h states it), shared by the k_rf_* kernels (pt_refit.hip) and gmupt_bvh_refit_host: one copy of the
+// Refit's arithmetic (include/gmupt.h states it), shared by the k_rf_* kernels (pt_refit.hip) and refit_host (pt_refit.cpp): one copy of the
 // box rule, the triangle record and the flat-child test, so that host and device run the same binary32 statements.  Only comparisons,
 // selections and two subtractions per component: no rounding that a compiler flag could change, apart from contraction (off, build.py).
 #pragma once
@@ -66,5 +66,7 @@ struct RfArgs {
     uint32_t* flags;                 // [0] kRfFlag* of the vertex check, [1] != 0: an opened node has a flat child in a face plane
 };
 constexpr uint32_t kRfFlagNonFinite = 1u, kRfFlagBadIndex = 2u;
+
+void refit_host(gmupt_bvh_node* nodes, size_t N, const gmupt_triangle* tris, const float* verts, int threads);   // pt_refit.cpp
 
 } // namespace gmupt

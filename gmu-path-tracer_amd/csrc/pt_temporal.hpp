@@ -1,5 +1,5 @@
 // Temporal reuse's per-pixel arithmetic (include/gmupt.h states it), shared by k_tp_integrate (pt_temporal.hip) and the host integration
-// gmupt_temporal_integrate_host: one copy of the projection, the tap tests, the blend and the new record, so that both run one binary32
+// temporal_host (pt_temporal.cpp): one copy of the projection, the tap tests, the blend and the new record, so that both run one binary32
 // sequence (build.py flags: no contraction, correctly rounded divide / sqrt, denormals kept).  No transcendental is needed.
 //
 // History layout: the public gmupt_history record, 48 bytes = three float4 per pixel, row-major:
@@ -127,5 +127,8 @@ GM_HD void tp_pixel(const float4 b, const float4 a0, const float4 a1, const floa
 {
     tp_pixel_t<false>(b, a0, a1, a2, a3, make_float4(0.0f, 0.0f, 0.0f, 0.0f), pv, prm, out, r0, r1, r2);
 }
+
+void temporal_host(const float* beauty, const void* aov, const void* motion, int W, int H, const void* prev, const gmupt_camera_buffer* prevCam, int px0, int py0,
+                   int pW, int pH, const TpParams& prm, float* out, void* outHist, int threads);   // pt_temporal.cpp
 
 } // namespace gmupt

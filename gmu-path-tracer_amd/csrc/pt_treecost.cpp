@@ -3,7 +3,7 @@
 // rule; threads only share out the runs of the first level, so the order inside every sum -- and with it every bit of the result -- does
 // not depend on the thread count.  The levels above hold 1/256 of the entries each and run on the calling thread.
 #include "pt_treecost.hpp"
-#include "pt_denoise.hpp"      // dn_bands
+#include "pt_bands.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -22,7 +22,7 @@ TcPartial tree_cost_host(const gmupt_bvh_node* nodes, uint32_t n, int threads)
 {
     const size_t N = n;
     std::vector<TcPartial> level(tc_runs(N));
-    dn_bands((int)level.size(), threads, [&](int r0, int r1) {       // at most 2^24 runs
+    host_bands((int)level.size(), threads, [&](int r0, int r1) {       // at most 2^24 runs
         TcPartial x[kTcRun];
         for (size_t run = (size_t)r0; run < (size_t)r1; run++) {
             for (uint32_t i = 0; i < kTcRun; i++) {

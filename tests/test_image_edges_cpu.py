@@ -6,7 +6,8 @@ that same_or_nan compares on bits, for every frame tests/test_image_edges_gpu.py
 Every bit-level read of a float in the four shared headers, and why a GENERATED NaN (whose sign and payload differ between x86 and
 gfx950) or an out-of-range value cannot reach it:
 
-  pt_denoise.hpp   dn_prepare: f2u(beauty.w), f2u(a3.x), f2u(a3.z) -- the sample count, triangle and light words.  Caller words, read as
+  pt_denoise.hpp   dn_prepare: f2u(beauty.w), and gd_prepare (pt_guides.hpp, which it calls): f2u(a3.x), f2u(a3.z) -- the sample count,
+                   triangle and light words.  Caller words, read as
                    integers and never the result of arithmetic: a NaN pattern in them is an input, the same bits on both sides
                    (cnt_* classes; test_count_words_come_through_on_bits).
   pt_temporal.hpp  tp_pixel_t: f2u(a3.x / a3.y / a3.z), f2u(m.w), f2u(b.w) -- caller words as above (mv_flags*, n_* classes).
@@ -18,7 +19,7 @@ gfx950) or an out-of-range value cannot reach it:
                    evaluated, not 0 (test_crafted_history_records: count +inf, NaN, denormal, negative).
                    (float)n, n + (uint32_t)..: integer arithmetic on a caller word; wraps modulo 2^32 for n = 0xFFFFFFFF on both sides.
   pt_motion.hpp    none (u2f(1u) only).  pt_motion.hip reads f2u(h0.w), f2u(h1.x): the hit's triangle and light words, integers.
-  detmath.hpp      dlog2: f2u(x), exponent and mantissa bits -- reached through dpow alone, which returns 0 for x <= 0; in dn_tap x is
+  detmath.hpp      dlog2: f2u(x), exponent and mantissa bits -- reached through dpow alone, which returns 0 for x <= 0; in gd_wn (pt_guides.hpp) x is
                    hmax(0, dot3(n_p, n_q)), and hmax drops a NaN second operand, so x is 0 (no dlog2) or positive and finite (a
                    normalised normal has finite components, 0 or NaN) -- n_inf class; test_an_infinite_normal_is_invisible_to_its_neighbours.
                    dexp2: (int)n -- behind !(y > -150) and y > 128, both of which catch NaN and +-inf, so n is in -150 .. 128

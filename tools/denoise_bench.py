@@ -6,9 +6,9 @@ room: its AOVs at s = 1 and a noisy beauty image made from their albedo), at 192
   rocprofv3 --kernel-trace --stats -f csv -d DIR/prof -o dn -- python tools/denoise_bench.py --profile-pass --prof DIR/prof [--reps 5]
   python tools/denoise_bench.py --split DIR/prof [--out DIR]                                 per kernel and per pass from the trace
 
-The gathered bytes of a pass are counted from the layout of csrc/pt_denoise.hpp over the frame's actual valid pixels: per valid pixel the
-centre (col 16 + nl 16 + xa 16 + ag 8 + z 4 B), the variance words of its in-image 3x3 neighbours (4 B each), 16 B of col per in-image tap and
-40 B more (nl, xa, ag) per valid one, and the 16 B store; an invalid pixel reads 16 B and writes 16 B.  The timing pass writes
+The gathered bytes of a pass are counted from the layout of csrc/pt_guides.hpp over the frame's actual valid pixels: per valid pixel the
+centre (col 16 + nw 16 + xa 16 + ag 8 + z 4 B), the variance words of its in-image 3x3 neighbours (4 B each), 16 B of col per in-image tap and
+40 B more (nw, xa, ag) per valid one, and the 16 B store; an invalid pixel reads 16 B and writes 16 B.  The timing pass writes
 DIR/denoise_bench.json; --split writes DIR/denoise_split.json (medians over the calls).
 """
 import argparse
@@ -48,7 +48,7 @@ def frame(pkg, dev, sb, scene, W, H):
 
 
 def gathered_bytes(beauty, aov, passes=PASSES):
-    """Bytes each pass reads + writes by the layout of pt_denoise.hpp, over this frame's valid pixels (see the module text)."""
+    """Bytes each pass reads + writes by the layout of pt_guides.hpp, over this frame's valid pixels (see the module text)."""
     import numpy as np
     b = beauty.cpu().numpy(); a = aov.cpu().numpy()
     u = a.view(np.uint32)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# ThreadSanitizer and AddressSanitizer + UBSan runs of the host SBVH builder (CPU build only: GPU sanitizers are not available on the pool).
+# ThreadSanitizer and AddressSanitizer + UBSan runs of the host code: the SBVH builder and the host rules (CPU builds only: GPU sanitizers are not available on the pool).
 set -e
 cd "$(dirname "$0")"
 SRC="builder_main.cpp ../../gmu-path-tracer_amd/host/sbvh_builder.cpp"
@@ -25,4 +25,11 @@ ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_treeopt_asan"
 # the host convergence rule (csrc/pt_converge.cpp), the same way
 "$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_converge_asan" converge_main.cpp ../../gmu-path-tracer_amd/csrc/pt_converge.cpp
 ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_converge_asan"
+# the host rules of the image stages (csrc/pt_denoise.cpp, pt_infill.cpp, pt_temporal.cpp), the same way; their row bands are std::threads, so
+# once more under ThreadSanitizer
+IMG="image_main.cpp ../../gmu-path-tracer_amd/csrc/pt_denoise.cpp ../../gmu-path-tracer_amd/csrc/pt_infill.cpp ../../gmu-path-tracer_amd/csrc/pt_temporal.cpp"
+"$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_image_asan" $IMG -lpthread
+ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_image_asan"
+"$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=thread -ffp-contract=off -o "$BIN/gmupt_image_tsan" $IMG -lpthread
+TSAN_OPTIONS="halt_on_error=1" $NORAND "$BIN/gmupt_image_tsan"
 echo "sanitizers: clean"
