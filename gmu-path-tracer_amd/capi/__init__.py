@@ -6,6 +6,9 @@ fails, GmuptError is raised with gmupt_last_error().
 One module per feature, like csrc/gmupt_capi_*.hip, each re-exported here so that callers write capi.NAME: _abi (the C-ABI's types and
 SYMBOLS), _lib (the loaded library, its only owner), _stage (what the rest shares), device, then the feature modules query, denoise,
 converge, mesh and accel, then core (Camera, Renderer), which imports the feature modules and is imported by none of them.
+
+adaptive (adaptive sampling) is the exception: it is reached as capi.adaptive.NAME and keeps its structures and prototypes itself, so
+that the names at this level, the Renderer class and SYMBOLS stay the recorded surface (tests/golden/capi_surface.json).
 """
 from ._abi import *  # noqa: F401,F403
 from ._lib import _check, _ptr, lib, use_build  # noqa: F401
@@ -19,3 +22,4 @@ from .mesh import Normals, Pose, pose_host, vertex_normals_host  # noqa: F401
 from .accel import (Lbvh, TreeOptimizer, bvh_refit_host, lbvh_build_host, sbvh_build, travtables, tree_cost_host,  # noqa: F401
                     tree_optimize_host, tree_sah, wide_tables_addressable)
 from .core import Camera, Renderer  # noqa: F401
+from . import adaptive  # noqa: F401,E402

@@ -244,6 +244,10 @@ class ConvergeInfo(C.Structure):
 converge_pixel_dtype = np.dtype([("n", "<u4"), ("k", "<u4"), ("w", "<u4"), ("pad", "<u4"), ("s", "<f8"), ("mean", "<f8"), ("m2", "<f8")])
 assert C.sizeof(ConvergeParams) == 12 and C.sizeof(ConvergeInfo) == 56 and converge_pixel_dtype.itemsize == 40
 
+# Prototypes of the feature modules that keep their own part of the ABI (adaptive.py): name -> (restype, argtypes), bound by _lib with
+# SYMBOLS on every load.  A module adds its entries when it is imported, which the package does before any library is loaded.
+_EXTRA_SYMBOLS = {}
+
 # the `which` of gmupt_debug_travtables_data / gmupt_debug_read_travtable, in order
 TRAVTABLE_KINDS = ("node64", "tri48", "tripair", "pair_ref", "wnode", "rec64", "scalars", "level_nodes", "level_off", "node_map", "wide_map", "opened")
 

@@ -4,7 +4,7 @@ import ctypes as C
 import os
 
 from .. import build as _build
-from ._abi import SYMBOLS, GmuptError
+from ._abi import _EXTRA_SYMBOLS, SYMBOLS, GmuptError
 
 _current = None
 _libs = {}
@@ -14,7 +14,7 @@ _devices_created = 0   # gmupt_device_create calls of this process (a process th
 def _load(path):
     if path not in _libs:
         handle = C.CDLL(path)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(_EXTRA_SYMBOLS.items()):
             fn = getattr(handle, name)  # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -57,7 +57,7 @@ class Renderer:
         self.pool = pool_paths or PATHCOUNT
         self._scene = None
         # the live handles of this renderer by class (Handle._siblings): closed before it
-        self._temporals, self._normals, self._poses, self._converges = [], [], [], []
+        self._temporals, self._normals, self._poses, self._converges, self._adaptives = [], [], [], [], []
 
     def bind_scene(self, sb):
         self._scene = sb  # keep the buffers alive
@@ -305,7 +305,7 @@ class Renderer:
 
     def close(self):
         if self.h:
-            for t in self._temporals + self._normals + self._poses + self._converges:
+            for t in self._temporals + self._normals + self._poses + self._converges + self._adaptives:
                 t.close()
             lib().gmupt_renderer_destroy(self.h)
             self.h = _P()

@@ -332,6 +332,9 @@ static int run_iteration(gmupt_renderer* r, bool doShade, bool doExtend, bool do
 {
     if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_iterate: no scene bound");
     if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_iterate: no camera set");
+    const gmupt_adaptive* plan = doShade ? r->adaptive : nullptr;   // adaptive sampling: null = the launches below are all there is
+    if (plan && (uint64_t)plan->W * plan->H != (uint64_t)r->p.fbW * r->p.fbH)
+        return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_iterate: the attached sampling plan is for %ux%u pixels, the renderer's rectangle is %ux%u", plan->W, plan->H, r->p.fbW, r->p.fbH);
     HIP_TRY(hipSetDevice(r->dev->id));
     const RenderParams& p = r->p;
     const int clearFrame = (p.cam.iterationCounter == 0) ? 1 : 0; // logic.hlsl:206
@@ -352,6 +355,7 @@ static int run_iteration(gmupt_renderer* r, bool doShade, bool doExtend, bool do
         if (clearFrame) { launch_clear(p, r->stream); r->accumGeneration++; } else launch_logic(p, r->stream);
         if (ev && !extOnly) HIP_TRY(hipEventRecord(ev->e[1], r->stream));
         launch_material(p, clearFrame, r->stream);  // computes its own queue offsets (no scan launch)
+        if (plan && plan->count) launch_adaptive_retarget(p, plan->sc.list, plan->count, plan->uniformEvery, r->stream);   // re-aims the fresh camera paths
         if (ev) HIP_TRY(hipEventRecord(ev->e[2], r->stream));
     }
     if (!doShade) HIP_TRY(hipMemsetAsync(p.travCounters, 0, 128, r->stream)); // k_material (block 0) zeroes the ray-cast work counters in a full iteration
@@ -427,6 +431,7 @@ extern "C" int gmupt_resize(gmupt_renderer* r, uint32_t width, uint32_t height)
     HIP_TRY(hipStreamSynchronize(r->stream));
     r->desc.width = width; r->desc.height = height;
     r->accumGeneration++;
+    r->adaptive = nullptr;                            // a sampling plan is a plan for the old rectangle
     return GMUPT_OK;
 }
 

@@ -385,6 +385,59 @@ extern "C" int gmupt_converge_host(gmupt_converge_pixel* state, const float* rgb
     return GMUPT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ adaptive sampling: parameters and the host rules (pt_adaptive.cpp, pt_adaptive.hpp)
+static_assert(sizeof(gmupt_adaptive_params) == 12 && offsetof(gmupt_adaptive_params, uniform_every) == 8, "gmupt_adaptive_params layout");
+static_assert(sizeof(gmupt_adaptive_info) == 32 && offsetof(gmupt_adaptive_info, max_rep) == 16 && offsetof(gmupt_adaptive_info, ms) == 24, "gmupt_adaptive_info layout");
+
+extern "C" void gmupt_adaptive_default_params(gmupt_adaptive_params* p)
+{
+    if (!p) return;
+    p->threshold = 0.0f; p->max_repeat = 1; p->uniform_every = 0;
+}
+
+int adaptive_params(const char* fn, const gmupt_adaptive_params* p, float monitorThreshold, AdParams& out)
+{
+    if (!p) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null parameters (there is no default threshold)", fn);
+    const float T = p->threshold == 0.0f ? monitorThreshold : p->threshold;
+    if (!(T > 0.0f) || !cv_finite(T)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: threshold = %g (finite and > 0)", fn, (double)T);
+    if (p->max_repeat < 1 || p->max_repeat > kAdMaxRepeat) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: max_repeat = %u (1..%u)", fn, p->max_repeat, kAdMaxRepeat);
+    out.threshold = T; out.maxRepeat = p->max_repeat;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_adaptive_select_host(const float* error, uint32_t width, uint32_t height, const gmupt_adaptive_params* params, uint32_t* list_out,
+                                          size_t capacity, gmupt_adaptive_info* info)
+{
+    const char* fn = "gmupt_adaptive_select_host";
+    if (!error || !info) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null error plane or info", fn);
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0 || n > 0xFFFFFFFFull) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: plane of %ux%u (1 .. 2^32 - 1 pixels)", fn, width, height);
+    AdParams prm;
+    GMUPT_TRY(adaptive_params(fn, params, 0.0f, prm));
+    if (n * prm.maxRepeat > kAdMaxEntries) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %ux%u pixels at max_repeat = %u are more than 2^28 entries", fn, width, height, prm.maxRepeat);
+    const AdPartial total = adaptive_select_host(error, (size_t)n, prm, nullptr, 0);
+    if (list_out) {
+        if (capacity < total.entries) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: room for %zu entries given, %u needed", fn, capacity, total.entries);
+        adaptive_select_host(error, (size_t)n, prm, list_out, capacity);
+    }
+    ad_fill_info(total, (uint32_t)n, info);
+    info->ms = 0.0;
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_adaptive_pixel_host(const uint32_t* list, uint32_t count, uint32_t uniform_every, uint32_t width, uint32_t height, uint32_t k, uint32_t* pix)
+{
+    const char* fn = "gmupt_adaptive_pixel_host";
+    if (!list || !pix) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null list or result", fn);
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0 || n > 0xFFFFFFFFull) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: rectangle of %ux%u (1 .. 2^32 - 1 pixels)", fn, width, height);
+    if (count == 0) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: an empty list re-aims nothing", fn);
+    const uint32_t at = ad_pixel_of(list, count, uniform_every, (uint32_t)n, k);
+    if (at >= n) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: list entry %u outside the %ux%u rectangle", fn, at, width, height);
+    *pix = at;
+    return GMUPT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ pose: the host reference (pt_pose.cpp) of gmupt_pose_update
 extern "C" int gmupt_pose_host(const float* rest, uint32_t num_verts, const uint16_t* joints, const float* weights, uint32_t influences, const float* joint_mats,
                                uint32_t num_joints, const float* deltas, const float* target_weights, uint32_t num_targets, float* verts_out, uint32_t threads)

@@ -13,6 +13,7 @@
 #include "pt_treeopt.hpp"
 #include "pt_pose.hpp"
 #include "pt_converge.hpp"
+#include "pt_adaptive.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
@@ -95,6 +96,8 @@ struct gmupt_camera { Camera cam; gmupt_camera(uint32_t w, uint32_t h) : cam(w, 
 struct gmupt_sbvh { gmupt::SbvhBuilder* b; };
 struct gmupt_travtables { TravTables t; };
 
+struct gmupt_adaptive;
+
 enum TravTable { TT_NODES, TT_TRIS, TT_RECS, TT_WIDE, TT_PAIRS, TT_PAIRREF, TT_COUNT };   // the renderer's six device tables, in the order build_traversal_copy fills them
 
 struct gmupt_renderer {
@@ -143,6 +146,8 @@ struct gmupt_renderer {
     // tree cost (gmupt_renderer_tree_cost): the partial results of every level, 48 bytes per 256 records; allocated on first use, grown on demand
     DevMem tcScratch;
     EventPair tcEv;
+    // adaptive sampling (gmupt_renderer_set_adaptive): the attached plan, not owned; null = every iteration launches what it always did
+    gmupt_adaptive* adaptive = nullptr;
 
     __attribute__((visibility("default"))) ~gmupt_renderer() { if (stream) (void)hipStreamDestroy(stream); }   // gmupt_renderer_destroy has synchronised it; the library has always exported this symbol
     uint32_t tile_x0() const { return p.tileEnabled ? p.tileX0 : 0u; } uint32_t tile_y0() const { return p.tileEnabled ? p.tileY0 : 0u; }   // the origin of the rendered rectangle
@@ -197,6 +202,18 @@ struct gmupt_converge {
     EventPair ev;
 };
 
+// the sampling plan of one renderer (gmupt_adaptive_*): the list, the run totals and their offsets of a W x H rectangle in one
+// allocation (adaptive_carve, pt_adaptive.hip), carved for `pixels` and `cap` entries; the error plane of gmupt_render_adaptive; which
+// accumulation of the renderer the plan was made from
+struct gmupt_adaptive {
+    gmupt_renderer* r = nullptr;
+    uint32_t W = 0, H = 0, count = 0, uniformEvery = 0;
+    DevMem mem; AdScratch sc{}; size_t pixels = 0, cap = 0;
+    DevMem errPlane;
+    uint64_t generation = 0;
+    EventPair ev;
+};
+
 // ------------------------------------------------------------------------------------------------ shared between units
 size_t kind_stride(gmupt_buffer_kind k);                                                                        // gmupt_capi.hip
 gmupt_buffer* buffer_alloc(gmupt_device* dev, gmupt_buffer_kind kind, size_t elems, size_t bytes, hipError_t* e);
@@ -207,6 +224,7 @@ int image_args(const char* fn, const void* beauty, const void* aov, uint32_t W, 
 int temporal_params(const char* fn, const gmupt_temporal_params* p, DnParams& dn, TpParams& tp);
 int infill_params(const char* fn, const gmupt_infill_params* p, IfParams& out);
 int converge_params(const char* fn, const gmupt_converge_params* p, CvParams& out);
+int adaptive_params(const char* fn, const gmupt_adaptive_params* p, float monitorThreshold, AdParams& out);   // threshold 0 = monitorThreshold
 // gmupt_capi_denoise.hip: the chains behind the temporal entry points; infill == nullptr is the chain without the infill stage
 int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
                      const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,

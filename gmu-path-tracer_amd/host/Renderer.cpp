@@ -303,6 +303,43 @@ gmupt_converge_info Renderer::renderUntil(const gmupt_converge_params* params, u
 	return info;
 }
 
+Renderer::AdaptiveRun Renderer::renderAdaptive(const gmupt_converge_params* cparams, const gmupt_adaptive_params* aparams, unsigned checkEvery,
+                                               unsigned maxIterations, float* deviceError)
+{
+	if (checkEvery == 0) throw std::invalid_argument("Renderer::renderAdaptive: checkEvery == 0");
+	if (!aparams || !deviceError) throw std::invalid_argument("Renderer::renderAdaptive: null parameters or error plane");
+	gmupt_converge_params cp;
+	if (cparams) cp = *cparams; else gmupt_converge_default_params(&cp);
+	gmupt_adaptive_params ap = *aparams;
+	if (ap.threshold == 0.f) ap.threshold = cp.threshold;   // "the monitor's"
+	if (!mConverge) { gmupt_converge* c = nullptr; check(gmupt_converge_create(mRenderer.get(), &c)); mConverge.reset(c); }
+	if (!mAdaptive) { gmupt_adaptive* a = nullptr; check(gmupt_adaptive_create(mRenderer.get(), &a)); mAdaptive.reset(a); }
+	AdaptiveRun run{};
+	const Resolution target = targetSize();
+	check(gmupt_renderer_set_adaptive(mRenderer.get(), nullptr)); // no error plane of this frame yet
+	bool attached = false;
+	unsigned k = 0;
+	while (k < maxIterations)
+	{
+		update(0.f);
+		if (attached && mScene.mCamera.getBuffer()->iterationCounter == 0) { check(gmupt_renderer_set_adaptive(mRenderer.get(), nullptr)); attached = false; } // a restarted frame
+		draw();
+		k++;
+		if (k % checkEvery) continue;
+		check(gmupt_converge_update(mConverge.get(), &cp, deviceError, &run.converge)); // synchronises
+		check(gmupt_synchronize(mRenderer.get()));
+		if (run.converge.converged) break;
+		check(gmupt_adaptive_select(mAdaptive.get(), deviceError, target.first, target.second, &ap, &run.plan));
+		check(gmupt_renderer_set_adaptive(mRenderer.get(), mAdaptive.get()));
+		attached = true;
+	}
+	check(gmupt_renderer_set_adaptive(mRenderer.get(), nullptr));
+	gmupt_stats st{};
+	check(gmupt_get_stats(mRenderer.get(), &st));
+	run.iterations = k; run.pathsGenerated = st.paths_generated;
+	return run;
+}
+
 gmupt_lbvh_info Renderer::rebuildScene(unsigned maxLeafSize, const std::vector<int32_t>* indices, unsigned optimizePasses, gmupt_treeopt_info* optimizeInfo)
 {
 	const gmupt_lbvh_info info = mScene.rebuildOnDevice(maxLeafSize, indices, optimizePasses, optimizeInfo);

@@ -7,6 +7,7 @@
 #include <utility>
 #include <vector>
 #include "Scene.hpp"
+#include "../../include/gmupt_adaptive.h"
 
 class Renderer
 {
@@ -98,6 +99,15 @@ public:
 	// *iterations = frames run by this call.  Returns the last check's info, all zero when no check ran.  checkEvery == 0 throws.
 	gmupt_converge_info renderUntil(const gmupt_converge_params* params, unsigned checkEvery, unsigned maxIterations, float* deviceErrorOrNull = nullptr,
 	                                unsigned* iterations = nullptr);
+	// renderUntil with adaptive sampling (include/gmupt_adaptive.h): after every check that does not end the loop the monitor's error plane
+	// becomes a sampling plan of this renderer (gmupt_adaptive_select through its own handle, created on first use), attached for the next
+	// frames: their new camera paths go to the pixels still above the threshold.  aparams->threshold == 0 means cparams' threshold.  The plan
+	// is detached before a frame that clears the target and before returning.  deviceError: targetSize() floats of caller-owned device
+	// memory, required here (the plan is made from it); it holds the last check's plane.  plan = the last selection's summary (all zero
+	// when none ran), pathsGenerated = gmupt_stats::paths_generated of the renderer after the last frame.  checkEvery == 0 throws.
+	struct AdaptiveRun { gmupt_converge_info converge; gmupt_adaptive_info plan; unsigned iterations; unsigned long long pathsGenerated; };
+	AdaptiveRun renderAdaptive(const gmupt_converge_params* cparams, const gmupt_adaptive_params* aparams, unsigned checkEvery, unsigned maxIterations,
+	                           float* deviceError);
 	// geometry a refit does not cover (after Scene::setVertices with vertices that moved far, or with another triangle list): a new tree
 	// from the GPU LBVH builder (Scene::rebuildOnDevice) bound in place of the old one, the accumulation restarted and the temporal history
 	// dropped -- a new binding is a new geometry.  The host pass of the bind (the traversal tables) runs as for any bind.
@@ -118,6 +128,7 @@ private:
 	struct NormalsDeleter { void operator()(gmupt_normals* n) const { gmupt_normals_destroy(n); } };
 	struct PoseDeleter { void operator()(gmupt_pose* p) const { gmupt_pose_destroy(p); } };
 	struct ConvergeDeleter { void operator()(gmupt_converge* c) const { gmupt_converge_destroy(c); } };
+	struct AdaptiveDeleter { void operator()(gmupt_adaptive* a) const { gmupt_adaptive_destroy(a); } };
 
 	void* mHwnd;
 	std::unique_ptr<gmupt_device, DeviceDeleter> mDevice;
@@ -126,6 +137,7 @@ private:
 	std::unique_ptr<gmupt_normals, NormalsDeleter> mNormals;    // adjacency of refitScene(.., smoothNormals) (declared after mRenderer: destroyed before it)
 	std::unique_ptr<gmupt_pose, PoseDeleter> mPose;             // the rig of poseScene on the device (declared after mRenderer: destroyed before it)
 	std::unique_ptr<gmupt_converge, ConvergeDeleter> mConverge; // the monitor of renderUntil (declared after mRenderer: destroyed before it)
+	std::unique_ptr<gmupt_adaptive, AdaptiveDeleter> mAdaptive; // the sampling plan of renderAdaptive (declared after mRenderer: destroyed before it)
 	Scene mScene;
 	Resolution mResolution;
 	RowBand mBand;

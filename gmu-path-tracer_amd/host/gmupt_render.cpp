@@ -28,6 +28,9 @@
 //                [--tree-cost]                            the surface-area cost of the bound tree (Renderer::treeCost), once after bind and once more
 //                                                         after --vertices is applied: one JSON line each with the gmupt_tree_cost_info fields, the
 //                                                         doubles as hex bit patterns; not with --ranks
+//                [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]
+//                                                         adaptive sampling in that loop (Renderer::renderAdaptive, include/gmupt_adaptive.h): the JSON
+//                                                         line gains active, entries, max_rep, skipped_nonfinite of the last plan and paths_generated
 //                [--until-error T [--check-every N] [--allow-pixels M] [--error-map FILE.pfm]]
 //                                                         the frames run until the image is done (Renderer::renderUntil, include/gmupt.h "Convergence"):
 //                                                         after every N frames (default 8) the per-pixel standard error of the tone-mapped luminance
@@ -49,6 +52,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <algorithm>
 #include <exception>
 #include <stdexcept>
@@ -115,13 +119,17 @@ void writePlanePfm(const std::string& path, const std::vector<float>& plane, uns
 	std::fclose(f);
 }
 // the gmupt_converge_info fields of the last check and the iterations run as one JSON line; the floats as hex bit patterns (ms as a decimal)
-void printConverge(unsigned iterations, const gmupt_converge_info& c)
+void printConverge(unsigned iterations, const gmupt_converge_info& c, const gmupt_adaptive_info* plan = nullptr, unsigned long long pathsGenerated = 0)
 {
 	auto bits = [](double d) { unsigned long long u; std::memcpy(&u, &d, sizeof(u)); return u; };
 	unsigned m; std::memcpy(&m, &c.max_error, sizeof(m));
 	std::printf("{\"converge\": {\"iterations\": %u, \"converged\": %u, \"pixels\": %u, \"unsampled\": %u, \"known\": %u, \"nonfinite\": %u, \"below\": %u, "
-	            "\"max_error\": \"%08x\", \"sum_error\": \"%016llx\", \"mean_error\": \"%016llx\", \"ms\": %.6g}}\n",
+	            "\"max_error\": \"%08x\", \"sum_error\": \"%016llx\", \"mean_error\": \"%016llx\", \"ms\": %.6g",
 	            iterations, c.converged, c.pixels, c.unsampled, c.known, c.nonfinite, c.below, m, bits(c.sum_error), bits(c.mean_error), c.ms);
+	if (plan)   // --adaptive: the last plan's summary and the paths generated
+		std::printf(", \"active\": %u, \"entries\": %u, \"max_rep\": %u, \"skipped_nonfinite\": %u, \"paths_generated\": %llu", plan->active, plan->entries, plan->max_rep,
+		            plan->skipped_nonfinite, pathsGenerated);
+	std::printf("}}\n");
 }
 // the gmupt_tree_cost_info fields as one JSON line; the doubles as the hex bit patterns of their binary64 values (ms as a decimal: it is a time)
 void printTreeCost(const char* when, const gmupt_tree_cost_info& c)
@@ -151,6 +159,7 @@ int main(int argc, char** argv)
 	bool infill = false;
 	std::string builder = "sbvh", dumpTree; unsigned leaf = 4, optimize = 0;
 	bool treeCost = false;
+	bool adaptive = false, maxRepeatGiven = false, uniformEveryGiven = false; unsigned maxRepeat = 1, uniformEvery = 0;
 	bool untilError = false, checkEveryGiven = false, allowPixelsGiven = false; float untilThreshold = 0.f; unsigned checkEvery = 8, allowPixels = 0; std::string errorMap;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
@@ -191,6 +200,9 @@ int main(int argc, char** argv)
 		else if (a == "--check-every") { char* end = nullptr; const char* v = next(); checkEvery = std::strtoul(v, &end, 10); checkEveryGiven = true; if (end == v || *end || checkEvery < 1) { std::fprintf(stderr, "--check-every takes a number of frames >= 1\n"); return 2; } }
 		else if (a == "--allow-pixels") { char* end = nullptr; const char* v = next(); allowPixels = std::strtoul(v, &end, 10); allowPixelsGiven = true; if (end == v || *end) { std::fprintf(stderr, "--allow-pixels takes a number of pixels\n"); return 2; } }
 		else if (a == "--error-map") errorMap = next();
+		else if (a == "--adaptive") adaptive = true;
+		else if (a == "--max-repeat") { char* end = nullptr; const char* v = next(); maxRepeat = std::strtoul(v, &end, 10); maxRepeatGiven = true; if (end == v || *end || maxRepeat < 1 || maxRepeat > 64) { std::fprintf(stderr, "--max-repeat takes a number in 1..64\n"); return 2; } }
+		else if (a == "--uniform-every") { char* end = nullptr; const char* v = next(); uniformEvery = std::strtoul(v, &end, 10); uniformEveryGiven = true; if (end == v || *end) { std::fprintf(stderr, "--uniform-every takes a number of paths (0 = off)\n"); return 2; } }
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -211,6 +223,10 @@ int main(int argc, char** argv)
 			            "                                 (default 8) the per-pixel standard error of the tone-mapped luminance mean is estimated; ends when all but M pixels\n"
 			            "                                 (default 0) are at or below T, or after --frames; one JSON line with the last check's info and the iterations run,\n"
 			            "                                 floats as hex bit patterns; FILE.pfm (Pf): the error per pixel, -1 = unknown; not with --ranks\n"
+			            "             [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]   adaptive sampling: after every check that does not end the loop\n"
+			            "                                 the new camera paths go to the pixels still above T, up to N (default 1, at most 64) list entries each,\n"
+			            "                                 every N-th path (default 0 = none) to the pixel it would have gone to anyway; T must be > 0; the JSON line\n"
+			            "                                 gains active, entries, max_rep and skipped_nonfinite of the last plan and paths_generated\n"
 			            "             [--builder sbvh|lbvh [--leaf L]]   lbvh: the tree rebuilt on the GPU before the frames (linear BVH, leaves of at most L triangles,\n"
 			            "                                 default 4), one JSON line with the build info; not with --ranks.  With --build-only: the host reference of that build\n"
 			            "             [--optimize N]      with --builder lbvh: N = 1..8 passes of the treelet optimiser on the new tree before it is bound (0, the\n"
@@ -313,6 +329,10 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--smooth-normals recomputes the normals of moved vertices: it needs --vertices FILE or --rig FILE --pose FILE");
 		if (!untilError && (checkEveryGiven || allowPixelsGiven || !errorMap.empty()))
 			throw std::invalid_argument("--check-every, --allow-pixels and --error-map belong to the convergence loop: they need --until-error T");
+		if (!adaptive && (maxRepeatGiven || uniformEveryGiven))
+			throw std::invalid_argument("--max-repeat and --uniform-every belong to adaptive sampling: they need --adaptive");
+		if (adaptive && (!untilError || !(untilThreshold > 0.f) || untilThreshold > std::numeric_limits<float>::max()))
+			throw std::invalid_argument("--adaptive plans from the convergence loop: it needs --until-error T with a finite T > 0");
 		if (untilError && ranks > 1)
 			throw std::invalid_argument("--until-error judges the frame of a single process: it cannot be combined with --ranks N > 1");
 		if (treeCost && ranks > 1)
@@ -386,15 +406,24 @@ int main(int argc, char** argv)
 			const size_t pixels = static_cast<size_t>(w) * h;
 			struct DeviceFree { void operator()(float* p) const { (void)hipFree(p); } };
 			std::unique_ptr<float, DeviceFree> deviceError;   // the error plane on the device, freed on every way out
-			if (!errorMap.empty()) {
+			if (!errorMap.empty() || adaptive) {
 				void* mem = nullptr;
 				if (hipMalloc(&mem, pixels * sizeof(float)) != hipSuccess) throw std::runtime_error("cannot allocate the error plane");
 				deviceError.reset(static_cast<float*>(mem));
 			}
 			unsigned ran = 0;
-			const gmupt_converge_info ci = renderer.renderUntil(&cp, checkEvery, frames, deviceError.get(), &ran);
-			printConverge(ran, ci);
-			if (deviceError) {
+			gmupt_converge_info ci{};
+			if (adaptive) {
+				gmupt_adaptive_params ap; gmupt_adaptive_default_params(&ap);
+				ap.max_repeat = maxRepeat; ap.uniform_every = uniformEvery;   // threshold 0: the monitor's
+				const Renderer::AdaptiveRun run = renderer.renderAdaptive(&cp, &ap, checkEvery, frames, deviceError.get());
+				ran = run.iterations; ci = run.converge;
+				printConverge(ran, ci, &run.plan, run.pathsGenerated);
+			} else {
+				ci = renderer.renderUntil(&cp, checkEvery, frames, deviceError.get(), &ran);
+				printConverge(ran, ci);
+			}
+			if (!errorMap.empty()) {
 				std::vector<float> plane(pixels, -1.0f);   // no check ran: every pixel unknown
 				if (ci.pixels && hipMemcpy(plane.data(), deviceError.get(), pixels * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("cannot read the error plane");
 				writePlanePfm(errorMap, plane, w, h);

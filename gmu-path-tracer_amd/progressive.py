@@ -30,6 +30,8 @@ class ProgressiveSession:
         self.previews = 0
         self.temporal = None   # the history handle of denoised_temporal, created on first use
         self.converge = None   # the convergence monitor of run_until, created on first use
+        self.adaptive = None   # the sampling plan of run_until(adaptive=True), created on first use
+        self._planned = False  # the plan is attached to the renderer
         self.motion = bool(motion)   # denoised_temporal goes through the motion entry point (also set by set_vertices(keep_history=True))
         self.lbvh = None       # the GPU tree builder of rebuild(), created on first use
         self._indices = None   # the index list of the last rebuild()
@@ -211,10 +213,34 @@ class ProgressiveSession:
     def _reset_converge(self):
         if self.converge is not None:
             self.converge.reset()
+        self._detach_plan()                          # a plan is made from the error plane of the accumulation that just ended
+
+    def _detach_plan(self):
+        if self._planned:
+            self._attach_plan(None)
+            self._planned = False
+
+    def _attach_plan(self, plan):
+        """A renderer with adaptive() and set_adaptive() of its own (a stand-in, a host's own class) is asked itself; capi.Renderer has
+        neither method and is served by capi.adaptive."""
+        if hasattr(self.renderer, "set_adaptive"):
+            self.renderer.set_adaptive(plan)
+        else:
+            from .capi import adaptive
+            adaptive.set_adaptive(self.renderer, plan)
+
+    def _new_plan(self):
+        if hasattr(self.renderer, "adaptive"):
+            return self.renderer.adaptive()
+        from .capi import adaptive
+        return adaptive.Adaptive(self.renderer)
 
     def close(self):
         """Releases what the session itself created: the tree builder of rebuild(), the Normals of set_vertices(normals="smooth"), the
-        history handle of denoised_temporal() and the convergence monitor of run_until()."""
+        history handle of denoised_temporal(), the convergence monitor of run_until() and its sampling plan."""
+        self._detach_plan()
+        if self.adaptive is not None:
+            self.adaptive.close(); self.adaptive = None
         if self.converge is not None:
             self.converge.close(); self.converge = None
         if self.normals is not None:
@@ -278,6 +304,8 @@ class ProgressiveSession:
     # ---- frames
     def frame(self, dt=0.0):
         self.camera.update(dt)                       # Renderer::update: camera vectors, iterationCounter, randomSeed
+        if self._planned and getattr(self.camera.buffer, "iterationCounter", 1) == 0:
+            self._detach_plan()                      # this frame clears the target: the restarted frame has no error plane yet
         self.renderer.set_camera(self.camera.buffer)
         self.renderer.iterate()                      # Renderer::draw
         self.frames += 1
@@ -292,7 +320,8 @@ class ProgressiveSession:
             last = out if out is not None else last
         return last
 
-    def run_until(self, threshold, check_every=8, max_frames=4096, min_batches=2, allow_pixels=0, dt=0.0):
+    def run_until(self, threshold, check_every=8, max_frames=4096, min_batches=2, allow_pixels=0, dt=0.0, adaptive=False, max_repeat=1,
+                  uniform_every=0):
         """Frames until the image is done: after every `check_every` frames the session's convergence monitor (capi.Converge,
         include/gmupt.h "Convergence", created on first use and kept until close()) estimates the standard error of every pixel's
         tone-mapped luminance mean, and the loop ends at the first check at which all but `allow_pixels` pixels have seen
@@ -303,19 +332,37 @@ class ProgressiveSession:
         per check, so that all of them leave in the same frame: a rank that stopped alone would hang the next tile gather.  The
         returned `converged` is the agreed one; the other fields are this rank's.
         The monitor comes from renderer.converge() (capi.Renderer has it; a stand-in returns anything with update(**params), reset()
-        and close())."""
+        and close()).
+        adaptive=True: after every check that does not end the loop the monitor's error plane becomes a sampling plan (capi.adaptive.Adaptive,
+        include/gmupt_adaptive.h, created on first use and kept until close()): the next frames send their new camera
+        paths to the pixels still above `threshold`, up to `max_repeat` entries each, every `uniform_every`-th path (0 = none) to
+        the pixel it would have gone to anyway.  The info dict then holds "plan", the last selection's summary.  A converged return
+        detaches the plan.  A return at max_frames leaves it attached -- the image is not done, and frame() and run() go on sampling
+        by it -- until an event that resets the monitor, a frame that clears the target, or a run_until without `adaptive` detaches it.  With world > 1 each rank plans its own tile.
+        The plan is a capi.adaptive.Adaptive of the renderer, attached with capi.adaptive.set_adaptive; a renderer that has adaptive()
+        and set_adaptive(plan) itself is asked instead (a stand-in returns anything with select(error, **params) and close()), and the
+        monitor's update(error=True, **params) returns (info, error plane)."""
         if check_every < 1:
             raise ValueError("run_until: check_every=%r (at least 1)" % (check_every,))
         if self.converge is None:
             self.converge = self.renderer.converge()
+        if not adaptive:
+            self._detach_plan()                      # of an earlier adaptive call
+        elif self.adaptive is None:
+            self.adaptive = self._new_plan()
         info = {"converged": False}
+        plan = None
         ran = 0
         while ran < max_frames:
             self.frame(dt)
             ran += 1
             if ran % check_every:
                 continue
-            info = dict(self.converge.update(threshold=threshold, min_batches=min_batches, allow_pixels=allow_pixels))
+            if adaptive:
+                info, error = self.converge.update(error=True, threshold=threshold, min_batches=min_batches, allow_pixels=allow_pixels)
+                info = dict(info)
+            else:
+                info = dict(self.converge.update(threshold=threshold, min_batches=min_batches, allow_pixels=allow_pixels))
             if self.dist is not None and self.world > 1:
                 import torch
                 flag = torch.tensor([0 if info["converged"] else 1], dtype=torch.int32)
@@ -324,7 +371,14 @@ class ProgressiveSession:
                 self.dist.all_reduce(flag, op=self.dist.ReduceOp.MAX)
                 info["converged"] = int(flag.item()) == 0
             if info["converged"]:
+                self._detach_plan()                  # the image is done: later frames are plain ones
                 break
+            if adaptive:
+                plan = self.adaptive.select(error, threshold=threshold, max_repeat=max_repeat, uniform_every=uniform_every)
+                self._attach_plan(self.adaptive)
+                self._planned = True
+        if plan is not None:
+            info["plan"] = plan
         info["frames"] = ran
         return info
 

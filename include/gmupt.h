@@ -1038,6 +1038,12 @@ int gmupt_converge_read_state(gmupt_converge* c, gmupt_converge_pixel* dst, size
 int gmupt_render_until(gmupt_renderer* r, gmupt_camera* camera, gmupt_converge* c, const gmupt_converge_params* params /* may be NULL */,
                        uint32_t check_every, uint32_t max_iterations, uint32_t* iters /* may be NULL */, gmupt_converge_info* info);
 
+/* ---- Adaptive sampling (an extension): new camera paths go where the convergence monitor's error still is.  Its rule, structures
+ * and functions are declared in include/gmupt_adaptive.h, which includes this file.  Opt-in everywhere: without a sampling plan
+ * attached to a renderer an iteration launches exactly what it launched before, and no kernel of the renderer is changed.
+ * The AOV, denoiser, temporal and infill stages need no change under a plan: they read the per-pixel running mean and count of the
+ * accumulation target, which stay valid under uneven counts. */
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);
