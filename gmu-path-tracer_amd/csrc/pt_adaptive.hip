@@ -23,7 +23,7 @@
 
 namespace gmupt {
 
-static_assert(kAdRun == 256 && kAdRun == (uint32_t)kBlock, "the block steps below are written for four waves of 64");
+static_assert(kSumRun == 256 && kSumRun == (uint32_t)kBlock, "the block steps below are written for four waves of 64");
 
 __device__ __forceinline__ AdPartial ad_shfl_down(const AdPartial& v, int s)
 {
@@ -36,17 +36,17 @@ __device__ __forceinline__ AdPartial ad_shfl_down(const AdPartial& v, int s)
 // the combination of the block's 256 entries, in thread 0
 __device__ __forceinline__ AdPartial ad_block_reduce(AdPartial v)
 {
-    __shared__ AdPartial sh[kAdRun / 64];
+    __shared__ AdPartial sh[kSumRun / 64];
     for (int s = 32; s > 0; s >>= 1) ad_combine(v, ad_shfl_down(v, s));
     if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = v;
     __syncthreads();
-    if (threadIdx.x == 0) for (uint32_t w = 1; w < kAdRun / 64; w++) ad_combine(v, sh[w]);
+    if (threadIdx.x == 0) for (uint32_t w = 1; w < kSumRun / 64; w++) ad_combine(v, sh[w]);
     return v;
 }
 
-__global__ __launch_bounds__(kAdRun) void k_ad_count(const float* __restrict__ error, size_t n, AdParams prm, AdPartial* __restrict__ out)
+__global__ __launch_bounds__(kSumRun) void k_ad_count(const float* __restrict__ error, size_t n, AdParams prm, AdPartial* __restrict__ out)
 {
-    const size_t i = (size_t)blockIdx.x * kAdRun + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * kSumRun + threadIdx.x;
     AdPartial v = ad_zero();
     if (i < n) { const float e = error[i]; v = ad_pixel(e, ad_rep(e, prm)); }
     v = ad_block_reduce(v);
@@ -68,7 +68,7 @@ __device__ __forceinline__ uint32_t ad_lane_prefix(uint32_t x, int bits, uint32_
 // the sum of x over the lower threads of the block (x < 2^bits); every thread of the block calls it
 __device__ __forceinline__ uint32_t ad_block_prefix(uint32_t x, int bits)
 {
-    __shared__ uint32_t s_wave[kAdRun / 64];
+    __shared__ uint32_t s_wave[kSumRun / 64];
     uint32_t tot;
     uint32_t pre = ad_lane_prefix(x, bits, &tot);
     if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = tot;
@@ -77,9 +77,9 @@ __device__ __forceinline__ uint32_t ad_block_prefix(uint32_t x, int bits)
     return pre;
 }
 
-__global__ __launch_bounds__(kAdRun) void k_ad_scan(const AdPartial* __restrict__ in, size_t n, uint32_t* __restrict__ offset, AdPartial* __restrict__ out)
+__global__ __launch_bounds__(kSumRun) void k_ad_scan(const AdPartial* __restrict__ in, size_t n, uint32_t* __restrict__ offset, AdPartial* __restrict__ out)
 {
-    const size_t i = (size_t)blockIdx.x * kAdRun + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * kSumRun + threadIdx.x;
     AdPartial v = ad_zero();
     if (i < n) v = in[i];
     const uint32_t pre = ad_block_prefix(v.entries, 29);        // a total is at most kAdMaxEntries = 2^28
@@ -88,9 +88,9 @@ __global__ __launch_bounds__(kAdRun) void k_ad_scan(const AdPartial* __restrict_
     if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
 
-__global__ __launch_bounds__(kAdRun) void k_ad_emit(const float* __restrict__ error, size_t n, AdParams prm, AdOffsets off, uint32_t* __restrict__ list, size_t cap)
+__global__ __launch_bounds__(kSumRun) void k_ad_emit(const float* __restrict__ error, size_t n, AdParams prm, AdOffsets off, uint32_t* __restrict__ list, size_t cap)
 {
-    const size_t i = (size_t)blockIdx.x * kAdRun + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * kSumRun + threadIdx.x;
     const uint32_t rep = i < n ? ad_rep(error[i], prm) : 0u;
     size_t at = ad_block_prefix(rep, 7);                         // rep <= kAdMaxRepeat = 64
     size_t run = blockIdx.x;
@@ -136,12 +136,12 @@ size_t adaptive_carve(void* base, size_t pixels, size_t cap, AdScratch* out)
     Scratch sc(base);
     AdScratch a{};
     a.list = sc.take<uint32_t>(cap);
-    size_t m = ad_runs(pixels);
+    size_t m = sum_runs(pixels);
     for (uint32_t l = 0; ; l++) {
         a.total[l] = sc.take<AdPartial>(m);
         if (l == kAdMaxLevels) break;
         a.offset[l] = sc.take<uint32_t>(m);
-        m = ad_runs(m);
+        m = sum_runs(m);
     }
     if (out) *out = a;
     return sc.used;
@@ -150,17 +150,17 @@ size_t adaptive_carve(void* base, size_t pixels, size_t cap, AdScratch* out)
 // enqueues count, the scan levels and emit; returns where the total of the image will be
 const AdPartial* launch_adaptive_select(const float* error, size_t n, const AdParams& prm, const AdScratch& sc, size_t cap, hipStream_t s)
 {
-    size_t m = ad_runs(n);
+    size_t m = sum_runs(n);
     const uint32_t runs = (uint32_t)m;
-    hipLaunchKernelGGL(k_ad_count, dim3(runs), dim3(kAdRun), 0, s, error, n, prm, sc.total[0]);
+    hipLaunchKernelGGL(k_ad_count, dim3(runs), dim3(kSumRun), 0, s, error, n, prm, sc.total[0]);
     AdOffsets off{};
     do {
-        const size_t next = ad_runs(m);
-        hipLaunchKernelGGL(k_ad_scan, dim3((uint32_t)next), dim3(kAdRun), 0, s, (const AdPartial*)sc.total[off.levels], m, sc.offset[off.levels], sc.total[off.levels + 1]);
+        const size_t next = sum_runs(m);
+        hipLaunchKernelGGL(k_ad_scan, dim3((uint32_t)next), dim3(kSumRun), 0, s, (const AdPartial*)sc.total[off.levels], m, sc.offset[off.levels], sc.total[off.levels + 1]);
         off.offset[off.levels] = sc.offset[off.levels];
         off.levels++; m = next;
     } while (m > 1);
-    hipLaunchKernelGGL(k_ad_emit, dim3(runs), dim3(kAdRun), 0, s, error, n, prm, off, sc.list, cap);
+    hipLaunchKernelGGL(k_ad_emit, dim3(runs), dim3(kSumRun), 0, s, error, n, prm, off, sc.list, cap);
     return sc.total[off.levels];
 }
 

@@ -7,10 +7,10 @@
 #include "../../include/gmupt_adaptive.h"
 #include "detmath.hpp"
 #include "pt_converge.hpp"     // cv_finite: the monitor's test for a finite error
+#include "pt_ordered_sum.hpp"  // kSumRun, sum_runs: pixels per run == threads per block, and the records of the level above
 
 namespace gmupt {
 
-constexpr uint32_t kAdRun = 256;                       // pixels per run == threads per block
 constexpr uint32_t kAdMaxRepeat = 64;
 constexpr uint64_t kAdMaxEntries = 1ull << 28;         // the largest list (1 GiB of pixel indices)
 constexpr uint32_t kAdMaxLevels = 3;                   // scan levels over the run totals: 2^32 pixels are 2^24 runs, 2^16, 2^8 totals
@@ -53,8 +53,6 @@ GM_HD uint32_t ad_pixel_of(const uint32_t* list, uint32_t count, uint32_t unifor
     if (uniformEvery != 0u && k % uniformEvery == 0u) return k % pixels;      // the reference's pixel, newPath.hlsl:33
     return list[k % count];
 }
-
-inline size_t ad_runs(size_t n) { return (n + kAdRun - 1) / kAdRun; }
 
 inline void ad_fill_info(const AdPartial& t, uint32_t pixels, gmupt_adaptive_info* info)
 {

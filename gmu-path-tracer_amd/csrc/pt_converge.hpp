@@ -3,15 +3,14 @@
 // pixel's error, what a pixel contributes to the summary, how two partial summaries combine and the step from the totals to the
 // public fields.  One copy, so that host and device run the same statements: binary64 except where the rule says binary32, nothing
 // contracted (build.py).  The ORDER in which the errors are summed -- runs of 256, stride halving, level by level, the one "Tree cost"
-// states -- is the other half of the rule; both callers follow it.
+// states -- is the other half of the rule: pt_ordered_sum.hpp, which both callers hand cv_zero and cv_combine to.
 #pragma once
 #include "pt_device.hpp"
 #include "detmath.hpp"
 #include "pt_denoise.hpp"      // dn_luminance: the one definition of the luminance
+#include "pt_ordered_sum.hpp"
 
 namespace gmupt {
-
-constexpr uint32_t kCvRun = 256;               // entries per run of the rule == threads per block
 
 // the state of one pixel in registers (the device keeps it as planes, the host as gmupt_converge_pixel records)
 struct CvState { uint32_t n, k, w; double s, mean, m2; };
@@ -88,9 +87,6 @@ inline void cv_fill_info(const CvPartial& t, uint32_t pixels, const CvParams& pr
     const uint32_t m = t.known - t.nonfinite;
     info->mean_error = m ? t.sumError / (double)m : 0.0;
 }
-
-// how many partials the level above `n` entries has
-inline size_t cv_runs(size_t n) { return (n + kCvRun - 1) / kCvRun; }
 
 // ---- host reference (pt_converge.cpp): the rule over n >= 1 pixels; error may be null
 CvPartial converge_host(gmupt_converge_pixel* state, const float* rgba, size_t n, const CvParams& prm, float* error);

@@ -1,14 +1,14 @@
 // The arithmetic of the tree cost (include/gmupt.h "Tree cost" states the rule), shared by gmupt_tree_cost_host (pt_treecost.cpp) and the
 // k_tc_* kernels (pt_treecost.hip): what one node record contributes, how two partial results combine, and the step from the totals to the
 // SAH.  One copy, so that host and device run the same binary64 statements; nothing is contracted (build.py).  The ORDER in which the
-// terms are combined -- runs of 256, stride halving, level by level -- is the other half of the rule; both callers follow it.
+// terms are combined -- runs of 256, stride halving, level by level -- is the other half of the rule: pt_ordered_sum.hpp, which both callers
+// hand tc_zero and tc_combine to.
 #pragma once
 #include "pt_device.hpp"
 #include "detmath.hpp"
+#include "pt_ordered_sum.hpp"
 
 namespace gmupt {
-
-constexpr uint32_t kTcRun = 256;               // entries per run of the rule == threads per block
 
 // What a node, a run, or the whole buffer amounts to.  rootHalfArea is the half area of the FIRST record the partial covers, so the one
 // partial that is left at the end carries that of record 0.  48 bytes: the records of the device scratch.
@@ -58,9 +58,6 @@ inline void tc_fill_info(const TcPartial& t, gmupt_tree_cost_info* info)
     info->root_half_area = t.rootHalfArea;
     info->sah = t.rootHalfArea > 0.0 ? (t.sumInner + t.sumLeaf) / t.rootHalfArea : 0.0;
 }
-
-// how many partials the level above `n` entries has
-inline size_t tc_runs(size_t n) { return (n + kTcRun - 1) / kTcRun; }
 
 // ---- host reference (pt_treecost.cpp): the rule over n >= 1 records; no device, no allocation the caller sees
 TcPartial tree_cost_host(const gmupt_bvh_node* nodes, uint32_t n, int threads);

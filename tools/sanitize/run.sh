@@ -15,8 +15,12 @@ g++ -std=c++17 -O1 -g -fsanitize=thread -ffp-contract=off -o "$BIN/gmupt_builder
 TSAN_OPTIONS="halt_on_error=1" $NORAND "$BIN/gmupt_builder_tsan" 20000
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_builder_asan" $SRC -lpthread
 ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_builder_asan" 20000
-# the host tree cost (csrc/pt_treecost.cpp): its headers are HIP headers, so the host side of hipcc compiles it; no device code is built or run
+# the ordered sum (csrc/pt_ordered_sum.hpp) on a partial that records the order, against the rule restated: its headers are HIP headers, so
+# the host side of hipcc compiles it; no device code is built or run
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
+"$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_ordered_sum_asan" ordered_sum_main.cpp -lpthread
+ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_ordered_sum_asan"
+# the host tree cost (csrc/pt_treecost.cpp), the same way
 "$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_treecost_asan" treecost_main.cpp ../../gmu-path-tracer_amd/csrc/pt_treecost.cpp -lpthread
 ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_treecost_asan"
 # the host treelet optimiser (csrc/pt_treeopt.cpp), the same way
