@@ -8,7 +8,8 @@ SYMBOLS), _lib (the loaded library, its only owner), _stage (what the rest share
 converge, mesh and accel, then core (Camera, Renderer), which imports the feature modules and is imported by none of them.
 
 adaptive (adaptive sampling) is the exception: it is reached as capi.adaptive.NAME and keeps its structures and prototypes itself, so
-that the names at this level, the Renderer class and SYMBOLS stay the recorded surface (tests/golden/capi_surface.json).
+that the names at this level, the Renderer class and SYMBOLS stay the recorded surface (tests/golden/capi_surface.json).  lens (the
+thin lens, capi.lens.NAME) follows it.
 """
 from ._abi import *  # noqa: F401,F403
 from ._lib import _check, _ptr, lib, use_build  # noqa: F401
@@ -23,3 +24,4 @@ from .accel import (Lbvh, TreeOptimizer, bvh_refit_host, lbvh_build_host, sbvh_b
                     tree_optimize_host, tree_sah, wide_tables_addressable)
 from .core import Camera, Renderer  # noqa: F401
 from . import adaptive  # noqa: F401,E402
+from . import lens  # noqa: F401,E402

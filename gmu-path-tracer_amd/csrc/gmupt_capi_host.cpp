@@ -438,6 +438,33 @@ extern "C" int gmupt_adaptive_pixel_host(const uint32_t* list, uint32_t count, u
     return GMUPT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ thin lens: parameters and the host rule (pt_lens.cpp, pt_lens.hpp)
+static_assert(sizeof(gmupt_lens) == 8 && offsetof(gmupt_lens, focus_distance) == 4, "gmupt_lens layout");
+
+extern "C" void gmupt_lens_default_params(gmupt_lens* lens)
+{
+    if (!lens) return;
+    lens->aperture_radius = 0.0f; lens->focus_distance = 1.0f;
+}
+
+int lens_params(const char* fn, const gmupt_lens* lens)
+{
+    if (!lens) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null lens", fn);
+    const float a = lens->aperture_radius, f = lens->focus_distance;
+    if (!(a >= 0.0f) || !cv_finite(a)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: aperture_radius = %g (finite and >= 0)", fn, (double)a);
+    if (a > 0.0f && (!(f > 0.0f) || !cv_finite(f))) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: focus_distance = %g (finite and > 0 while the aperture is open)", fn, (double)f);
+    return GMUPT_OK;
+}
+
+extern "C" int gmupt_lens_ray_host(const gmupt_camera_buffer* cam, const gmupt_lens* lens, uint32_t q, uint32_t cx, uint32_t cy, gmupt_ray* out)
+{
+    const char* fn = "gmupt_lens_ray_host";
+    if (!cam || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null camera or result", fn);
+    GMUPT_TRY(lens_params(fn, lens));
+    lens_ray_host(*cam, *lens, q, cx, cy, out);
+    return GMUPT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ pose: the host reference (pt_pose.cpp) of gmupt_pose_update
 extern "C" int gmupt_pose_host(const float* rest, uint32_t num_verts, const uint16_t* joints, const float* weights, uint32_t influences, const float* joint_mats,
                                uint32_t num_joints, const float* deltas, const float* target_weights, uint32_t num_targets, float* verts_out, uint32_t threads)

@@ -14,6 +14,7 @@
 #include "pt_pose.hpp"
 #include "pt_converge.hpp"
 #include "pt_adaptive.hpp"
+#include "pt_lens.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
@@ -148,6 +149,8 @@ struct gmupt_renderer {
     EventPair tcEv;
     // adaptive sampling (gmupt_renderer_set_adaptive): the attached plan, not owned; null = every iteration launches what it always did
     gmupt_adaptive* adaptive = nullptr;
+    // thin lens (gmupt_renderer_set_lens): aperture_radius 0 = none attached, every iteration launches what it always did
+    gmupt_lens lens{ 0.0f, 1.0f };
 
     __attribute__((visibility("default"))) ~gmupt_renderer() { if (stream) (void)hipStreamDestroy(stream); }   // gmupt_renderer_destroy has synchronised it; the library has always exported this symbol
     uint32_t tile_x0() const { return p.tileEnabled ? p.tileX0 : 0u; } uint32_t tile_y0() const { return p.tileEnabled ? p.tileY0 : 0u; }   // the origin of the rendered rectangle
@@ -225,6 +228,7 @@ int temporal_params(const char* fn, const gmupt_temporal_params* p, DnParams& dn
 int infill_params(const char* fn, const gmupt_infill_params* p, IfParams& out);
 int converge_params(const char* fn, const gmupt_converge_params* p, CvParams& out);
 int adaptive_params(const char* fn, const gmupt_adaptive_params* p, float monitorThreshold, AdParams& out);   // threshold 0 = monitorThreshold
+int lens_params(const char* fn, const gmupt_lens* lens);                                                         // the argument errors of include/gmupt_lens.h
 // gmupt_capi_denoise.hip: the chains behind the temporal entry points; infill == nullptr is the chain without the infill stage
 int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
                      const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,

@@ -95,6 +95,23 @@ Renderer::Pick Renderer::pick(float x, float y)
 	return p;
 }
 
+void Renderer::setLens(float apertureRadius, float focusDistance)
+{
+	const gmupt_lens lens{ apertureRadius, focusDistance };
+	check(gmupt_renderer_set_lens(mRenderer.get(), &lens));
+	mScene.mCamera.getBuffer()->iterationCounter = -1; // the samples so far were made with the old lens
+}
+
+gmupt_lens Renderer::focusAt(float x, float y, float apertureRadius)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	gmupt_lens lens{ apertureRadius, 1.f };
+	check(gmupt_lens_focus_at(mRenderer.get(), x, y, mScene.mCamera.getBuffer()->lightCount, &lens));
+	setLens(lens.aperture_radius, lens.focus_distance);
+	return lens;
+}
+
 gmupt_trace_info Renderer::renderAovs(gmupt_aov* deviceOut, size_t bytes, unsigned samples)
 {
 	bindScene();

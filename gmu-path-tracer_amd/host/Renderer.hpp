@@ -8,6 +8,7 @@
 #include <vector>
 #include "Scene.hpp"
 #include "../../include/gmupt_adaptive.h"
+#include "../../include/gmupt_lens.h"
 
 class Renderer
 {
@@ -46,6 +47,12 @@ public:
 	// and what it hits first, light spheres up to the camera's lightCount included
 	struct Pick { gmupt_ray ray; gmupt_hit hit; };
 	Pick pick(float x, float y);
+	// depth of field (include/gmupt_lens.h): a thin lens of radius `apertureRadius` focused at `focusDistance` along the camera's forward axis,
+	// attached to the renderer; apertureRadius == 0 detaches it.  focusAt focuses on what whole-frame pixel (x, y) of the current camera sees
+	// (gmupt_lens_focus_at; throws when it sees nothing) and returns the lens it attached.  Both restart the accumulation like a camera move;
+	// pick, the AOV planes and the temporal projection stay on the pinhole centre ray.
+	void setLens(float apertureRadius, float focusDistance);
+	gmupt_lens focusAt(float x, float y, float apertureRadius);
 	// AOV buffers of the current camera (gmupt_render_aovs): one gmupt_aov per pixel of targetSize(), row-major -- albedo / normal guide images
 	// for a denoiser, depth, position, ids.  samples 1..8: s*s stratified rays per pixel for the albedo and normal planes when > 1.
 	// The first form writes caller-owned device memory (16-byte aligned, bytes >= pixels * 64); the second returns the records on the host.

@@ -28,6 +28,10 @@
 //                [--tree-cost]                            the surface-area cost of the bound tree (Renderer::treeCost), once after bind and once more
 //                                                         after --vertices is applied: one JSON line each with the gmupt_tree_cost_info fields, the
 //                                                         doubles as hex bit patterns; not with --ranks
+//                [--aperture R --focus D | --focus-at X,Y] depth of field (Renderer::setLens / focusAt, include/gmupt_lens.h): a thin lens of radius R
+//                                                         (scene units, > 0) focused at distance D along the camera's forward axis, or on what
+//                                                         whole-frame pixel (X, Y) sees after one camera update; one JSON line with the lens, the
+//                                                         floats also as hex bit patterns; not with --ranks
 //                [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]
 //                                                         adaptive sampling in that loop (Renderer::renderAdaptive, include/gmupt_adaptive.h): the JSON
 //                                                         line gains active, entries, max_rep, skipped_nonfinite of the last plan and paths_generated
@@ -160,6 +164,7 @@ int main(int argc, char** argv)
 	std::string builder = "sbvh", dumpTree; unsigned leaf = 4, optimize = 0;
 	bool treeCost = false;
 	bool adaptive = false, maxRepeatGiven = false, uniformEveryGiven = false; unsigned maxRepeat = 1, uniformEvery = 0;
+	bool apertureGiven = false, focusGiven = false, focusAtGiven = false; float aperture = 0.f, focus = 0.f, focusX = 0.f, focusY = 0.f;
 	bool untilError = false, checkEveryGiven = false, allowPixelsGiven = false; float untilThreshold = 0.f; unsigned checkEvery = 8, allowPixels = 0; std::string errorMap;
 	for (int i = 1; i < argc; i++) {
 		const std::string a = argv[i];
@@ -203,6 +208,9 @@ int main(int argc, char** argv)
 		else if (a == "--adaptive") adaptive = true;
 		else if (a == "--max-repeat") { char* end = nullptr; const char* v = next(); maxRepeat = std::strtoul(v, &end, 10); maxRepeatGiven = true; if (end == v || *end || maxRepeat < 1 || maxRepeat > 64) { std::fprintf(stderr, "--max-repeat takes a number in 1..64\n"); return 2; } }
 		else if (a == "--uniform-every") { char* end = nullptr; const char* v = next(); uniformEvery = std::strtoul(v, &end, 10); uniformEveryGiven = true; if (end == v || *end) { std::fprintf(stderr, "--uniform-every takes a number of paths (0 = off)\n"); return 2; } }
+		else if (a == "--aperture") { char* end = nullptr; const char* v = next(); aperture = std::strtof(v, &end); apertureGiven = true; if (end == v || *end || !(aperture > 0.f) || aperture > std::numeric_limits<float>::max()) { std::fprintf(stderr, "--aperture takes a finite radius > 0\n"); return 2; } }
+		else if (a == "--focus") { char* end = nullptr; const char* v = next(); focus = std::strtof(v, &end); focusGiven = true; if (end == v || *end || !(focus > 0.f) || focus > std::numeric_limits<float>::max()) { std::fprintf(stderr, "--focus takes a finite distance > 0\n"); return 2; } }
+		else if (a == "--focus-at") { if (std::sscanf(next(), "%f,%f", &focusX, &focusY) != 2) { std::fprintf(stderr, "--focus-at takes a pixel X,Y\n"); return 2; } focusAtGiven = true; }
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -223,6 +231,9 @@ int main(int argc, char** argv)
 			            "                                 (default 8) the per-pixel standard error of the tone-mapped luminance mean is estimated; ends when all but M pixels\n"
 			            "                                 (default 0) are at or below T, or after --frames; one JSON line with the last check's info and the iterations run,\n"
 			            "                                 floats as hex bit patterns; FILE.pfm (Pf): the error per pixel, -1 = unknown; not with --ranks\n"
+			            "             [--aperture R --focus D | --focus-at X,Y]   depth of field: a thin lens of radius R > 0 (scene units) focused at distance D along the\n"
+			            "                                 forward axis, or on what whole-frame pixel (X, Y) sees after one camera update; one JSON line with the lens;\n"
+			            "                                 picks, AOVs and previews stay on the pinhole centre ray; not with --ranks\n"
 			            "             [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]   adaptive sampling: after every check that does not end the loop\n"
 			            "                                 the new camera paths go to the pixels still above T, up to N (default 1, at most 64) list entries each,\n"
 			            "                                 every N-th path (default 0 = none) to the pixel it would have gone to anyway; T must be > 0; the JSON line\n"
@@ -333,6 +344,10 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--max-repeat and --uniform-every belong to adaptive sampling: they need --adaptive");
 		if (adaptive && (!untilError || !(untilThreshold > 0.f) || untilThreshold > std::numeric_limits<float>::max()))
 			throw std::invalid_argument("--adaptive plans from the convergence loop: it needs --until-error T with a finite T > 0");
+		if (apertureGiven ? (focusGiven == focusAtGiven) : (focusGiven || focusAtGiven))
+			throw std::invalid_argument("--aperture R opens a lens focused by exactly one of --focus D and --focus-at X,Y, which need it");
+		if (apertureGiven && ranks > 1)
+			throw std::invalid_argument("--aperture sets the lens of a single process: it cannot be combined with --ranks N > 1");
 		if (untilError && ranks > 1)
 			throw std::invalid_argument("--until-error judges the frame of a single process: it cannot be combined with --ranks N > 1");
 		if (treeCost && ranks > 1)
@@ -399,6 +414,13 @@ int main(int argc, char** argv)
 			if (optimize)
 				std::printf("{\"optimize\": {\"passes\": %u, \"num_nodes\": %u, \"depth_before\": %u, \"depth_after\": %u, \"treelets_rewritten\": %u, \"cost_before\": %.17g, \"cost_after\": %.17g, \"ms\": %.6g}}\n",
 				            optimize, oinfo.num_nodes, oinfo.depth_before, oinfo.depth_after, oinfo.treelets_rewritten, oinfo.cost_before, oinfo.cost_after, oinfo.ms);
+		}
+		if (apertureGiven) {   // after whatever moved or rebuilt the geometry: --focus-at picks in the scene the frames will see
+			gmupt_lens lens{ aperture, focus };
+			if (focusAtGiven) { renderer.update(0.f); lens = renderer.focusAt(focusX, focusY, aperture); }
+			else renderer.setLens(aperture, focus);
+			unsigned ab, fb; std::memcpy(&ab, &lens.aperture_radius, 4); std::memcpy(&fb, &lens.focus_distance, 4);
+			std::printf("{\"lens\": {\"aperture_radius\": %.9g, \"focus_distance\": %.9g, \"aperture_bits\": \"%08x\", \"focus_bits\": \"%08x\"}}\n", lens.aperture_radius, lens.focus_distance, ab, fb);
 		}
 		if (untilError) {
 			gmupt_converge_params cp; gmupt_converge_default_params(&cp);

@@ -51,6 +51,27 @@ class ProgressiveSession:
             self.temporal.reset()                    # the history was lit by the old lights
         self._reset_converge()
 
+    def set_lens(self, aperture, focus=None, focus_at=None):
+        """Depth of field (capi.lens, include/gmupt_lens.h): from the next frame on every fresh camera path starts on a disk of radius
+        `aperture` (scene units) around the camera position and aims through its pinhole ray's point on the focal plane; aperture 0
+        detaches the lens.  The plane is `focus` (its distance along the camera's forward axis) or, with focus_at=(px, py), the depth
+        of what that whole-frame pixel sees under the camera of the frame just drawn (GmuptError when it sees nothing); exactly one
+        of the two with an aperture > 0.  The accumulation restarts like after a camera move: the temporal history stays and is
+        reprojected as usual (pick, the AOV planes and the projection stay on the pinhole centre ray).  Returns the capi.lens.Lens."""
+        from .capi import lens as L
+        if aperture > 0 and (focus is None) == (focus_at is None):
+            raise ValueError("set_lens: an open aperture takes either focus=distance or focus_at=(px, py)")
+        if aperture > 0 and focus_at is not None:
+            lens = L.focus_at(self.renderer, focus_at[0], focus_at[1], int(self.camera.buffer.lightCount), aperture_radius=aperture)
+        elif focus is not None:
+            lens = L.lens_params(aperture_radius=aperture, focus_distance=focus)
+        else:
+            lens = L.lens_params(aperture_radius=aperture)
+        L.set_lens(self.renderer, lens)
+        self.camera.reset_accumulation()
+        self._reset_converge()                       # the batches seen so far are of the old lens
+        return lens
+
     def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False, indices=None, rebuild_above=None, optimize=0):
         """The geometry moved (same vertex count, same triangles): upload the vertices, and `normals` (when given) into the property
         records, refit the tree and the renderer's traversal tables on the GPU (gmupt_renderer_refit), restart the accumulation.  The

@@ -1044,6 +1044,12 @@ int gmupt_render_until(gmupt_renderer* r, gmupt_camera* camera, gmupt_converge* 
  * The AOV, denoiser, temporal and infill stages need no change under a plan: they read the per-pixel running mean and count of the
  * accumulation target, which stay valid under uneven counts. */
 
+/* ---- Lens (an extension): depth of field.  A thin lens attached to a renderer moves the origin of every fresh camera path onto a disk
+ * around the camera position and aims it through the focal plane, in one extra launch after the shading stage.  Its rule, structure and
+ * functions are declared in include/gmupt_lens.h, which includes this file.  Opt-in everywhere: without a lens, or at aperture 0, an
+ * iteration launches exactly what it launched before.  gmupt_pick, gmupt_camera_pick_ray, the AOV rays, the motion plane and the
+ * temporal projection stay on the pinhole centre ray. */
+
 /* ---- test / debug access (reference path-state layout, structs.h:19-48) ---- */
 int gmupt_debug_read_path_state(gmupt_renderer* r, void* dst, size_t bytes);        /* 248 * pool_paths */
 int gmupt_debug_write_path_state(gmupt_renderer* r, const void* src, size_t bytes);
