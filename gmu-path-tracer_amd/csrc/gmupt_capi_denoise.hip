@@ -25,7 +25,7 @@ extern "C" int gmupt_denoise_image(gmupt_renderer* r, const float* beauty_rgba, 
 
 // What the render_denoised* chains check once they have a renderer, in this order: the output, the caller's parameters (`params`, which
 // has called fail() itself), then what gmupt_render_aovs would refuse, before the scratch is grown for it.  Leaves the device set.
-template <class P> static int render_args(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const float* out_rgba, size_t bytes, const P& params)
+template <class P> static int render_args(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const float* out_rgba, size_t bytes, const P& params, bool centre = true)
 {
     const uint32_t W = r->p.fbW, H = r->p.fbH;
     if (!out_rgba || ((uintptr_t)out_rgba & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned output (16 bytes)", fn);
@@ -33,27 +33,29 @@ template <class P> static int render_args(const char* fn, gmupt_renderer* r, uin
     GMUPT_TRY(params());
     if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
     if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "%s: no camera set", fn);
-    GMUPT_TRY(aov_sample_plan(fn, "aov_samples", W, aov_samples, nullptr));
+    GMUPT_TRY(aov_sample_plan(fn, "aov_samples", W, aov_samples, nullptr, centre));
     GMUPT_TRY(query_supported(r, fn));
     HIP_TRY(hipSetDevice(r->dev->id));
     return GMUPT_OK;
 }
 
-// gmupt_render_denoised; with `infill` gmupt_render_preview without a history: the infill stage between the framebuffer copy and the filter
+// gmupt_render_denoised; with `infill` gmupt_render_preview without a history: the infill stage between the framebuffer copy and the filter;
+// with `lensGuides` gmupt_render_denoised_lens: the records are those of gmupt_render_aovs_lens under that (checked) lens
 int render_denoised(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, const IfParams* infill, float* out_rgba, size_t bytes,
-                    gmupt_trace_info* info)
+                    gmupt_trace_info* info, const gmupt_lens* lensGuides)
 {
     if (info) std::memset(info, 0, sizeof(*info));
     if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer", fn);
     const uint32_t W = r->p.fbW, H = r->p.fbH;
     DnParams prm;
-    GMUPT_TRY(render_args(fn, r, aov_samples, out_rgba, bytes, [&] { return denoise_params(fn, p, prm); }));
+    GMUPT_TRY(render_args(fn, r, aov_samples, out_rgba, bytes, [&] { return denoise_params(fn, p, prm); }, !lensGuides));
     GMUPT_TRY(r->dnInput.grow(r->stream, (size_t)W * H * (sizeof(gmupt_aov) + 16)));
     if (infill) GMUPT_TRY(r->ifImage.grow(r->stream, (size_t)W * H * 16));
     gmupt_aov* aov = r->dnInput.as<gmupt_aov>();
     const float* beauty = reinterpret_cast<float*>(r->dnInput.as<char>() + (size_t)W * H * sizeof(gmupt_aov));
     gmupt_trace_info ai;
-    int rc = gmupt_render_aovs(r, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai);
+    int rc = lensGuides ? render_aovs_lens(fn, r, *lensGuides, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai)
+                        : gmupt_render_aovs(r, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai);
     if (info) *info = ai;
     if (rc != GMUPT_OK) return rc;
     GMUPT_TRY(gmupt_copy_framebuffer_to_device(r, const_cast<float*>(beauty), (size_t)W * H * 16));

@@ -19,7 +19,7 @@ int query_supported(gmupt_renderer* r, const char* fn)
 }
 
 // the query's own work counters and statistics, on first use
-static int query_buffers(gmupt_renderer* r)
+int query_buffers(gmupt_renderer* r)
 {
     HIP_TRY(hipSetDevice(r->dev->id));
     if (r->queryStats.ptr) return GMUPT_OK;
@@ -29,7 +29,7 @@ static int query_buffers(gmupt_renderer* r)
 
 // One timed span of cast queries on the renderer's stream, behind whatever the renderer has queued: *q is the kernel argument of its
 // launches, with the query's counters and statistics (the renderer's are left alone).  Zeroes the statistics, records the first event.
-static int query_begin(gmupt_renderer* r, RenderParams* q)
+int query_begin(gmupt_renderer* r, RenderParams* q)
 {
     *q = r->p;
     q->travCounters = r->queryCounters.as<uint32_t>(); q->stats = r->queryStats.as<DevStats>();
@@ -38,7 +38,7 @@ static int query_begin(gmupt_renderer* r, RenderParams* q)
 }
 
 // Records the second event, waits for the span and fills *info; a launch that flagged its `what` (results, records) as invalid is fn's error.
-static int query_end(gmupt_renderer* r, const char* fn, const char* what, gmupt_trace_info* info)
+int query_end(gmupt_renderer* r, const char* fn, const char* what, gmupt_trace_info* info)
 {
     GMUPT_TRY(r->queryEv.stop(r->stream));
     DevStats ds;
@@ -121,6 +121,15 @@ extern "C" int gmupt_aov_ray(const gmupt_camera_buffer* cam, uint32_t x, uint32_
     return gmupt_camera_pick_ray(cam, px, py, out);
 }
 
+int aov_chunk_scratch(gmupt_renderer* r)
+{
+    if (!r->aovHits.ptr) {
+        GMUPT_TRY(r->aovRays.alloc((size_t)GMUPT_AOV_CHUNK_RAYS * sizeof(gmupt_ray), 0, r->stream));
+        GMUPT_TRY(r->aovHits.alloc((size_t)GMUPT_AOV_CHUNK_RAYS * sizeof(gmupt_hit), 0, r->stream));
+    }
+    return GMUPT_OK;
+}
+
 // gmupt_render_aovs, and with motion != nullptr gmupt_render_aovs_motion: k_mv_resolve follows k_aov_resolve on every chunk's hits
 static int render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info, const float* prevVerts, gmupt_motion* motion)
 {
@@ -134,10 +143,7 @@ static int render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size
     if (bytes < (size_t)W * H * sizeof(gmupt_aov)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: %zu bytes for %ux%u records of 64 bytes", bytes, W, H);
     GMUPT_TRY(query_supported(r, "gmupt_render_aovs"));
     GMUPT_TRY(query_buffers(r));
-    if (!r->aovHits.ptr) {
-        GMUPT_TRY(r->aovRays.alloc((size_t)GMUPT_AOV_CHUNK_RAYS * sizeof(gmupt_ray), 0, r->stream));
-        GMUPT_TRY(r->aovHits.alloc((size_t)GMUPT_AOV_CHUNK_RAYS * sizeof(gmupt_hit), 0, r->stream));
-    }
+    GMUPT_TRY(aov_chunk_scratch(r));
     const RenderParams& p = r->p;
     gmupt_ray* rays = r->aovRays.as<gmupt_ray>(); gmupt_hit* hits = r->aovHits.as<gmupt_hit>();
     const uint32_t rowsPerChunk = GMUPT_AOV_CHUNK_RAYS / (W * R);

@@ -15,6 +15,7 @@
 #include "pt_converge.hpp"
 #include "pt_adaptive.hpp"
 #include "pt_lens.hpp"
+#include "pt_lens_aov.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
@@ -222,6 +223,10 @@ size_t kind_stride(gmupt_buffer_kind k);                                        
 gmupt_buffer* buffer_alloc(gmupt_device* dev, gmupt_buffer_kind kind, size_t elems, size_t bytes, hipError_t* e);
 int build_traversal_copy(gmupt_renderer* r, const gmupt_buffer* nodesB, const gmupt_buffer* trisB, const gmupt_buffer* vertsB);   // gmupt_capi_accel.hip
 int query_supported(gmupt_renderer* r, const char* fn);                                                         // gmupt_capi_query.hip
+int query_buffers(gmupt_renderer* r);                                                                           // one timed span of cast queries on the query's own counters and statistics
+int query_begin(gmupt_renderer* r, RenderParams* q);
+int query_end(gmupt_renderer* r, const char* fn, const char* what, gmupt_trace_info* info);
+int aov_chunk_scratch(gmupt_renderer* r);                                                                       // the rays and hits of one AOV chunk, on first use
 int denoise_params(const char* fn, const gmupt_denoise_params* p, DnParams& out);                               // gmupt_capi_host.cpp
 int image_args(const char* fn, const void* beauty, const void* aov, uint32_t W, uint32_t H, const void* out, size_t bytes, bool device);
 int temporal_params(const char* fn, const gmupt_temporal_params* p, DnParams& dn, TpParams& tp);
@@ -234,7 +239,9 @@ int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba
                      const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
                      const gmupt_temporal_params* p, const IfParams* infill, float* out_rgba, size_t out_bytes, float* ms);
 int render_denoised(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, const IfParams* infill, float* out_rgba, size_t bytes,
-                    gmupt_trace_info* info);
+                    gmupt_trace_info* info, const gmupt_lens* lensGuides = nullptr);   // lensGuides: the records of gmupt_render_aovs_lens under that lens
+// gmupt_capi_lens_aov.hip: gmupt_render_aovs_lens under a checked lens, with fn as the name in its errors
+int render_aovs_lens(const char* fn, gmupt_renderer* r, const gmupt_lens& lens, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info);
 int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
                              const IfParams* infill, float* out_rgba, size_t bytes, gmupt_trace_info* info);
 // gmupt_capi_infill.hip: grows the renderer's infill scratch for the image (the one place that does) and enqueues the stage
@@ -257,11 +264,12 @@ inline uint32_t cast_fault_flags(const DevStats& ds)
 }
 
 // The rays per pixel of an AOV sample plan in *R (if asked for), or what gmupt_render_aovs refuses: `what` is the caller's name for
-// `samples`, W the width of a row (a chunk of GMUPT_AOV_CHUNK_RAYS rays holds whole rows; 0 where there is no row)
-inline int aov_sample_plan(const char* fn, const char* what, uint32_t W, uint32_t samples, uint32_t* R)
+// `samples`, W the width of a row (a chunk of GMUPT_AOV_CHUNK_RAYS rays holds whole rows; 0 where there is no row).  centre = false:
+// the plan of the lens records (include/gmupt_lens_aov.h), s*s rays and no centre ray
+inline int aov_sample_plan(const char* fn, const char* what, uint32_t W, uint32_t samples, uint32_t* R, bool centre = true)
 {
     if (samples < 1 || samples > GMUPT_AOV_MAX_SAMPLES) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %s = %u (1..%d)", fn, what, samples, GMUPT_AOV_MAX_SAMPLES);
-    const uint32_t n = samples == 1 ? 1u : samples * samples + 1u;
+    const uint32_t n = !centre ? samples * samples : samples == 1 ? 1u : samples * samples + 1u;
     if ((uint64_t)W * n > GMUPT_AOV_CHUNK_RAYS) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: one row of %u pixels is %u rays at %s = %u (at most 2^21)", fn, W, W * n, what, samples);
     if (R) *R = n;
     return GMUPT_OK;

@@ -136,6 +136,54 @@ std::vector<gmupt_aov> Renderer::renderAovs(unsigned samples)
 	return out;
 }
 
+gmupt_trace_info Renderer::renderAovsLens(gmupt_aov* deviceOut, size_t bytes, unsigned samples)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	gmupt_trace_info info{};
+	check(gmupt_render_aovs_lens(mRenderer.get(), nullptr, samples, deviceOut, bytes, &info));
+	return info;
+}
+
+std::vector<gmupt_aov> Renderer::renderAovsLens(unsigned samples)
+{
+	const Resolution t = targetSize();
+	std::vector<gmupt_aov> out(static_cast<size_t>(t.first) * t.second);
+	const size_t bytes = out.size() * sizeof(gmupt_aov);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("renderAovsLens: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { renderAovsLens(static_cast<gmupt_aov*>(d), bytes, samples); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error("renderAovsLens: cannot read the records back");
+	return out;
+}
+
+gmupt_trace_info Renderer::denoiseLens(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_denoise_params* params)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	gmupt_trace_info info{};
+	check(gmupt_render_denoised_lens(mRenderer.get(), nullptr, aovSamples, params, deviceOut, bytes, &info));
+	return info;
+}
+
+std::vector<float> Renderer::denoiseLens(unsigned aovSamples, const gmupt_denoise_params* params)
+{
+	const Resolution t = targetSize();
+	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
+	const size_t bytes = out.size() * sizeof(float);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoiseLens: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { denoiseLens(static_cast<float*>(d), bytes, aovSamples, params); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error("denoiseLens: cannot read the image back");
+	return out;
+}
+
 gmupt_trace_info Renderer::denoise(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_denoise_params* params)
 {
 	bindScene();

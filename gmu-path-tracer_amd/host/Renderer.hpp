@@ -9,6 +9,7 @@
 #include "Scene.hpp"
 #include "../../include/gmupt_adaptive.h"
 #include "../../include/gmupt_lens.h"
+#include "../../include/gmupt_lens_aov.h"
 
 class Renderer
 {
@@ -58,6 +59,13 @@ public:
 	// The first form writes caller-owned device memory (16-byte aligned, bytes >= pixels * 64); the second returns the records on the host.
 	gmupt_trace_info renderAovs(gmupt_aov* deviceOut, size_t bytes, unsigned samples = 1);
 	std::vector<gmupt_aov> renderAovs(unsigned samples = 1);
+	// the same records seen through the attached lens (gmupt_render_aovs_lens, include/gmupt_lens_aov.h): samples * samples rays per pixel,
+	// each pixel-filter cell through its own lens stratum, so that the planes are blurred where the beauty is; without a lens, a pinhole's.
+	// denoiseLens is denoise() guided by these records (gmupt_render_denoised_lens).  The forms as renderAovs() and denoise().
+	gmupt_trace_info renderAovsLens(gmupt_aov* deviceOut, size_t bytes, unsigned samples = 1);
+	std::vector<gmupt_aov> renderAovsLens(unsigned samples = 1);
+	gmupt_trace_info denoiseLens(float* deviceOut, size_t bytes, unsigned aovSamples = 1, const gmupt_denoise_params* params = nullptr);
+	std::vector<float> denoiseLens(unsigned aovSamples = 1, const gmupt_denoise_params* params = nullptr);
 	// the a-trous denoiser on the current frame (gmupt_render_denoised): AOVs of the current camera at aovSamples, then the filter over
 	// targetSize(); RGBA32F, rgb denoised, a = the frame's sample-count bits.  params == nullptr: gmupt_denoise_default_params.
 	// The first form writes caller-owned device memory (16-byte aligned, bytes >= pixels * 16); the second returns the texels on the host.

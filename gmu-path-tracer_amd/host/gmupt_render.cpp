@@ -32,6 +32,8 @@
 //                                                         (scene units, > 0) focused at distance D along the camera's forward axis, or on what
 //                                                         whole-frame pixel (X, Y) sees after one camera update; one JSON line with the lens, the
 //                                                         floats also as hex bit patterns; not with --ranks
+//                [--lens-guides]                          with --aperture: --denoise and --aov use the lens-filtered records (Renderer::denoiseLens /
+//                                                         renderAovsLens, include/gmupt_lens_aov.h), S*S rays per pixel through the lens; not with --infill
 //                [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]
 //                                                         adaptive sampling in that loop (Renderer::renderAdaptive, include/gmupt_adaptive.h): the JSON
 //                                                         line gains active, entries, max_rep, skipped_nonfinite of the last plan and paths_generated
@@ -164,6 +166,7 @@ int main(int argc, char** argv)
 	std::string builder = "sbvh", dumpTree; unsigned leaf = 4, optimize = 0;
 	bool treeCost = false;
 	bool adaptive = false, maxRepeatGiven = false, uniformEveryGiven = false; unsigned maxRepeat = 1, uniformEvery = 0;
+	bool lensGuides = false;
 	bool apertureGiven = false, focusGiven = false, focusAtGiven = false; float aperture = 0.f, focus = 0.f, focusX = 0.f, focusY = 0.f;
 	bool untilError = false, checkEveryGiven = false, allowPixelsGiven = false; float untilThreshold = 0.f; unsigned checkEvery = 8, allowPixels = 0; std::string errorMap;
 	for (int i = 1; i < argc; i++) {
@@ -211,6 +214,7 @@ int main(int argc, char** argv)
 		else if (a == "--aperture") { char* end = nullptr; const char* v = next(); aperture = std::strtof(v, &end); apertureGiven = true; if (end == v || *end || !(aperture > 0.f) || aperture > std::numeric_limits<float>::max()) { std::fprintf(stderr, "--aperture takes a finite radius > 0\n"); return 2; } }
 		else if (a == "--focus") { char* end = nullptr; const char* v = next(); focus = std::strtof(v, &end); focusGiven = true; if (end == v || *end || !(focus > 0.f) || focus > std::numeric_limits<float>::max()) { std::fprintf(stderr, "--focus takes a finite distance > 0\n"); return 2; } }
 		else if (a == "--focus-at") { if (std::sscanf(next(), "%f,%f", &focusX, &focusY) != 2) { std::fprintf(stderr, "--focus-at takes a pixel X,Y\n"); return 2; } focusAtGiven = true; }
+		else if (a == "--lens-guides") lensGuides = true;
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -234,6 +238,8 @@ int main(int argc, char** argv)
 			            "             [--aperture R --focus D | --focus-at X,Y]   depth of field: a thin lens of radius R > 0 (scene units) focused at distance D along the\n"
 			            "                                 forward axis, or on what whole-frame pixel (X, Y) sees after one camera update; one JSON line with the lens;\n"
 			            "                                 picks, AOVs and previews stay on the pinhole centre ray; not with --ranks\n"
+			            "             [--lens-guides]     with --aperture: --denoise and --aov use the lens-filtered AOV records (S*S rays per pixel through the lens),\n"
+			            "                                 so that the guides are blurred where the frame is; not with --infill\n"
 			            "             [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]   adaptive sampling: after every check that does not end the loop\n"
 			            "                                 the new camera paths go to the pixels still above T, up to N (default 1, at most 64) list entries each,\n"
 			            "                                 every N-th path (default 0 = none) to the pixel it would have gone to anyway; T must be > 0; the JSON line\n"
@@ -346,6 +352,10 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--adaptive plans from the convergence loop: it needs --until-error T with a finite T > 0");
 		if (apertureGiven ? (focusGiven == focusAtGiven) : (focusGiven || focusAtGiven))
 			throw std::invalid_argument("--aperture R opens a lens focused by exactly one of --focus D and --focus-at X,Y, which need it");
+		if (lensGuides && !apertureGiven)
+			throw std::invalid_argument("--lens-guides filters the guide records through the lens: it needs --aperture R");
+		if (lensGuides && infill)
+			throw std::invalid_argument("--lens-guides guides --denoise and --aov: it cannot be combined with --infill");
 		if (apertureGiven && ranks > 1)
 			throw std::invalid_argument("--aperture sets the lens of a single process: it cannot be combined with --ranks N > 1");
 		if (untilError && ranks > 1)
@@ -464,7 +474,7 @@ int main(int argc, char** argv)
 			if (found) std::printf(", \"point\": [%.9g, %.9g, %.9g]}\n", pt[0], pt[1], pt[2]); else std::printf(", \"point\": null}\n");
 		}
 		if (!aovPrefix.empty()) {
-			const std::vector<gmupt_aov> aov = renderer.renderAovs(aovSamples);
+			const std::vector<gmupt_aov> aov = lensGuides ? renderer.renderAovsLens(aovSamples) : renderer.renderAovs(aovSamples);
 			writeAovPfm(aovPrefix + "_albedo.pfm", aov, w, h, offsetof(gmupt_aov, albedo), 3);
 			writeAovPfm(aovPrefix + "_normal.pfm", aov, w, h, offsetof(gmupt_aov, normal), 3);
 			writeAovPfm(aovPrefix + "_depth.pfm", aov, w, h, offsetof(gmupt_aov, depth), 1);
@@ -475,7 +485,7 @@ int main(int argc, char** argv)
 		}
 		if (!denoisePrefix.empty()) {
 			gmupt_infill_params ip; gmupt_infill_default_params(&ip);
-			const std::vector<float> img = infill ? renderer.preview(false, false, aovSamples, nullptr, &ip) : renderer.denoise(aovSamples);
+			const std::vector<float> img = infill ? renderer.preview(false, false, aovSamples, nullptr, &ip) : lensGuides ? renderer.denoiseLens(aovSamples) : renderer.denoise(aovSamples);
 			writePfmFile(denoisePrefix + ".pfm", img, w, h);
 			std::vector<unsigned char> png(img.size());
 			for (size_t i = 0; i < img.size(); i += 4) // Renderer::captureScreen's conversion: float * 255 truncated, alpha 255

@@ -37,6 +37,8 @@ class ProgressiveSession:
         self._indices = None   # the index list of the last rebuild()
         self.normals = None    # the capi.Normals of set_vertices(normals="smooth"), created on first use, dropped by rebuild()
         self.baseline = None   # the tree cost (sah) that set_vertices(rebuild_above=...) compares a refitted tree with; rebuild() forgets it
+        self._epoch = 0        # accumulations started (a frame that cleared the target, a resize): what denoised_temporal(lens_guides=True) folds its history by
+        self._guided_epoch = None   # the epoch of its last call
 
     # ---- events (applied before the next frame, like the GUI callbacks of the reference)
     def move_camera(self, mouse_dx=0.0, mouse_dy=0.0, w=False, s=False, a=False, d=False):
@@ -276,6 +278,7 @@ class ProgressiveSession:
         self.width, self.height = width, height
         self.renderer.resize(width, rows if rows is not None else height)
         self.camera.update_resolution(width, height)
+        self._epoch += 1
         self._reset_converge()
 
     def pick(self, px, py):
@@ -297,26 +300,61 @@ class ProgressiveSession:
         from . import capi
         return capi.aov_fields(self.renderer.aovs(samples))
 
-    def denoised(self, aov_samples=1, infill=False, **params):
+    def _guide_lens(self, lens_guides):
+        """The renderer's attached lens when lens guides are asked for and one is attached, else None (the pinhole records)."""
+        if not lens_guides:
+            return None
+        from .capi import lens as L
+        lens = L.get_lens(self.renderer)
+        return lens if lens.aperture_radius > 0 else None
+
+    def denoised(self, aov_samples=1, infill=False, lens_guides=False, **params):
         """A clean preview of the session's current frame: capi.Renderer.denoise (gmupt_render_denoised) as an (H, W, 4) float32 numpy
         array -- rgb denoised, alpha the sample-count bits -- so to_rgba8 and the frame writers take it as they take a preview.  On a
         tile renderer it is this rank's tile, denoised on its own (tile edges are image edges).  params: the gmupt_denoise_params fields.
         infill: True, or a dict of capi.infill_params fields -- surface pixels without a sample take a colour from the sampled pixels of
-        their surface before the filter runs (capi.Renderer.preview, gmupt_render_preview); False keeps today's bits."""
+        their surface before the filter runs (capi.Renderer.preview, gmupt_render_preview); False keeps today's bits.
+        lens_guides: True with a lens attached (set_lens) -- the guide records are the lens-filtered ones (capi.lens_aov,
+        include/gmupt_lens_aov.h: aov_samples^2 rays per pixel through the lens), so that out-of-focus silhouettes are filtered like
+        the beauty shows them; without a lens, or False (the default), the pinhole records and today's bits."""
+        lens = self._guide_lens(lens_guides)
+        if lens is not None:
+            from . import capi
+            if infill is None or infill is False:
+                return capi.lens_aov.denoise(self.renderer, aov_samples, **params).cpu().numpy()
+            beauty, aov = capi.lens_aov.guided_inputs(self.renderer, aov_samples)
+            filled = capi.infill_image(self.renderer, beauty, aov, **(infill if isinstance(infill, dict) else {}))
+            return capi.denoise_image(self.renderer, filled, aov, **params).cpu().numpy()
         if infill is not None and infill is not False:
             return self.renderer.preview(aov_samples=aov_samples, infill=infill, **params).cpu().numpy()
         return self.renderer.denoise(aov_samples, **params).cpu().numpy()
 
-    def denoised_temporal(self, aov_samples=1, infill=False, **params):
+    def denoised_temporal(self, aov_samples=1, infill=False, lens_guides=False, **params):
         """A preview that survives camera motion: capi.Renderer.denoise_temporal (gmupt_render_denoised_temporal) with a history handle the
         session owns, as an (H, W, 4) float32 numpy array -- rgb denoised, alpha the effective sample-count bits.  Pixels the new
         accumulation has not reached yet show the reprojected history of the frames before the restart.  set_lights drops the history;
         resize keeps it.  On a tile renderer each rank keeps its own tile's history.  params: the capi.temporal_params fields.
         infill: as denoised() -- the pixels without a sample that have no consistent history either (first frame, light edit,
-        disocclusion) are filled after the integration; filled colour never enters the history.  False keeps today's bits."""
+        disocclusion) are filled after the integration; filled colour never enters the history.  False keeps today's bits.
+        lens_guides: as denoised() -- with a lens attached the lens records and a copy of the frame go through
+        capi.temporal_denoise_image (gmupt_temporal_denoise_image) on the same handle; the history folds when a frame of this session
+        has cleared the target, or a resize happened, since the last such call.  The projection reprojects the record's position, with
+        lens records a mean over the surface samples, and the motion plane stays a pinhole's and is not used on this path; one
+        history should be fed by one kind of record."""
         if self.temporal is None:
             from . import capi
             self.temporal = capi.Temporal(self.renderer)
+        lens = self._guide_lens(lens_guides)
+        if lens is not None:
+            from . import capi
+            beauty, aov = capi.lens_aov.guided_inputs(self.renderer, aov_samples)
+            fold = self._guided_epoch is None or self._guided_epoch != self._epoch
+            d = getattr(self.renderer, "desc", None)
+            origin = (int(d.tile_x0), int(d.tile_y0)) if d is not None and d.tile_enabled else (0, 0)
+            out = capi.temporal_denoise_image(self.temporal, beauty, aov, self.camera.buffer, fold, origin=origin,
+                                              infill=infill if infill is not None and infill is not False else None, **params)
+            self._guided_epoch = self._epoch
+            return out.cpu().numpy()
         if infill is not None and infill is not False:
             return self.renderer.preview(self.temporal, motion=self.motion, aov_samples=aov_samples, infill=infill, **params).cpu().numpy()
         call = self.renderer.denoise_temporal_motion if self.motion else self.renderer.denoise_temporal
@@ -325,8 +363,10 @@ class ProgressiveSession:
     # ---- frames
     def frame(self, dt=0.0):
         self.camera.update(dt)                       # Renderer::update: camera vectors, iterationCounter, randomSeed
-        if self._planned and getattr(self.camera.buffer, "iterationCounter", 1) == 0:
-            self._detach_plan()                      # this frame clears the target: the restarted frame has no error plane yet
+        if getattr(getattr(self.camera, "buffer", None), "iterationCounter", 1) == 0:
+            self._epoch += 1                         # this frame clears the target: a new accumulation
+            if self._planned:
+                self._detach_plan()                  # the restarted frame has no error plane yet
         self.renderer.set_camera(self.camera.buffer)
         self.renderer.iterate()                      # Renderer::draw
         self.frames += 1

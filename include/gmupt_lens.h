@@ -41,8 +41,8 @@ extern "C" {
  *   state, so it follows an attached sampling plan without knowing about it.
  * What stays a pinhole (a limit).  gmupt_pick, gmupt_camera_pick_ray, the AOV rays (gmupt_aov_ray, gmupt_render_aovs), the motion
  *   plane and the temporal projection stay on the centre ray through cam.position: the guide planes of a frame with depth of field
- *   are sharp where the beauty is not.  What that costs the denoiser on out-of-focus regions is not measured; lens-filtered AOV
- *   planes are a follow-up.
+ *   are sharp where the beauty is not.  Lens-filtered AOV planes, the same record from rays through the lens, are an extension of
+ *   their own: include/gmupt_lens_aov.h (gmupt_render_aovs_lens, gmupt_render_denoised_lens).
  * Accumulation.  Setting, changing or detaching a lens does NOT clear the frame by itself: the samples that follow are simply made
  *   with the new lens.  A caller that wants a clean frame restarts the accumulation (gmupt_camera_reset_accumulation, a camera whose
  *   iterationCounter is 0), as ProgressiveSession.set_lens, Renderer::setLens and gmupt_render do.

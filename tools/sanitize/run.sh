@@ -32,6 +32,9 @@ ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_converge_asan"
 # the host rules of adaptive sampling (csrc/pt_adaptive.cpp), the same way
 "$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_adaptive_asan" adaptive_main.cpp ../../gmu-path-tracer_amd/csrc/pt_adaptive.cpp
 ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_adaptive_asan"
+# the host rule of the lens-filtered AOV rays (csrc/pt_lens_aov.cpp), the same way
+"$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_lens_aov_asan" lens_aov_main.cpp ../../gmu-path-tracer_amd/csrc/pt_lens_aov.cpp
+ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_lens_aov_asan"
 # the host rules of the image stages (csrc/pt_denoise.cpp, pt_infill.cpp, pt_temporal.cpp), the same way; their row bands are std::threads, so
 # once more under ThreadSanitizer
 IMG="image_main.cpp ../../gmu-path-tracer_amd/csrc/pt_denoise.cpp ../../gmu-path-tracer_amd/csrc/pt_infill.cpp ../../gmu-path-tracer_amd/csrc/pt_temporal.cpp"
