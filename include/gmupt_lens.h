@@ -59,7 +59,31 @@ extern "C" {
  *   without the wide tables) are returned as they are.
  * Errors: GMUPT_ERR_INVALID_ARGUMENT for a NULL renderer, camera, lens or result, an aperture_radius that is NaN, infinite or
  *   negative, and -- while aperture_radius > 0 -- a focus_distance that is NaN, infinite or not > 0.  No error path changes the
- *   attached lens or writes an output. */
+ *   attached lens or writes an output.
+ * Extreme lenses.  A lens is checked for the errors above and for nothing else: every finite aperture_radius >= 0 and every finite
+ *   focus_distance > 0 is admitted, denormals and FLT_MAX included, and the rule then runs as written, without a guard
+ *   (tests/lens_extremes_util.py LENS_CLASSES is the table of such lenses; tests/test_lens_extremes_cpu.py
+ *   test_every_class_holds_what_it_is_named_for counts what each produces, from gmupt_lens_ray_host alone).
+ *   - Which rays come out.  The origin is always finite.  The direction is a unit vector, or (0, 0, 0), or NaN in at least one
+ *     component, and nothing else: a lens offset or a focal distance t beyond about 1.84e19 makes dot3 inside normalize3 overflow, the
+ *     length is +inf, 1 / inf is 0 and the direction is ZERO (aperture 1e30, focus 1e30; around the limit a lens gives both kinds,
+ *     aperture 3e19 split by the draw r1, focus 1.5e19 split by the pixel); where d*t is itself infinite (focus near FLT_MAX) inf * 0
+ *     is NaN, and where Pf rounds onto the origin (a tiny focus with the draw r1 = 0; a tiny focus with a tiny aperture) the zero vector
+ *     times 1 / 0 is NaN.  A denormal aperture gives ordinary rays whose denormal lens offset is kept, not flushed (visible only with
+ *     cam.position at the origin: pos + 1e-45 is pos elsewhere).  An aperture up to 1.5e19 gives ordinary rays from that far away.
+ *     (test_every_class_holds_what_it_is_named_for, test_a_denormal_aperture_moves_the_origin_only_of_a_camera_at_the_origin)
+ *   - What such rays get.  A ray with a zero or NaN direction is a ray of include/gmupt.h "Degenerate rays": it misses every triangle
+ *     and light, in the renderer's own ray casts (both shipped kernels) as for caller rays, no fault flag is raised, its path ends in
+ *     the next shading stage with the environment colour, and the frame stays finite.  A renderer whose lens gives only such rays
+ *     renders the environment.  Ordinary rays from 1e18 away get what the oracle gives them, to the bit (mostly a light sphere: its
+ *     test cancels from that far).  (tests/test_lens_extremes_cpu.py test_the_oracle_alone_on_the_lens_rays;
+ *     tests/test_lens_extremes_gpu.py test_whole_iterations_equal_the_oracle)
+ *   - Host and device.  gmupt_lens_ray_host and the renderer's lens launch agree bit for bit on every such lens except in the sign and
+ *     payload of a generated NaN, which neither IEEE 754 nor this library pins; which words are NaN is the same.  (On the MI355X
+ *     against an x86 host even those agreed: 0xffc00000 on both.)  (tests/test_lens_extremes_gpu.py test_stage_holds_the_host_rays; the numpy restatements against the host rule:
+ *     tests/test_lens_extremes_cpu.py test_host_rules_equal_the_restatements_on_every_class)
+ *   - The guards of the lens launch (queue length, live paths, path budget) do not depend on the lens, and hold together with a tile
+ *     origin and a sampling plan.  (tests/test_lens_extremes_gpu.py test_tile_budget_and_plan_together) */
 typedef struct { float aperture_radius; float focus_distance; } gmupt_lens;   /* 8 bytes; scene units */
 void gmupt_lens_default_params(gmupt_lens* lens);   /* aperture_radius 0 (a pinhole), focus_distance 1 */
 int gmupt_renderer_set_lens(gmupt_renderer* r, const gmupt_lens* lens_or_null);

@@ -66,7 +66,14 @@ extern "C" {
  *   projection, which reprojects the record's position -- here a mean over the surface samples.
  * Errors: those of gmupt_render_aovs (gmupt_render_denoised) with `samples` checked against s*s rays per pixel, and the lens checks
  *   of gmupt_renderer_set_lens on a lens that is given.  gmupt_aov_lens_ray: GMUPT_ERR_INVALID_ARGUMENT for a NULL camera, lens or
- *   result, a bad lens, samples outside 1..GMUPT_AOV_MAX_SAMPLES or k >= s*s.  No error path writes an output. */
+ *   result, a bad lens, samples outside 1..GMUPT_AOV_MAX_SAMPLES or k >= s*s.  No error path writes an output.
+ * Extreme lenses: include/gmupt_lens.h, "Extreme lenses", holds here too -- steps 3-5 are the same statements, so an admitted lens can
+ *   give these rays a zero or a NaN direction.  Such a ray misses everything and is never a surface sample: it adds cam.envColor to
+ *   the albedo sum and nothing to the others, so no record holds a NaN because of it; a pixel whose every ray is one has coverage 0,
+ *   position (0, 0, 0) and the miss record of ray k = 0, is no surface pixel, and gmupt_render_denoised_lens on a frame of such
+ *   pixels returns the beauty bit for bit.  (tests/test_lens_extremes_gpu.py test_lens_aov_records_equal_the_oracle,
+ *   test_denoiser_copies_a_frame_without_a_surface_pixel, test_denoiser_on_the_mixed_records; the rays on the host:
+ *   tests/test_lens_extremes_cpu.py test_host_rules_equal_the_restatements_on_every_class) */
 int gmupt_render_aovs_lens(gmupt_renderer* r, const gmupt_lens* lens_or_null, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info);
 int gmupt_aov_lens_ray(const gmupt_camera_buffer* cam, const gmupt_lens* lens, uint32_t x, uint32_t y, uint32_t samples, uint32_t k, gmupt_ray* out);
 int gmupt_render_denoised_lens(gmupt_renderer* r, const gmupt_lens* lens_or_null, uint32_t aov_samples, const gmupt_denoise_params* p, float* out_rgba,

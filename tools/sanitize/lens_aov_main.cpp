@@ -1,6 +1,6 @@
 // Stand-alone driver of the host rule of the lens-filtered AOV planes (csrc/pt_lens_aov.cpp and pt_lens_aov.hpp, what gmupt_aov_lens_ray
 // runs) for the sanitizer runs of tools/sanitize/run.sh: every ray of the corner and centre pixels of two frames at every sample count,
-// with a closed, an open and a huge aperture, a focus of 1e-30 and of 1e30, and a camera whose frame vectors are degenerate (zero
+// with a closed, an open and a huge aperture, a focus of 1e-30 and of 1e30, the extreme lenses of tests/lens_extremes_util.py, and a camera whose frame vectors are degenerate (zero
 // `horizontal`: the rule divides by a zero length and must still only compute, never trap or read outside its arguments).  For the
 // well-formed cameras the directions must be unit vectors and the origins must lie within the aperture of the position.  CPU only;
 // nothing here touches a device.
@@ -28,7 +28,11 @@ static gmupt_camera_buffer camera(uint32_t W, uint32_t H, bool degenerate)
 int main()
 {
     const uint32_t sizes[][2] = { { 32, 18 }, { 1920, 1080 } };
-    const gmupt_lens lenses[] = { { 0.0f, 1.0f }, { 0.3f, 13.0f }, { 1.0e6f, 2.0f }, { 0.3f, 1.0e-30f }, { 0.3f, 1.0e30f } };
+    const float fltMax = 3.402823466e+38f;
+    const gmupt_lens lenses[] = { { 0.0f, 1.0f }, { 0.3f, 13.0f }, { 1.0e6f, 2.0f }, { 0.3f, 1.0e-30f }, { 0.3f, 1.0e30f },
+        // the extreme lenses of tests/lens_extremes_util.py (LENS_CLASSES): zero and NaN directions, denormal offsets, origins 1e18 away
+        { 1.0e-45f, 13.0f }, { 1.0e-38f, 13.0f }, { 1.0e18f, 13.0f }, { 1.5e19f, 13.0f }, { 3.0e19f, 13.0f }, { 1.0e30f, 13.0f }, { fltMax, 13.0f },
+        { 0.3f, 1.0e-45f }, { 0.3f, 1.0e19f }, { 0.3f, 1.5e19f }, { 0.3f, 3.0e38f }, { 0.3f, fltMax }, { 1.0e-45f, 1.0e-45f } };
     size_t rays = 0, checked = 0;
     for (int degenerate = 0; degenerate < 2; degenerate++) for (const auto& wh : sizes) {
         const uint32_t W = wh[0], H = wh[1];
@@ -42,7 +46,7 @@ int main()
             if (ray.tmax != 3.402823466e+38f) { std::fprintf(stderr, "tmax is not FLT_MAX\n"); return 1; }
             uint32_t pad; std::memcpy(&pad, reinterpret_cast<const char*>(&ray) + 28, 4);
             if (pad != 0) { std::fprintf(stderr, "the pad word is not 0\n"); return 1; }
-            if (degenerate || p[0] == 0xFFFFFFFFu || lens.focus_distance < 1.0e-20f || lens.focus_distance > 1.0e20f) continue;
+            if (degenerate || p[0] == 0xFFFFFFFFu || lens.focus_distance < 1.0e-20f || lens.focus_distance > 1.0e19f || lens.aperture_radius > 1.0e19f) continue;   // (beyond: zero and NaN directions by design)
             const double len = std::sqrt((double)ray.direction[0] * ray.direction[0] + (double)ray.direction[1] * ray.direction[1] + (double)ray.direction[2] * ray.direction[2]);
             const double off = std::sqrt(std::pow((double)ray.origin[0] - cam.position[0], 2) + std::pow((double)ray.origin[1] - cam.position[1], 2) + std::pow((double)ray.origin[2] - cam.position[2], 2));
             if (!(std::fabs(len - 1.0) < 1e-5) || !(off <= (double)lens.aperture_radius * (1.0 + 1e-5)) || ray.origin[2] != cam.position[2]) {

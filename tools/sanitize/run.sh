@@ -32,6 +32,9 @@ ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_converge_asan"
 # the host rules of adaptive sampling (csrc/pt_adaptive.cpp), the same way
 "$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_adaptive_asan" adaptive_main.cpp ../../gmu-path-tracer_amd/csrc/pt_adaptive.cpp
 ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_adaptive_asan"
+# the host rule of the thin lens (csrc/pt_lens.cpp) on the extreme lenses of tests/lens_extremes_util.py, the same way
+"$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_lens_asan" lens_main.cpp ../../gmu-path-tracer_amd/csrc/pt_lens.cpp
+ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_lens_asan"
 # the host rule of the lens-filtered AOV rays (csrc/pt_lens_aov.cpp), the same way
 "$HIPCC" -x hip --offload-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -ffp-contract=off -o "$BIN/gmupt_lens_aov_asan" lens_aov_main.cpp ../../gmu-path-tracer_amd/csrc/pt_lens_aov.cpp
 ASAN_OPTIONS="detect_leaks=1" $NORAND "$BIN/gmupt_lens_aov_asan"
