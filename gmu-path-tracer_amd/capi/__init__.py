@@ -9,7 +9,8 @@ converge, mesh and accel, then core (Camera, Renderer), which imports the featur
 
 adaptive (adaptive sampling) is the exception: it is reached as capi.adaptive.NAME and keeps its structures and prototypes itself, so
 that the names at this level, the Renderer class and SYMBOLS stay the recorded surface (tests/golden/capi_surface.json).  lens (the
-thin lens, capi.lens.NAME) follows it, and so does lens_aov (the lens-filtered AOV planes, capi.lens_aov.NAME).
+thin lens, capi.lens.NAME) follows it, and so do lens_aov (the lens-filtered AOV planes, capi.lens_aov.NAME) and projection (the camera
+projections, capi.projection.NAME).
 """
 from ._abi import *  # noqa: F401,F403
 from ._lib import _check, _ptr, lib, use_build  # noqa: F401
@@ -26,3 +27,4 @@ from .core import Camera, Renderer  # noqa: F401
 from . import adaptive  # noqa: F401,E402
 from . import lens  # noqa: F401,E402
 from . import lens_aov  # noqa: F401,E402
+from . import projection  # noqa: F401,E402

@@ -357,6 +357,7 @@ static int run_iteration(gmupt_renderer* r, bool doShade, bool doExtend, bool do
         launch_material(p, clearFrame, r->stream);  // computes its own queue offsets (no scan launch)
         if (plan && plan->count) launch_adaptive_retarget(p, plan->sc.list, plan->count, plan->uniformEvery, r->stream);   // re-aims the fresh camera paths
         if (r->lens.aperture_radius > 0.0f) launch_lens_retarget(p, r->lens.aperture_radius, r->lens.focus_distance, r->stream);   // thin lens: after the re-aim, it reads the pixel from the state
+        if (r->projection.kind != GMUPT_PROJ_PINHOLE) launch_proj_retarget(p, r->projection, r->stream);   // camera projection: where the lens would be (the two do not combine)
         if (ev) HIP_TRY(hipEventRecord(ev->e[2], r->stream));
     }
     if (!doShade) HIP_TRY(hipMemsetAsync(p.travCounters, 0, 128, r->stream)); // k_material (block 0) zeroes the ray-cast work counters in a full iteration

@@ -10,6 +10,8 @@ extern "C" int gmupt_renderer_set_lens(gmupt_renderer* r, const gmupt_lens* lens
     gmupt_lens_default_params(&none);
     if (!lens) { r->lens = none; return GMUPT_OK; }
     GMUPT_TRY(lens_params(fn, lens));
+    if (lens->aperture_radius > 0.0f && r->projection.kind != GMUPT_PROJ_PINHOLE)   // include/gmupt_projection.h: the focal plane has no meaning behind the camera
+        return fail(GMUPT_ERR_UNSUPPORTED, "%s: a projection of kind %u is attached: lens and projection do not combine", fn, r->projection.kind);
     r->lens = lens->aperture_radius > 0.0f ? *lens : none;   // the launch argument of the iterations that follow; nothing is enqueued here
     return GMUPT_OK;
 }

@@ -86,13 +86,9 @@ extern "C" int gmupt_camera_pick_ray(const gmupt_camera_buffer* cam, float px, f
     return GMUPT_OK;
 }
 
-extern "C" int gmupt_pick(gmupt_renderer* r, float px, float py, uint32_t light_count, gmupt_ray* ray_out, gmupt_hit* hit_out)
+// the closest hit of one host ray through the renderer's pick buffer: what gmupt_pick and gmupt_pick_projected do with their ray
+int pick_ray_hit(gmupt_renderer* r, const gmupt_ray& ray, uint32_t light_count, gmupt_ray* ray_out, gmupt_hit* hit_out)
 {
-    if (!r || !hit_out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pick: null argument");
-    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_pick: no camera set");
-    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_pick: no scene bound");
-    gmupt_ray ray;
-    GMUPT_TRY(gmupt_camera_pick_ray(&r->p.cam, px, py, &ray));
     HIP_TRY(hipSetDevice(r->dev->id));
     if (!r->pickBuf.ptr) GMUPT_TRY(r->pickBuf.alloc(64, 0, r->stream));
     gmupt_ray* dRay = r->pickBuf.as<gmupt_ray>();
@@ -102,6 +98,16 @@ extern "C" int gmupt_pick(gmupt_renderer* r, float px, float py, uint32_t light_
     GMUPT_TRY(copy_sync(hit_out, dHit, sizeof(*hit_out), hipMemcpyDeviceToHost, r->stream));
     if (ray_out) *ray_out = ray;
     return GMUPT_OK;
+}
+
+extern "C" int gmupt_pick(gmupt_renderer* r, float px, float py, uint32_t light_count, gmupt_ray* ray_out, gmupt_hit* hit_out)
+{
+    if (!r || !hit_out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_pick: null argument");
+    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_pick: no camera set");
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_pick: no scene bound");
+    gmupt_ray ray;
+    GMUPT_TRY(gmupt_camera_pick_ray(&r->p.cam, px, py, &ray));
+    return pick_ray_hit(r, ray, light_count, ray_out, hit_out);
 }
 
 // ------------------------------------------------------------------------------------------------ AOV buffers

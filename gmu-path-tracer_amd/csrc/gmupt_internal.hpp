@@ -16,6 +16,7 @@
 #include "pt_adaptive.hpp"
 #include "pt_lens.hpp"
 #include "pt_lens_aov.hpp"
+#include "pt_projection.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
@@ -152,6 +153,8 @@ struct gmupt_renderer {
     gmupt_adaptive* adaptive = nullptr;
     // thin lens (gmupt_renderer_set_lens): aperture_radius 0 = none attached, every iteration launches what it always did
     gmupt_lens lens{ 0.0f, 1.0f };
+    // camera projection (gmupt_renderer_set_projection): kind GMUPT_PROJ_PINHOLE = none attached, every iteration launches what it always did
+    gmupt_projection projection{ GMUPT_PROJ_PINHOLE, 3.14159274f, 1.0f, 0u };
 
     __attribute__((visibility("default"))) ~gmupt_renderer() { if (stream) (void)hipStreamDestroy(stream); }   // gmupt_renderer_destroy has synchronised it; the library has always exported this symbol
     uint32_t tile_x0() const { return p.tileEnabled ? p.tileX0 : 0u; } uint32_t tile_y0() const { return p.tileEnabled ? p.tileY0 : 0u; }   // the origin of the rendered rectangle
@@ -226,6 +229,7 @@ int query_supported(gmupt_renderer* r, const char* fn);                         
 int query_buffers(gmupt_renderer* r);                                                                           // one timed span of cast queries on the query's own counters and statistics
 int query_begin(gmupt_renderer* r, RenderParams* q);
 int query_end(gmupt_renderer* r, const char* fn, const char* what, gmupt_trace_info* info);
+int pick_ray_hit(gmupt_renderer* r, const gmupt_ray& ray, uint32_t light_count, gmupt_ray* ray_out, gmupt_hit* hit_out);   // gmupt_pick on a ray already made
 int aov_chunk_scratch(gmupt_renderer* r);                                                                       // the rays and hits of one AOV chunk, on first use
 int denoise_params(const char* fn, const gmupt_denoise_params* p, DnParams& out);                               // gmupt_capi_host.cpp
 int image_args(const char* fn, const void* beauty, const void* aov, uint32_t W, uint32_t H, const void* out, size_t bytes, bool device);
@@ -234,14 +238,18 @@ int infill_params(const char* fn, const gmupt_infill_params* p, IfParams& out);
 int converge_params(const char* fn, const gmupt_converge_params* p, CvParams& out);
 int adaptive_params(const char* fn, const gmupt_adaptive_params* p, float monitorThreshold, AdParams& out);   // threshold 0 = monitorThreshold
 int lens_params(const char* fn, const gmupt_lens* lens);                                                         // the argument errors of include/gmupt_lens.h
+int projection_params(const char* fn, const gmupt_projection* proj);                                             // gmupt_capi_projection.hip: those of include/gmupt_projection.h
 // gmupt_capi_denoise.hip: the chains behind the temporal entry points; infill == nullptr is the chain without the infill stage
 int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
                      const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
                      const gmupt_temporal_params* p, const IfParams* infill, float* out_rgba, size_t out_bytes, float* ms);
 int render_denoised(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, const IfParams* infill, float* out_rgba, size_t bytes,
-                    gmupt_trace_info* info, const gmupt_lens* lensGuides = nullptr);   // lensGuides: the records of gmupt_render_aovs_lens under that lens
+                    gmupt_trace_info* info, const gmupt_lens* lensGuides = nullptr,    // lensGuides: the records of gmupt_render_aovs_lens under that lens
+                    const gmupt_projection* projGuides = nullptr);                     // projGuides: those of gmupt_render_aovs_projected under that projection
 // gmupt_capi_lens_aov.hip: gmupt_render_aovs_lens under a checked lens, with fn as the name in its errors
 int render_aovs_lens(const char* fn, gmupt_renderer* r, const gmupt_lens& lens, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info);
+// gmupt_capi_projection.hip: gmupt_render_aovs_projected under a checked projection, with fn as the name in its errors
+int render_aovs_projected(const char* fn, gmupt_renderer* r, const gmupt_projection& proj, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info);
 int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
                              const IfParams* infill, float* out_rgba, size_t bytes, gmupt_trace_info* info);
 // gmupt_capi_infill.hip: grows the renderer's infill scratch for the image (the one place that does) and enqueues the stage

@@ -112,6 +112,69 @@ gmupt_lens Renderer::focusAt(float x, float y, float apertureRadius)
 	return lens;
 }
 
+void Renderer::setProjection(const gmupt_projection& projection)
+{
+	check(gmupt_renderer_set_projection(mRenderer.get(), &projection));
+	mScene.mCamera.getBuffer()->iterationCounter = -1; // the samples so far were made with the old projection
+}
+
+Renderer::Pick Renderer::pickProjected(float x, float y)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	Pick p{};
+	check(gmupt_pick_projected(mRenderer.get(), x, y, mScene.mCamera.getBuffer()->lightCount, &p.ray, &p.hit));
+	return p;
+}
+
+gmupt_trace_info Renderer::renderAovsProjected(gmupt_aov* deviceOut, size_t bytes, unsigned samples)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	gmupt_trace_info info{};
+	check(gmupt_render_aovs_projected(mRenderer.get(), nullptr, samples, deviceOut, bytes, &info));
+	return info;
+}
+
+std::vector<gmupt_aov> Renderer::renderAovsProjected(unsigned samples)
+{
+	const Resolution t = targetSize();
+	std::vector<gmupt_aov> out(static_cast<size_t>(t.first) * t.second);
+	const size_t bytes = out.size() * sizeof(gmupt_aov);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("renderAovsProjected: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { renderAovsProjected(static_cast<gmupt_aov*>(d), bytes, samples); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error("renderAovsProjected: cannot read the records back");
+	return out;
+}
+
+gmupt_trace_info Renderer::denoiseProjected(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_denoise_params* params)
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	gmupt_trace_info info{};
+	check(gmupt_render_denoised_projected(mRenderer.get(), nullptr, aovSamples, params, deviceOut, bytes, &info));
+	return info;
+}
+
+std::vector<float> Renderer::denoiseProjected(unsigned aovSamples, const gmupt_denoise_params* params)
+{
+	const Resolution t = targetSize();
+	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
+	const size_t bytes = out.size() * sizeof(float);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoiseProjected: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { denoiseProjected(static_cast<float*>(d), bytes, aovSamples, params); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error("denoiseProjected: cannot read the image back");
+	return out;
+}
+
 gmupt_trace_info Renderer::renderAovs(gmupt_aov* deviceOut, size_t bytes, unsigned samples)
 {
 	bindScene();

@@ -10,6 +10,7 @@
 #include "../../include/gmupt_adaptive.h"
 #include "../../include/gmupt_lens.h"
 #include "../../include/gmupt_lens_aov.h"
+#include "../../include/gmupt_projection.h"
 
 class Renderer
 {
@@ -54,6 +55,17 @@ public:
 	// pick, the AOV planes and the temporal projection stay on the pinhole centre ray.
 	void setLens(float apertureRadius, float focusDistance);
 	gmupt_lens focusAt(float x, float y, float apertureRadius);
+	// camera projections (include/gmupt_projection.h): an orthographic, fisheye or equirectangular camera attached to the renderer; kind
+	// GMUPT_PROJ_PINHOLE detaches it.  Restarts the accumulation like a camera move.  Throws while a lens with an aperture is attached (and
+	// setLens with one throws while a projection is): the two do not combine.  pickProjected is pick() on the attached projection's ray;
+	// renderAovsProjected / denoiseProjected are renderAovsLens / denoiseLens under it (gmupt_render_aovs_projected, gmupt_render_denoised_projected):
+	// samples * samples stratified rays per pixel, no centre ray.  The temporal previews stay a pinhole's and must not be used with a projection.
+	void setProjection(const gmupt_projection& projection);
+	Pick pickProjected(float x, float y);
+	gmupt_trace_info renderAovsProjected(gmupt_aov* deviceOut, size_t bytes, unsigned samples = 1);
+	std::vector<gmupt_aov> renderAovsProjected(unsigned samples = 1);
+	gmupt_trace_info denoiseProjected(float* deviceOut, size_t bytes, unsigned aovSamples = 1, const gmupt_denoise_params* params = nullptr);
+	std::vector<float> denoiseProjected(unsigned aovSamples = 1, const gmupt_denoise_params* params = nullptr);
 	// AOV buffers of the current camera (gmupt_render_aovs): one gmupt_aov per pixel of targetSize(), row-major -- albedo / normal guide images
 	// for a denoiser, depth, position, ids.  samples 1..8: s*s stratified rays per pixel for the albedo and normal planes when > 1.
 	// The first form writes caller-owned device memory (16-byte aligned, bytes >= pixels * 64); the second returns the records on the host.

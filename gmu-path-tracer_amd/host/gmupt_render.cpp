@@ -34,6 +34,8 @@
 //                                                         floats also as hex bit patterns; not with --ranks
 //                [--lens-guides]                          with --aperture: --denoise and --aov use the lens-filtered records (Renderer::denoiseLens /
 //                                                         renderAovsLens, include/gmupt_lens_aov.h), S*S rays per pixel through the lens; not with --infill
+//                [--projection ortho:H | fisheye:DEG | equirect]   another camera (Renderer::setProjection, include/gmupt_projection.h); --pick, --aov and
+//                                                         --denoise follow it; one JSON line with the projection; not with --aperture, --temporal, --infill, --ranks
 //                [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]
 //                                                         adaptive sampling in that loop (Renderer::renderAdaptive, include/gmupt_adaptive.h): the JSON
 //                                                         line gains active, entries, max_rep, skipped_nonfinite of the last plan and paths_generated
@@ -167,6 +169,7 @@ int main(int argc, char** argv)
 	bool treeCost = false;
 	bool adaptive = false, maxRepeatGiven = false, uniformEveryGiven = false; unsigned maxRepeat = 1, uniformEvery = 0;
 	bool lensGuides = false;
+	bool projectionGiven = false; gmupt_projection projection{ GMUPT_PROJ_PINHOLE, 3.14159274f, 1.f, 0u };
 	bool apertureGiven = false, focusGiven = false, focusAtGiven = false; float aperture = 0.f, focus = 0.f, focusX = 0.f, focusY = 0.f;
 	bool untilError = false, checkEveryGiven = false, allowPixelsGiven = false; float untilThreshold = 0.f; unsigned checkEvery = 8, allowPixels = 0; std::string errorMap;
 	for (int i = 1; i < argc; i++) {
@@ -215,6 +218,20 @@ int main(int argc, char** argv)
 		else if (a == "--focus") { char* end = nullptr; const char* v = next(); focus = std::strtof(v, &end); focusGiven = true; if (end == v || *end || !(focus > 0.f) || focus > std::numeric_limits<float>::max()) { std::fprintf(stderr, "--focus takes a finite distance > 0\n"); return 2; } }
 		else if (a == "--focus-at") { if (std::sscanf(next(), "%f,%f", &focusX, &focusY) != 2) { std::fprintf(stderr, "--focus-at takes a pixel X,Y\n"); return 2; } focusAtGiven = true; }
 		else if (a == "--lens-guides") lensGuides = true;
+		else if (a == "--projection") {
+			const std::string v = next(); char* end = nullptr; projectionGiven = true;
+			if (v == "equirect") projection.kind = GMUPT_PROJ_EQUIRECT;
+			else if (v.compare(0, 6, "ortho:") == 0) {
+				projection.kind = GMUPT_PROJ_ORTHOGRAPHIC; projection.extent = std::strtof(v.c_str() + 6, &end);
+				if (end == v.c_str() + 6 || *end || !(projection.extent > 0.f) || projection.extent > std::numeric_limits<float>::max()) { std::fprintf(stderr, "--projection ortho:H takes a finite height H > 0\n"); return 2; }
+			}
+			else if (v.compare(0, 8, "fisheye:") == 0) {
+				const float deg = std::strtof(v.c_str() + 8, &end);
+				if (end == v.c_str() + 8 || *end || !(deg > 0.f) || deg > 360.f) { std::fprintf(stderr, "--projection fisheye:DEG takes a field of view in (0, 360] degrees\n"); return 2; }
+				projection.kind = GMUPT_PROJ_FISHEYE; projection.fov = deg >= 360.f ? 6.28318548f : deg * 0.0174532925f;
+			}
+			else { std::fprintf(stderr, "--projection takes ortho:H, fisheye:DEG or equirect\n"); return 2; }
+		}
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -240,6 +257,10 @@ int main(int argc, char** argv)
 			            "                                 picks, AOVs and previews stay on the pinhole centre ray; not with --ranks\n"
 			            "             [--lens-guides]     with --aperture: --denoise and --aov use the lens-filtered AOV records (S*S rays per pixel through the lens),\n"
 			            "                                 so that the guides are blurred where the frame is; not with --infill\n"
+			            "             [--projection ortho:H | fisheye:DEG | equirect]   another camera: orthographic with a view H scene units high, equidistant fisheye with\n"
+			            "                                 DEG degrees across the image circle, or the 360-degree equirectangular panorama; --pick, --aov and --denoise\n"
+			            "                                 follow it (S*S stratified rays per pixel); one JSON line with the projection; not with --aperture, --temporal,\n"
+			            "                                 --infill or --ranks\n"
 			            "             [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]   adaptive sampling: after every check that does not end the loop\n"
 			            "                                 the new camera paths go to the pixels still above T, up to N (default 1, at most 64) list entries each,\n"
 			            "                                 every N-th path (default 0 = none) to the pixel it would have gone to anyway; T must be > 0; the JSON line\n"
@@ -356,6 +377,14 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--lens-guides filters the guide records through the lens: it needs --aperture R");
 		if (lensGuides && infill)
 			throw std::invalid_argument("--lens-guides guides --denoise and --aov: it cannot be combined with --infill");
+		if (projectionGiven && apertureGiven)
+			throw std::invalid_argument("--projection and --aperture do not combine: the focal plane of a lens has no meaning behind the camera");
+		if (projectionGiven && !temporalPrefix.empty())
+			throw std::invalid_argument("--projection cannot be combined with --temporal: the temporal projection inverts a pinhole");
+		if (projectionGiven && infill)
+			throw std::invalid_argument("--projection guides --denoise by its own records: it cannot be combined with --infill");
+		if (projectionGiven && ranks > 1)
+			throw std::invalid_argument("--projection sets the camera of a single process: it cannot be combined with --ranks N > 1");
 		if (apertureGiven && ranks > 1)
 			throw std::invalid_argument("--aperture sets the lens of a single process: it cannot be combined with --ranks N > 1");
 		if (untilError && ranks > 1)
@@ -432,6 +461,11 @@ int main(int argc, char** argv)
 			unsigned ab, fb; std::memcpy(&ab, &lens.aperture_radius, 4); std::memcpy(&fb, &lens.focus_distance, 4);
 			std::printf("{\"lens\": {\"aperture_radius\": %.9g, \"focus_distance\": %.9g, \"aperture_bits\": \"%08x\", \"focus_bits\": \"%08x\"}}\n", lens.aperture_radius, lens.focus_distance, ab, fb);
 		}
+		if (projectionGiven) {
+			renderer.setProjection(projection);
+			unsigned fb, eb; std::memcpy(&fb, &projection.fov, 4); std::memcpy(&eb, &projection.extent, 4);
+			std::printf("{\"projection\": {\"kind\": %u, \"fov\": %.9g, \"extent\": %.9g, \"fov_bits\": \"%08x\", \"extent_bits\": \"%08x\"}}\n", projection.kind, projection.fov, projection.extent, fb, eb);
+		}
 		if (untilError) {
 			gmupt_converge_params cp; gmupt_converge_default_params(&cp);
 			cp.threshold = untilThreshold; cp.allow_pixels = allowPixels;
@@ -464,7 +498,7 @@ int main(int argc, char** argv)
 		else for (unsigned f = 0; f < frames; f++) { renderer.update(0.f); renderer.draw(); }
 		if (capture) { renderer.requestCapture(); renderer.update(0.f); std::printf("capture %s\n", renderer.lastCapturePath().c_str()); }
 		if (doPick) {
-			const Renderer::Pick pk = renderer.pick(pickX, pickY);
+			const Renderer::Pick pk = projectionGiven ? renderer.pickProjected(pickX, pickY) : renderer.pick(pickX, pickY);
 			const bool found = pk.hit.triangle >= 0 || pk.hit.light > 0;
 			float pt[3] = { 0.f, 0.f, 0.f };
 			for (int k = 0; k < 3; k++) pt[k] = pk.ray.origin[k] + pk.ray.direction[k] * pk.hit.t;
@@ -474,7 +508,7 @@ int main(int argc, char** argv)
 			if (found) std::printf(", \"point\": [%.9g, %.9g, %.9g]}\n", pt[0], pt[1], pt[2]); else std::printf(", \"point\": null}\n");
 		}
 		if (!aovPrefix.empty()) {
-			const std::vector<gmupt_aov> aov = lensGuides ? renderer.renderAovsLens(aovSamples) : renderer.renderAovs(aovSamples);
+			const std::vector<gmupt_aov> aov = projectionGiven ? renderer.renderAovsProjected(aovSamples) : lensGuides ? renderer.renderAovsLens(aovSamples) : renderer.renderAovs(aovSamples);
 			writeAovPfm(aovPrefix + "_albedo.pfm", aov, w, h, offsetof(gmupt_aov, albedo), 3);
 			writeAovPfm(aovPrefix + "_normal.pfm", aov, w, h, offsetof(gmupt_aov, normal), 3);
 			writeAovPfm(aovPrefix + "_depth.pfm", aov, w, h, offsetof(gmupt_aov, depth), 1);
@@ -485,7 +519,7 @@ int main(int argc, char** argv)
 		}
 		if (!denoisePrefix.empty()) {
 			gmupt_infill_params ip; gmupt_infill_default_params(&ip);
-			const std::vector<float> img = infill ? renderer.preview(false, false, aovSamples, nullptr, &ip) : lensGuides ? renderer.denoiseLens(aovSamples) : renderer.denoise(aovSamples);
+			const std::vector<float> img = infill ? renderer.preview(false, false, aovSamples, nullptr, &ip) : projectionGiven ? renderer.denoiseProjected(aovSamples) : lensGuides ? renderer.denoiseLens(aovSamples) : renderer.denoise(aovSamples);
 			writePfmFile(denoisePrefix + ".pfm", img, w, h);
 			std::vector<unsigned char> png(img.size());
 			for (size_t i = 0; i < img.size(); i += 4) // Renderer::captureScreen's conversion: float * 255 truncated, alpha 255

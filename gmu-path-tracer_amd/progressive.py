@@ -39,6 +39,7 @@ class ProgressiveSession:
         self.baseline = None   # the tree cost (sah) that set_vertices(rebuild_above=...) compares a refitted tree with; rebuild() forgets it
         self._epoch = 0        # accumulations started (a frame that cleared the target, a resize): what denoised_temporal(lens_guides=True) folds its history by
         self._guided_epoch = None   # the epoch of its last call
+        self.projection = None # the capi.projection.Projection of set_projection(); None = the pinhole
 
     # ---- events (applied before the next frame, like the GUI callbacks of the reference)
     def move_camera(self, mouse_dx=0.0, mouse_dy=0.0, w=False, s=False, a=False, d=False):
@@ -61,6 +62,8 @@ class ProgressiveSession:
         of the two with an aperture > 0.  The accumulation restarts like after a camera move: the temporal history stays and is
         reprojected as usual (pick, the AOV planes and the projection stay on the pinhole centre ray).  Returns the capi.lens.Lens."""
         from .capi import lens as L
+        if aperture > 0 and self.projection is not None:
+            raise ValueError("set_lens: a projection is attached (set_projection): lens and projection do not combine")
         if aperture > 0 and (focus is None) == (focus_at is None):
             raise ValueError("set_lens: an open aperture takes either focus=distance or focus_at=(px, py)")
         if aperture > 0 and focus_at is not None:
@@ -73,6 +76,31 @@ class ProgressiveSession:
         self.camera.reset_accumulation()
         self._reset_converge()                       # the batches seen so far are of the old lens
         return lens
+
+    def set_projection(self, kind, fov=None, extent=None):
+        """Another camera projection (capi.projection, include/gmupt_projection.h): kind "orthographic" (extent: the world-space height
+        of the view), "fisheye" (fov: the angle across the image circle in radians, default pi), "equirect" (the 360-degree panorama)
+        or "pinhole" / None, which detaches.  From the next frame on every fresh camera path gets that projection's ray, and the
+        accumulation restarts like after a camera move.  While a projection is attached pick(), aovs() and denoised() go through the
+        projected entry points (pinhole guides would show a different picture); denoised(infill=...) is the projected preview chain
+        (the infill takes the projected records as they are), and preview() is a tile gather without guides, so it needs no routing.  What inverts a pinhole refuses with ValueError:
+        denoised_temporal(), set_vertices / set_pose with keep_history=True, and set_lens with an aperture.  While a lens with an
+        aperture is attached the library refuses the projection (GmuptError, ERR_UNSUPPORTED).  Returns the capi.projection.Projection (None when detached)."""
+        from .capi import projection as P
+        kind = P.KINDS.get(kind, kind) if kind is not None else P.PINHOLE
+        fields = {k: v for k, v in (("fov", fov), ("extent", extent)) if v is not None}
+        proj = P.projection_params(kind, **fields)
+        P.set_projection(self.renderer, proj)        # GmuptError (ERR_UNSUPPORTED) while a lens with an aperture is attached
+        self.projection = proj if proj.kind != P.PINHOLE else None
+        self.camera.reset_accumulation()
+        if self.temporal is not None:
+            self.temporal.reset()                    # the history is another picture
+        self._reset_converge()
+        return self.projection
+
+    def _no_projection(self, who):
+        if self.projection is not None:
+            raise ValueError("%s: a projection is attached (set_projection), and the temporal projection inverts a pinhole" % who)
 
     def set_vertices(self, scene_buffers, verts, normals=None, keep_history=False, indices=None, rebuild_above=None, optimize=0):
         """The geometry moved (same vertex count, same triangles): upload the vertices, and `normals` (when given) into the property
@@ -105,6 +133,8 @@ class ProgressiveSession:
         A baseline of 0 (a root without area) never triggers.  The returned dict then also holds cost, baseline (the value the
         decision was made against), candidate_cost (None when none was built) and tree_rebuilt.  There is no default threshold:
         DESIGN.md "Tree cost" has the measurements."""
+        if keep_history:
+            self._no_projection("set_vertices(keep_history=True)")
         rebuild_above = self._moved_args("set_vertices", normals, rebuild_above)
         if hasattr(verts, "is_cuda"):
             scene_buffers.verts.update_from_device(verts)
@@ -120,6 +150,8 @@ class ProgressiveSession:
         rebuild_above is taken before the pose.  The other arguments and the returned dict are set_vertices'.  joint_mats /
         target_weights: numpy arrays or torch device tensors.  The session does not own `pose`: a rebuild() that keeps the vertex count
         keeps it valid, and closing it is the caller's business (the renderer closes it at the latest)."""
+        if keep_history:
+            self._no_projection("set_pose(keep_history=True)")
         rebuild_above = self._moved_args("set_pose", normals, rebuild_above)
         pose.update(joint_mats, target_weights)
         return self._after_vertices(scene_buffers, normals, keep_history, indices, rebuild_above, optimize)
@@ -286,7 +318,11 @@ class ProgressiveSession:
         camera through the renderer's closest-hit query, light spheres up to the session's lightCount included.  Returns a dict:
         triangle (reference index, -1: none), material (of that triangle), light (0, or 1 + the light sphere in front of every
         triangle), t and the world-space point origin + direction * t (None when nothing was hit)."""
-        ray, hit = self.renderer.pick(px, py, int(self.camera.buffer.lightCount))
+        if self.projection is not None:              # the attached projection's ray, not the pinhole's
+            from .capi import projection as P
+            ray, hit = P.pick(self.renderer, px, py, int(self.camera.buffer.lightCount))
+        else:
+            ray, hit = self.renderer.pick(px, py, int(self.camera.buffer.lightCount))
         o = np.array(ray.origin[:], np.float32); d = np.array(ray.direction[:], np.float32)
         found = hit.triangle >= 0 or hit.light > 0
         return {"triangle": int(hit.triangle), "material": int(hit.material), "light": int(hit.light), "t": float(hit.t),
@@ -298,6 +334,8 @@ class ProgressiveSession:
         triangle, material, light, coverage.  samples: 1..8 stratified samples per axis for the albedo / normal planes.  Like pick, it
         uses the camera the renderer was last given (the frame just drawn)."""
         from . import capi
+        if self.projection is not None:              # samples^2 stratified rays of the attached projection, no centre ray
+            return capi.aov_fields(capi.projection.aovs(self.renderer, samples))
         return capi.aov_fields(self.renderer.aovs(samples))
 
     def _guide_lens(self, lens_guides):
@@ -317,6 +355,13 @@ class ProgressiveSession:
         lens_guides: True with a lens attached (set_lens) -- the guide records are the lens-filtered ones (capi.lens_aov,
         include/gmupt_lens_aov.h: aov_samples^2 rays per pixel through the lens), so that out-of-focus silhouettes are filtered like
         the beauty shows them; without a lens, or False (the default), the pinhole records and today's bits."""
+        if self.projection is not None:              # the guides follow the projection; the infill takes its records as they are
+            from . import capi
+            if infill is None or infill is False:
+                return capi.projection.denoise(self.renderer, aov_samples, **params).cpu().numpy()
+            beauty, aov = capi.projection.guided_inputs(self.renderer, aov_samples)
+            filled = capi.infill_image(self.renderer, beauty, aov, **(infill if isinstance(infill, dict) else {}))
+            return capi.denoise_image(self.renderer, filled, aov, **params).cpu().numpy()
         lens = self._guide_lens(lens_guides)
         if lens is not None:
             from . import capi
@@ -341,6 +386,7 @@ class ProgressiveSession:
         has cleared the target, or a resize happened, since the last such call.  The projection reprojects the record's position, with
         lens records a mean over the surface samples, and the motion plane stays a pinhole's and is not used on this path; one
         history should be fed by one kind of record."""
+        self._no_projection("denoised_temporal")
         if self.temporal is None:
             from . import capi
             self.temporal = capi.Temporal(self.renderer)

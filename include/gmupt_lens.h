@@ -60,6 +60,10 @@ extern "C" {
  * Errors: GMUPT_ERR_INVALID_ARGUMENT for a NULL renderer, camera, lens or result, an aperture_radius that is NaN, infinite or
  *   negative, and -- while aperture_radius > 0 -- a focus_distance that is NaN, infinite or not > 0.  No error path changes the
  *   attached lens or writes an output.
+ * Lens and projection do not combine (include/gmupt_projection.h): the focal plane of step 4 has no meaning behind the camera.
+ *   gmupt_renderer_set_lens returns GMUPT_ERR_UNSUPPORTED for aperture_radius > 0 while a projection other than the pinhole is
+ *   attached, and gmupt_renderer_set_projection returns it while a lens with aperture_radius > 0 is.  With no projection attached
+ *   gmupt_renderer_set_lens is what it was.
  * Extreme lenses.  A lens is checked for the errors above and for nothing else: every finite aperture_radius >= 0 and every finite
  *   focus_distance > 0 is admitted, denormals and FLT_MAX included, and the rule then runs as written, without a guard
  *   (tests/lens_extremes_util.py LENS_CLASSES is the table of such lenses; tests/test_lens_extremes_cpu.py
