@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import _P, ERR_INVALID_ARGUMENT, GmuptError, aov_dtype
+from ._abi import _P, ERR_INVALID_ARGUMENT, GmuptError, Ray, aov_dtype
 from ._lib import _check, lib
 
 
@@ -66,6 +66,34 @@ def make_params(struct, defaults, what, params, fields, inner=None, inner_fields
         else:
             raise TypeError("unknown %s parameter %r" % (what, k))
     return p
+
+
+def opt_ref(struct):
+    """byref(struct), or NULL for None: an optional structure argument (`lens_or_null`, `proj_or_null`)."""
+    return C.byref(struct) if struct is not None else None
+
+
+def aov_ray_table(fn, cam_buffer, rule, xs, ys, samples):
+    """All s*s-ray-plan AOV rays of the pixels (xs[i], ys[i]) as an (N, R, 8) float32 array of gmupt_ray records (R = samples^2):
+    fn(cam, rule, x, y, samples, k, ray) is gmupt_aov_lens_ray or gmupt_aov_projected_ray, `rule` its Lens or Projection."""
+    R = samples * samples
+    out = np.empty((len(xs), R, 8), np.float32)
+    ray = Ray()
+    pc, pp, pr = C.byref(cam_buffer), C.byref(rule), C.byref(ray)
+    for i, (x, y) in enumerate(zip(xs, ys)):
+        for k in range(R):
+            _check(fn(pc, pp, int(x), int(y), int(samples), k, pr))
+            out[i, k] = np.frombuffer(ray, np.float32)
+    return out
+
+
+def guided_inputs(renderer, aov):
+    """(beauty, aov) for an *_image stage: the renderer's frame as an (H, W, 4) float32 tensor (gmupt_copy_framebuffer_to_device) next to
+    the (H, W, 16) records `aov`, on their GPU."""
+    import torch
+    beauty = torch.empty(tuple(aov.shape[:2]) + (4,), dtype=torch.float32, device=aov.device)
+    renderer.copy_framebuffer_to_device(beauty.data_ptr(), beauty.numel() * 4)
+    return beauty, aov
 
 
 # Base of every class that wraps a library object in `h`: close() destroys it through the function the subclass names in _destroy;

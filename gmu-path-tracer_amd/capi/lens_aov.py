@@ -3,8 +3,7 @@ field, the rays they are made of on the CPU, and the denoiser on them.  Like cap
 adds nothing to capi's own names, to the Renderer class or to capi.SYMBOLS: those are the recorded surface of the binding."""
 import ctypes as C
 
-import numpy as np
-
+from . import _stage
 from ._abi import _EXTRA_SYMBOLS, _P, CameraBuffer, DenoiseParams, Ray, TraceInfo
 from ._lib import _check, lib
 from .denoise import denoise_params
@@ -19,16 +18,12 @@ SYMBOLS = {
 _EXTRA_SYMBOLS.update(SYMBOLS)
 
 
-def _lens_arg(lens):
-    return C.byref(lens) if lens is not None else None
-
-
 def aovs(renderer, samples=1, lens=None, info=None):
     """gmupt_render_aovs_lens: the G-buffer of the renderer's rectangle seen through `lens` (a capi.lens.Lens; None = the lens attached
     to the renderer, a pinhole when none is) -- samples * samples rays per pixel, each pixel-filter cell through its own lens stratum.
     Returns an (H, W, 16) float32 torch tensor on the renderer's GPU shaped like Renderer.aovs (capi.aov_fields splits it); the
     renderer's last_aovs is its TraceInfo.  The renderer's frame, state and attached lens are not touched."""
-    (out,), renderer.last_aovs = renderer._frame(info, (16,), lambda *tail: lib().gmupt_render_aovs_lens(renderer.h, _lens_arg(lens), int(samples), *tail))
+    (out,), renderer.last_aovs = renderer._frame(info, (16,), lambda *tail: lib().gmupt_render_aovs_lens(renderer.h, _stage.opt_ref(lens), int(samples), *tail))
     return out
 
 
@@ -41,25 +36,13 @@ def aov_lens_ray(cam_buffer, lens, x, y, samples, k):
 
 def aov_lens_rays(cam_buffer, lens, xs, ys, samples):
     """All lens AOV rays of the pixels (xs[i], ys[i]) as an (N, R, 8) float32 array of gmupt_ray records (R = samples^2)."""
-    R = samples * samples
-    out = np.empty((len(xs), R, 8), np.float32)
-    ray = Ray()
-    fn, pc, pl, pr = lib().gmupt_aov_lens_ray, C.byref(cam_buffer), C.byref(lens), C.byref(ray)
-    for i, (x, y) in enumerate(zip(xs, ys)):
-        for k in range(R):
-            _check(fn(pc, pl, int(x), int(y), int(samples), k, pr))
-            out[i, k] = np.frombuffer(ray, np.float32)
-    return out
+    return _stage.aov_ray_table(lib().gmupt_aov_lens_ray, cam_buffer, lens, xs, ys, samples)
 
 
 def guided_inputs(renderer, aov_samples=1, lens=None):
     """What an *_image stage takes for a frame with depth of field: (beauty, aov), the renderer's frame as an (H, W, 4) float32 tensor
     (gmupt_copy_framebuffer_to_device) and the lens records of aovs(renderer, aov_samples, lens), both on the renderer's GPU."""
-    import torch
-    aov = aovs(renderer, aov_samples, lens)
-    beauty = torch.empty(tuple(aov.shape[:2]) + (4,), dtype=torch.float32, device=aov.device)
-    renderer.copy_framebuffer_to_device(beauty.data_ptr(), beauty.numel() * 4)
-    return beauty, aov
+    return _stage.guided_inputs(renderer, aovs(renderer, aov_samples, lens))
 
 
 def denoise(renderer, aov_samples=1, lens=None, info=None, **params):
@@ -67,5 +50,5 @@ def denoise(renderer, aov_samples=1, lens=None, info=None, **params):
     Returns an (H, W, 4) float32 torch tensor on the renderer's GPU; params: the denoise_params fields."""
     dp = denoise_params(**params)
     (out,), renderer.last_denoise = renderer._frame(info, (4,), lambda *tail: lib().gmupt_render_denoised_lens(
-        renderer.h, _lens_arg(lens), int(aov_samples), C.byref(dp), *tail))
+        renderer.h, _stage.opt_ref(lens), int(aov_samples), C.byref(dp), *tail))
     return out

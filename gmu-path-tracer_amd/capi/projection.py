@@ -10,7 +10,7 @@ import numpy as np
 
 from ._abi import _EXTRA_SYMBOLS, _P, CameraBuffer, DenoiseParams, Hit, Ray, TraceInfo
 from ._lib import _check, lib
-from ._stage import make_params
+from . import _stage
 from .denoise import denoise_params
 
 PINHOLE, ORTHOGRAPHIC, FISHEYE, EQUIRECT = 0, 1, 2, 3
@@ -45,7 +45,7 @@ _EXTRA_SYMBOLS.update(SYMBOLS)
 
 def projection_params(kind=PINHOLE, **params):
     """gmupt_projection_default_params with the given fields replaced (kind: a number or a name of KINDS; fov, extent)."""
-    return make_params(Projection, "gmupt_projection_default_params", "projection", dict(params, kind=KINDS.get(kind, kind)), ("kind", "fov", "extent"))
+    return _stage.make_params(Projection, "gmupt_projection_default_params", "projection", dict(params, kind=KINDS.get(kind, kind)), ("kind", "fov", "extent"))
 
 
 def fisheye(fov_degrees=180.0):
@@ -60,15 +60,11 @@ def equirect():
     return projection_params(EQUIRECT)
 
 
-def _arg(proj):
-    return C.byref(proj) if proj is not None else None
-
-
 def set_projection(renderer, proj):
     """gmupt_renderer_set_projection: attaches `proj` (a Projection) -- from the next iteration on every fresh camera path gets that
     projection's ray -- or, with None or the pinhole kind, detaches: the iterations are again what they always were.  The frame is
     not cleared.  GmuptError (ERR_UNSUPPORTED) while a lens with an aperture is attached."""
-    _check(lib().gmupt_renderer_set_projection(renderer.h, _arg(proj)))
+    _check(lib().gmupt_renderer_set_projection(renderer.h, _stage.opt_ref(proj)))
 
 
 def get_projection(renderer):
@@ -140,22 +136,14 @@ def aov_projected_ray(cam_buffer, proj, x, y, samples, k):
 
 def aov_projected_rays(cam_buffer, proj, xs, ys, samples):
     """All projected AOV rays of the pixels (xs[i], ys[i]) as an (N, R, 8) float32 array of gmupt_ray records (R = samples^2)."""
-    R = samples * samples
-    out = np.empty((len(xs), R, 8), np.float32)
-    ray = Ray()
-    fn, pc, pp, pr = lib().gmupt_aov_projected_ray, C.byref(cam_buffer), C.byref(proj), C.byref(ray)
-    for i, (x, y) in enumerate(zip(xs, ys)):
-        for k in range(R):
-            _check(fn(pc, pp, int(x), int(y), int(samples), k, pr))
-            out[i, k] = np.frombuffer(ray, np.float32)
-    return out
+    return _stage.aov_ray_table(lib().gmupt_aov_projected_ray, cam_buffer, proj, xs, ys, samples)
 
 
 def aovs(renderer, samples=1, proj=None, info=None):
     """gmupt_render_aovs_projected: the G-buffer of the renderer's rectangle under `proj` (None = the projection attached to the
     renderer, the pinhole when none is) -- samples * samples stratified rays per pixel.  Returns an (H, W, 16) float32 torch tensor on
     the renderer's GPU shaped like Renderer.aovs (capi.aov_fields splits it); the renderer's last_aovs is its TraceInfo."""
-    (out,), renderer.last_aovs = renderer._frame(info, (16,), lambda *tail: lib().gmupt_render_aovs_projected(renderer.h, _arg(proj), int(samples), *tail))
+    (out,), renderer.last_aovs = renderer._frame(info, (16,), lambda *tail: lib().gmupt_render_aovs_projected(renderer.h, _stage.opt_ref(proj), int(samples), *tail))
     return out
 
 
@@ -170,11 +158,7 @@ def read_aov_rays(renderer, count):
 def guided_inputs(renderer, aov_samples=1, proj=None):
     """What an *_image stage takes for a frame under a projection: (beauty, aov), the renderer's frame as an (H, W, 4) float32 tensor
     and the records of aovs(renderer, aov_samples, proj), both on the renderer's GPU."""
-    import torch
-    aov = aovs(renderer, aov_samples, proj)
-    beauty = torch.empty(tuple(aov.shape[:2]) + (4,), dtype=torch.float32, device=aov.device)
-    renderer.copy_framebuffer_to_device(beauty.data_ptr(), beauty.numel() * 4)
-    return beauty, aov
+    return _stage.guided_inputs(renderer, aovs(renderer, aov_samples, proj))
 
 
 def denoise(renderer, aov_samples=1, proj=None, info=None, **params):
@@ -182,5 +166,5 @@ def denoise(renderer, aov_samples=1, proj=None, info=None, **params):
     Returns an (H, W, 4) float32 torch tensor on the renderer's GPU; params: the denoise_params fields."""
     dp = denoise_params(**params)
     (out,), renderer.last_denoise = renderer._frame(info, (4,), lambda *tail: lib().gmupt_render_denoised_projected(
-        renderer.h, _arg(proj), int(aov_samples), C.byref(dp), *tail))
+        renderer.h, _stage.opt_ref(proj), int(aov_samples), C.byref(dp), *tail))
     return out

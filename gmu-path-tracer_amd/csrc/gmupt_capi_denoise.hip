@@ -40,24 +40,22 @@ template <class P> static int render_args(const char* fn, gmupt_renderer* r, uin
 }
 
 // gmupt_render_denoised; with `infill` gmupt_render_preview without a history: the infill stage between the framebuffer copy and the filter;
-// with `lensGuides` gmupt_render_denoised_lens: the records are those of gmupt_render_aovs_lens under that (checked) lens;
-// with `projGuides` gmupt_render_denoised_projected: those of gmupt_render_aovs_projected under that (checked) projection
+// with `guides` gmupt_render_denoised_lens / gmupt_render_denoised_projected: the records are what it renders (AovGuides, gmupt_internal.hpp)
 int render_denoised(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, const IfParams* infill, float* out_rgba, size_t bytes,
-                    gmupt_trace_info* info, const gmupt_lens* lensGuides, const gmupt_projection* projGuides)
+                    gmupt_trace_info* info, const AovGuides& guides)
 {
     if (info) std::memset(info, 0, sizeof(*info));
     if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer", fn);
     const uint32_t W = r->p.fbW, H = r->p.fbH;
     DnParams prm;
-    GMUPT_TRY(render_args(fn, r, aov_samples, out_rgba, bytes, [&] { return denoise_params(fn, p, prm); }, !lensGuides && !projGuides));
+    GMUPT_TRY(render_args(fn, r, aov_samples, out_rgba, bytes, [&] { return denoise_params(fn, p, prm); }, !guides));
     GMUPT_TRY(r->dnInput.grow(r->stream, (size_t)W * H * (sizeof(gmupt_aov) + 16)));
     if (infill) GMUPT_TRY(r->ifImage.grow(r->stream, (size_t)W * H * 16));
     gmupt_aov* aov = r->dnInput.as<gmupt_aov>();
     const float* beauty = reinterpret_cast<float*>(r->dnInput.as<char>() + (size_t)W * H * sizeof(gmupt_aov));
     gmupt_trace_info ai;
-    int rc = projGuides ? render_aovs_projected(fn, r, *projGuides, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai)
-           : lensGuides ? render_aovs_lens(fn, r, *lensGuides, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai)
-                        : gmupt_render_aovs(r, aov_samples, aov, (size_t)W * H * sizeof(gmupt_aov), &ai);
+    const size_t aovBytes = (size_t)W * H * sizeof(gmupt_aov);
+    int rc = guides ? guides(aov, aovBytes, &ai) : gmupt_render_aovs(r, aov_samples, aov, aovBytes, &ai);
     if (info) *info = ai;
     if (rc != GMUPT_OK) return rc;
     GMUPT_TRY(gmupt_copy_framebuffer_to_device(r, const_cast<float*>(beauty), (size_t)W * H * 16));

@@ -1,5 +1,5 @@
-// C-ABI of libgmupt.so: the lens-filtered AOV records (include/gmupt_lens_aov.h) -- gmupt_render_aovs_lens through pt_lens_aov.hip on the
-// chunk scratch and the query counters of gmupt_render_aovs, the host rule of its rays, and the denoiser on these records.
+// C-ABI of libgmupt.so: the lens-filtered AOV records (include/gmupt_lens_aov.h) -- gmupt_render_aovs_lens through pt_lens_aov.hip and the
+// chunk loop of gmupt_render_aovs (render_aov_chunks), the host rule of its rays, and the denoiser on these records.
 #include "gmupt_internal.hpp"
 
 // the lens of a call: the one given, checked as gmupt_renderer_set_lens checks it, or the renderer's (none attached: aperture 0)
@@ -10,35 +10,12 @@ static int call_lens(const char* fn, const gmupt_renderer* r, const gmupt_lens* 
     return GMUPT_OK;
 }
 
-int render_aovs_lens(const char* fn, gmupt_renderer* r, const gmupt_lens& lens, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info)
+// gmupt_render_aovs_lens under a checked lens, with fn as the name in its errors
+static int render_aovs_lens(const char* fn, gmupt_renderer* r, const gmupt_lens& lens, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info)
 {
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
-    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "%s: no camera set", fn);
-    if (!out || ((uintptr_t)out & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned output (16 bytes)", fn);
-    const uint32_t W = r->p.fbW, H = r->p.fbH;
-    uint32_t R;
-    GMUPT_TRY(aov_sample_plan(fn, "samples", W, samples, &R, false));
-    if (bytes < (size_t)W * H * sizeof(gmupt_aov)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu bytes for %ux%u records of 64 bytes", fn, bytes, W, H);
-    GMUPT_TRY(query_supported(r, fn));
-    GMUPT_TRY(query_buffers(r));
-    GMUPT_TRY(aov_chunk_scratch(r));
-    const RenderParams& p = r->p;
-    gmupt_ray* rays = r->aovRays.as<gmupt_ray>(); gmupt_hit* hits = r->aovHits.as<gmupt_hit>();
-    const uint32_t rowsPerChunk = GMUPT_AOV_CHUNK_RAYS / (W * R);   // >= 1: aov_sample_plan admitted the row
-    RenderParams q;
-    GMUPT_TRY(query_begin(r, &q));
-    for (uint32_t row = 0; row < H; row += rowsPerChunk) {
-        const uint32_t rows = std::min(rowsPerChunk, H - row), n = rows * W * R;
-        launch_laov_raygen(p.cam, lens, r->tile_x0(), r->tile_y0() + row, W, rows, samples, rays, r->stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(q.travCounters, 0, 128, r->stream));
-        launch_trace_wide(q, rays, n, hits, nullptr, 0, nullptr, p.cam.lightCount, r->stream);
-        HIP_TRY(hipGetLastError());
-        launch_laov_resolve(p, rows * W, samples, rays, hits, out + (size_t)row * W, r->stream);
-        HIP_TRY(hipGetLastError());
-    }
-    return query_end(r, fn, "records", info);
+    return render_aov_chunks(fn, r, samples, false, out, bytes, info,
+        [&](const AovRows& c) { launch_laov_raygen(r->p.cam, lens, r->tile_x0(), r->tile_y0() + c.row, c.W, c.rows, samples, c.rays, r->stream); },
+        [&](const AovRows& c) { launch_laov_resolve(r->p, c.rows * c.W, samples, c.rays, c.hits, out + (size_t)c.row * c.W, r->stream); });
 }
 
 extern "C" int gmupt_render_aovs_lens(gmupt_renderer* r, const gmupt_lens* lens_or_null, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info)
@@ -71,5 +48,6 @@ extern "C" int gmupt_render_denoised_lens(gmupt_renderer* r, const gmupt_lens* l
     if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer", fn);
     gmupt_lens lens;
     GMUPT_TRY(call_lens(fn, r, lens_or_null, &lens));
-    return render_denoised(fn, r, aov_samples, p, nullptr, out_rgba, bytes, info, &lens);
+    return render_denoised(fn, r, aov_samples, p, nullptr, out_rgba, bytes, info,
+                           [&](gmupt_aov* aov, size_t n, gmupt_trace_info* ai) { return render_aovs_lens(fn, r, lens, aov_samples, aov, n, ai); });
 }

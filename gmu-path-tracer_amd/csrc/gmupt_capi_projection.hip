@@ -1,6 +1,6 @@
 // C-ABI of libgmupt.so: the camera projections (include/gmupt_projection.h) -- the projection of a renderer (launched by run_iteration
-// through pt_projection.hip), the host rules, picking, and the AOV records and the denoiser under a projection, on the chunk scratch,
-// the resolve and the query counters of gmupt_render_aovs_lens.
+// through pt_projection.hip), the host rules, picking, and the AOV records and the denoiser under a projection: the chunk loop of
+// gmupt_render_aovs (render_aov_chunks) with this file's ray generation and the resolve of gmupt_render_aovs_lens.
 #include "gmupt_internal.hpp"
 
 static_assert(sizeof(gmupt_projection) == 16 && offsetof(gmupt_projection, fov) == 4 && offsetof(gmupt_projection, extent) == 8 &&
@@ -54,7 +54,7 @@ extern "C" int gmupt_projection_ray_host(const gmupt_camera_buffer* cam, const g
     const char* fn = "gmupt_projection_ray_host";
     if (!cam || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null camera or result", fn);
     GMUPT_TRY(projection_params(fn, proj));
-    projection_store(projection_fresh_ray(*cam, *proj, q, cx, cy), out);
+    store_ray(projection_fresh_ray(*cam, *proj, q, cx, cy), out);
     return GMUPT_OK;
 }
 
@@ -63,7 +63,7 @@ extern "C" int gmupt_projection_pick_ray(const gmupt_camera_buffer* cam, const g
     const char* fn = "gmupt_projection_pick_ray";
     if (!cam || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null camera or result", fn);
     GMUPT_TRY(projection_params(fn, proj));
-    projection_store(projection_pixel_ray(*cam, *proj, px, py), out);
+    store_ray(projection_pixel_ray(*cam, *proj, px, py), out);
     return GMUPT_OK;
 }
 
@@ -84,7 +84,7 @@ extern "C" int gmupt_aov_projected_ray(const gmupt_camera_buffer* cam, const gmu
     uint32_t R;
     GMUPT_TRY(aov_sample_plan(fn, "samples", 0, samples, &R, false));
     if (k >= R) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: ray %u of %u", fn, k, R);
-    projection_store(projection_aov_ray(*cam, *proj, x, y, samples, k), out);
+    store_ray(projection_aov_ray(*cam, *proj, x, y, samples, k), out);
     return GMUPT_OK;
 }
 
@@ -109,35 +109,12 @@ extern "C" int gmupt_debug_read_aov_rays(gmupt_renderer* r, gmupt_ray* out, uint
     return copy_sync(out, r->aovRays.ptr, (size_t)count * sizeof(gmupt_ray), hipMemcpyDeviceToHost, r->stream);
 }
 
-int render_aovs_projected(const char* fn, gmupt_renderer* r, const gmupt_projection& proj, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info)
+// gmupt_render_aovs_projected under a checked projection, with fn as the name in its errors
+static int render_aovs_projected(const char* fn, gmupt_renderer* r, const gmupt_projection& proj, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info)
 {
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
-    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "%s: no camera set", fn);
-    if (!out || ((uintptr_t)out & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned output (16 bytes)", fn);
-    const uint32_t W = r->p.fbW, H = r->p.fbH;
-    uint32_t R;
-    GMUPT_TRY(aov_sample_plan(fn, "samples", W, samples, &R, false));
-    if (bytes < (size_t)W * H * sizeof(gmupt_aov)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu bytes for %ux%u records of 64 bytes", fn, bytes, W, H);
-    GMUPT_TRY(query_supported(r, fn));
-    GMUPT_TRY(query_buffers(r));
-    GMUPT_TRY(aov_chunk_scratch(r));
-    const RenderParams& p = r->p;
-    gmupt_ray* rays = r->aovRays.as<gmupt_ray>(); gmupt_hit* hits = r->aovHits.as<gmupt_hit>();
-    const uint32_t rowsPerChunk = GMUPT_AOV_CHUNK_RAYS / (W * R);   // >= 1: aov_sample_plan admitted the row
-    RenderParams q;
-    GMUPT_TRY(query_begin(r, &q));
-    for (uint32_t row = 0; row < H; row += rowsPerChunk) {
-        const uint32_t rows = std::min(rowsPerChunk, H - row), n = rows * W * R;
-        launch_paov_raygen(p.cam, proj, r->tile_x0(), r->tile_y0() + row, W, rows, samples, rays, r->stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(q.travCounters, 0, 128, r->stream));
-        launch_trace_wide(q, rays, n, hits, nullptr, 0, nullptr, p.cam.lightCount, r->stream);
-        HIP_TRY(hipGetLastError());
-        launch_laov_resolve(p, rows * W, samples, rays, hits, out + (size_t)row * W, r->stream);
-        HIP_TRY(hipGetLastError());
-    }
-    return query_end(r, fn, "records", info);
+    return render_aov_chunks(fn, r, samples, false, out, bytes, info,
+        [&](const AovRows& c) { launch_paov_raygen(r->p.cam, proj, r->tile_x0(), r->tile_y0() + c.row, c.W, c.rows, samples, c.rays, r->stream); },
+        [&](const AovRows& c) { launch_laov_resolve(r->p, c.rows * c.W, samples, c.rays, c.hits, out + (size_t)c.row * c.W, r->stream); });
 }
 
 extern "C" int gmupt_render_aovs_projected(gmupt_renderer* r, const gmupt_projection* proj_or_null, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info)
@@ -158,5 +135,6 @@ extern "C" int gmupt_render_denoised_projected(gmupt_renderer* r, const gmupt_pr
     if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null renderer", fn);
     gmupt_projection proj;
     GMUPT_TRY(call_projection(fn, r, proj_or_null, &proj));
-    return render_denoised(fn, r, aov_samples, p, nullptr, out_rgba, bytes, info, nullptr, &proj);
+    return render_denoised(fn, r, aov_samples, p, nullptr, out_rgba, bytes, info,
+                           [&](gmupt_aov* aov, size_t n, gmupt_trace_info* ai) { return render_aovs_projected(fn, r, proj, aov_samples, aov, n, ai); });
 }

@@ -78,11 +78,7 @@ extern "C" int gmupt_camera_pick_ray(const gmupt_camera_buffer* cam, float px, f
 {
     if (!cam || !out) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_camera_pick_ray: null argument");
     // newPath.hlsl:36-39 with the jitter at 0: (x + 0) * pixelSize is x * pixelSize for every float x
-    const f3 dir = camera_ray_direction(*cam, px, py);
-    std::memset(out, 0, sizeof(*out));
-    for (int k = 0; k < 3; k++) out->origin[k] = cam->position[k];
-    out->direction[0] = dir.x; out->direction[1] = dir.y; out->direction[2] = dir.z;
-    out->tmax = std::numeric_limits<float>::max();   // FLT_MAX: the reference's starting distance (structs.h:9)
+    store_ray(mk3(cam->position[0], cam->position[1], cam->position[2]), camera_ray_direction(*cam, px, py), out);
     return GMUPT_OK;
 }
 
@@ -136,40 +132,47 @@ int aov_chunk_scratch(gmupt_renderer* r)
     return GMUPT_OK;
 }
 
+// The one chunk loop behind every gmupt_render_aovs* (gmupt_internal.hpp states the contract).  The order of the checks is part of it.
+int render_aov_chunks(const char* fn, gmupt_renderer* r, uint32_t samples, bool centre, gmupt_aov* out, size_t bytes, gmupt_trace_info* info,
+                      const AovStage& raygen, const AovStage& after_cast)
+{
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "%s: no scene bound", fn);
+    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "%s: no camera set", fn);
+    if (!out || ((uintptr_t)out & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: null or misaligned output (16 bytes)", fn);
+    const uint32_t W = r->p.fbW, H = r->p.fbH;
+    uint32_t R;
+    GMUPT_TRY(aov_sample_plan(fn, "samples", W, samples, &R, centre));
+    if (bytes < (size_t)W * H * sizeof(gmupt_aov)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "%s: %zu bytes for %ux%u records of 64 bytes", fn, bytes, W, H);
+    GMUPT_TRY(query_supported(r, fn));
+    GMUPT_TRY(query_buffers(r));
+    GMUPT_TRY(aov_chunk_scratch(r));
+    const uint32_t rowsPerChunk = GMUPT_AOV_CHUNK_RAYS / (W * R);   // >= 1: aov_sample_plan admitted the row
+    RenderParams q;
+    GMUPT_TRY(query_begin(r, &q));
+    for (uint32_t row = 0; row < H; row += rowsPerChunk) {
+        const AovRows c{ row, std::min(rowsPerChunk, H - row), W, R, r->aovRays.as<gmupt_ray>(), r->aovHits.as<gmupt_hit>() };
+        raygen(c);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(q.travCounters, 0, 128, r->stream));
+        launch_trace_wide(q, c.rays, c.rows * W * R, c.hits, nullptr, 0, nullptr, r->p.cam.lightCount, r->stream);
+        HIP_TRY(hipGetLastError());
+        after_cast(c);
+        HIP_TRY(hipGetLastError());
+    }
+    return query_end(r, fn, "records", info);
+}
+
 // gmupt_render_aovs, and with motion != nullptr gmupt_render_aovs_motion: k_mv_resolve follows k_aov_resolve on every chunk's hits
 static int render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info, const float* prevVerts, gmupt_motion* motion)
 {
     if (!r) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: null renderer");
-    if (!r->sceneBound) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_aovs: no scene bound");
-    if (!r->cameraSet) return fail(GMUPT_ERR_NOT_BOUND, "gmupt_render_aovs: no camera set");
-    if (!out || ((uintptr_t)out & 15u)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: null or misaligned output (16 bytes)");
-    const uint32_t W = r->p.fbW, H = r->p.fbH;
-    uint32_t R;
-    GMUPT_TRY(aov_sample_plan("gmupt_render_aovs", "samples", W, samples, &R));
-    if (bytes < (size_t)W * H * sizeof(gmupt_aov)) return fail(GMUPT_ERR_INVALID_ARGUMENT, "gmupt_render_aovs: %zu bytes for %ux%u records of 64 bytes", bytes, W, H);
-    GMUPT_TRY(query_supported(r, "gmupt_render_aovs"));
-    GMUPT_TRY(query_buffers(r));
-    GMUPT_TRY(aov_chunk_scratch(r));
-    const RenderParams& p = r->p;
-    gmupt_ray* rays = r->aovRays.as<gmupt_ray>(); gmupt_hit* hits = r->aovHits.as<gmupt_hit>();
-    const uint32_t rowsPerChunk = GMUPT_AOV_CHUNK_RAYS / (W * R);
-    RenderParams q;
-    GMUPT_TRY(query_begin(r, &q));
-    for (uint32_t row = 0; row < H; row += rowsPerChunk) {
-        const uint32_t rows = std::min(rowsPerChunk, H - row), n = rows * W * R;
-        launch_aov_raygen(p.cam, r->tile_x0(), r->tile_y0() + row, W, rows, samples, R, rays, r->stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(q.travCounters, 0, 128, r->stream));
-        launch_trace_wide(q, rays, n, hits, nullptr, 0, nullptr, p.cam.lightCount, r->stream);
-        HIP_TRY(hipGetLastError());
-        launch_aov_resolve(p, rows * W, samples, R, rays, hits, out + (size_t)row * W, r->stream);
-        HIP_TRY(hipGetLastError());
-        if (motion) {
-            launch_mv_resolve(p.scene, prevVerts, rows * W, R, hits, out + (size_t)row * W, motion + (size_t)row * W, r->stream);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return query_end(r, "gmupt_render_aovs", "records", info);
+    return render_aov_chunks("gmupt_render_aovs", r, samples, true, out, bytes, info,
+        [&](const AovRows& c) { launch_aov_raygen(r->p.cam, r->tile_x0(), r->tile_y0() + c.row, c.W, c.rows, samples, c.R, c.rays, r->stream); },
+        [&](const AovRows& c) {
+            launch_aov_resolve(r->p, c.rows * c.W, samples, c.R, c.rays, c.hits, out + (size_t)c.row * c.W, r->stream);
+            if (motion) launch_mv_resolve(r->p.scene, prevVerts, c.rows * c.W, c.R, c.hits, out + (size_t)c.row * c.W, motion + (size_t)c.row * c.W, r->stream);
+        });
 }
 
 extern "C" int gmupt_render_aovs(gmupt_renderer* r, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info)

@@ -25,6 +25,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <new>
 #include <string>
@@ -243,13 +244,18 @@ int projection_params(const char* fn, const gmupt_projection* proj);            
 int temporal_denoise(const char* fn, gmupt_temporal* t, const float* beauty_rgba, const gmupt_aov* aov, const gmupt_motion* motion,
                      const gmupt_camera_buffer* cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, int new_accumulation,
                      const gmupt_temporal_params* p, const IfParams* infill, float* out_rgba, size_t out_bytes, float* ms);
+// the guide records of render_denoised: empty = gmupt_render_aovs, with its centre ray; otherwise what renders the s*s-ray records of a
+// lens or a projection (render_aov_chunks with centre = false) into (out, bytes) under the caller's name
+using AovGuides = std::function<int(gmupt_aov* out, size_t bytes, gmupt_trace_info* info)>;
 int render_denoised(const char* fn, gmupt_renderer* r, uint32_t aov_samples, const gmupt_denoise_params* p, const IfParams* infill, float* out_rgba, size_t bytes,
-                    gmupt_trace_info* info, const gmupt_lens* lensGuides = nullptr,    // lensGuides: the records of gmupt_render_aovs_lens under that lens
-                    const gmupt_projection* projGuides = nullptr);                     // projGuides: those of gmupt_render_aovs_projected under that projection
-// gmupt_capi_lens_aov.hip: gmupt_render_aovs_lens under a checked lens, with fn as the name in its errors
-int render_aovs_lens(const char* fn, gmupt_renderer* r, const gmupt_lens& lens, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info);
-// gmupt_capi_projection.hip: gmupt_render_aovs_projected under a checked projection, with fn as the name in its errors
-int render_aovs_projected(const char* fn, gmupt_renderer* r, const gmupt_projection& proj, uint32_t samples, gmupt_aov* out, size_t bytes, gmupt_trace_info* info);
+                    gmupt_trace_info* info, const AovGuides& guides = nullptr);
+// gmupt_capi_query.hip: the AOV records of the renderer's rectangle, chunk by chunk of whole pixel rows on the chunk scratch, as one timed
+// span of cast queries; every gmupt_render_aovs* is a call of it.  fn: the name in its errors; centre: the sample plan (aov_sample_plan).
+// Per chunk: raygen writes c.rays, the wide ray cast fills c.hits, after_cast resolves them into the records of rows c.row .. + c.rows
+struct AovRows { uint32_t row, rows, W, R; gmupt_ray* rays; gmupt_hit* hits; };
+using AovStage = std::function<void(const AovRows& c)>;
+int render_aov_chunks(const char* fn, gmupt_renderer* r, uint32_t samples, bool centre, gmupt_aov* out, size_t bytes, gmupt_trace_info* info,
+                      const AovStage& raygen, const AovStage& after_cast);
 int render_denoised_temporal(const char* fn, bool poses, gmupt_renderer* r, gmupt_temporal* t, uint32_t aov_samples, const gmupt_temporal_params* p,
                              const IfParams* infill, float* out_rgba, size_t bytes, gmupt_trace_info* info);
 // gmupt_capi_infill.hip: grows the renderer's infill scratch for the image (the one place that does) and enqueues the stage

@@ -101,13 +101,8 @@ __global__ __launch_bounds__(kSumRun) void k_ad_emit(const float* __restrict__ e
 __global__ __launch_bounds__(kBlock) void k_ad_retarget(RenderParams p, const uint32_t* __restrict__ list, uint32_t count, uint32_t uniformEvery)
 {
     const uint32_t queueIndex = blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t qc0 = p.qc[QC_NEWPATH];
-    const uint32_t nNew = qc0 < p.L ? qc0 : p.L;                              // newPath.hlsl:21-25, as k_material
-    if (queueIndex >= nNew || count == 0u) return;
-    const uint32_t index = p.queues[(size_t)Q_NEWPATH * p.P + queueIndex];
-    if (index >= p.L) return;
-    const uint32_t lastPath = p.qc[QC_LASTPATHCNT];                          // :19 -- the ray cast advances it, later
-    if (p.budget && (uint32_t)(lastPath + queueIndex) >= p.budget) return;   // retired by stage_new_path
+    uint32_t index, lastPath;
+    if (count == 0u || !fresh_path_slot(p, queueIndex, index, lastPath)) return;   // an empty plan re-aims nothing
     const uint32_t w = p.tileEnabled ? p.fbW : cam_width(p.cam), h = p.tileEnabled ? p.fbH : cam_height(p.cam);
     const uint32_t k = lastPath + queueIndex;
     // one rectangle for both cases: w x h as stage_new_path has it (run_iteration has checked the plan against it)

@@ -1,42 +1,32 @@
 // AOV buffers (gmupt_render_aovs, include/gmupt.h): the per-pixel G-buffer of the camera rays, in three launches per chunk of pixel rows
 //
 //   k_aov_raygen   one thread per ray: the R rays of every pixel of the chunk as gmupt_ray records, pixel-major (ray k of chunk pixel j at
-//                  j * R + k) -- the centre ray, then the s*s stratified rays
+//                  j * R + k) -- the centre ray, then the s*s stratified rays.  The body is aov_raygen (pt_camera_rays.hpp), shared
+//                  with k_laov_raygen and k_paov_raygen; the centre ray is this rule's k = 0 and the R that the launcher passes
 //   k_cast_w       the QueryIO instantiation of the wide ray cast (launch_trace_wide, pt_traverse_wide.hip): one gmupt_hit per ray
 //   k_aov_resolve  one thread per pixel: the R hits in order, the hit shading of k_logic (pt_shading.hpp), the ordered mean of the filtered
 //                  planes, and the 64-byte record as four float4 stores
 //
 // Arithmetic as everywhere else: binary32 in the stated order, no contraction (build.py flags), so the records are the CPU oracle's bits.
-#include "pt_device.hpp"
-#include "detmath.hpp"
-#include "pt_shading.hpp"
+#include "pt_camera_rays.hpp"
 #include "pt_launch.hpp"
 
 namespace gmupt {
 
 static_assert(sizeof(gmupt_aov) == 64, "gmupt_aov is four float4");
 
-struct AovRaygen {
+// ray k of whole-frame pixel (x, y): the pinhole ray through the coordinates of aov_ray_coords, k = 0 the centre ray
+struct PinholeAovRule {
     gmupt_camera_buffer cam;
-    uint32_t x0, y0;     // whole-frame coordinates of the chunk's first pixel
-    uint32_t width;      // pixels per row
-    uint32_t samples, R; // s, rays per pixel
-    uint32_t n;          // rays of the chunk (rows * width * R <= GMUPT_AOV_CHUNK_RAYS)
-    float4* rays;        // 2 float4 per gmupt_ray
+    __device__ __forceinline__ CamRay operator()(uint32_t x, uint32_t y, uint32_t s, uint32_t k) const
+    {
+        float px, py;
+        aov_ray_coords(x, y, s, k, px, py);
+        return CamRay{ mk3(cam.position[0], cam.position[1], cam.position[2]), camera_ray_direction(cam, px, py) };
+    }
 };
 
-__global__ __launch_bounds__(kBlock) void k_aov_raygen(AovRaygen g)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= g.n) return;
-    const uint32_t pix = i / g.R, k = i - pix * g.R;
-    const uint32_t ly = pix / g.width, lx = pix - ly * g.width;
-    float px, py;
-    aov_ray_coords(g.x0 + lx, g.y0 + ly, g.samples, k, px, py);
-    const f3 d = camera_ray_direction(g.cam, px, py);
-    g.rays[2 * (size_t)i] = make_float4(g.cam.position[0], g.cam.position[1], g.cam.position[2], kFltMax);   // tmax = FLT_MAX (structs.h:9)
-    g.rays[2 * (size_t)i + 1] = make_float4(d.x, d.y, d.z, 0.0f);
-}
+__global__ __launch_bounds__(kBlock) void k_aov_raygen(AovRaygen<PinholeAovRule> g) { aov_raygen(g.chunk, g.rule); }
 
 struct AovResolve {
     SceneView scene;
@@ -48,22 +38,6 @@ struct AovResolve {
     float4* out;           // 4 float4 per pixel: the chunk's first record
 };
 
-// the shading of one ray's closest hit (include/gmupt.h): albedo, normal, metallic, roughness; returns true for a triangle hit without a nearer light
-__device__ __forceinline__ bool aov_shade(const AovResolve& a, const float4 h0, const float4 h1, f3 dir, f3& albedo, f3& normal, float& metallic, float& rough)
-{
-    const int tri = (int)__builtin_bit_cast(uint32_t, h0.w);
-    const uint32_t light = __builtin_bit_cast(uint32_t, h1.x);
-    normal = mk3(0.0f, 0.0f, 0.0f); metallic = 0.0f; rough = 0.0f;
-    if (light > 0) { albedo = sample_light_color(a.scene.lights, light); return false; }
-    if (tri < 0) { albedo = mk3(a.env[0], a.env[1], a.env[2]); return false; }
-    // the record finish_extension_ray stores: vertex indices and material of the triangle, bary = (1 - u - v, u, v)
-    const int4 T = *reinterpret_cast<const int4*>(&a.scene.tris[tri]);
-    const HitProps hp = material_hit_properties(a.scene, (uint32_t)T.x, (uint32_t)T.y, (uint32_t)T.z, (uint32_t)T.w,
-                                                mk3(1.0f - h0.y - h0.z, h0.y, h0.z), [&]() { return dir; });
-    albedo = hp.color; normal = hp.normal; metallic = hp.metallic; rough = hp.roughness;
-    return true;
-}
-
 __global__ __launch_bounds__(kBlock) void k_aov_resolve(AovResolve a)
 {
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
@@ -74,7 +48,7 @@ __global__ __launch_bounds__(kBlock) void k_aov_resolve(AovResolve a)
     const float4 h0 = a.hits[2 * base], h1 = a.hits[2 * base + 1];
     const f3 o = mk3(o0.x, o0.y, o0.z), d = mk3(d0.x, d0.y, d0.z);
     f3 albedo, normal; float metallic, rough;
-    const bool surface = aov_shade(a, h0, h1, d, albedo, normal, metallic, rough);
+    const bool surface = aov_shade(a.scene, a.env, h0, h1, d, albedo, normal, metallic, rough);
     uint32_t coverage = surface ? 1u : 0u;
     const float t = h0.x;
     const bool found = (int)__builtin_bit_cast(uint32_t, h0.w) >= 0 || __builtin_bit_cast(uint32_t, h1.x) > 0;
@@ -87,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void k_aov_resolve(AovResolve a)
             const float4 dk = a.rays[2 * (base + k) + 1];
             const float4 g0 = a.hits[2 * (base + k)], g1 = a.hits[2 * (base + k) + 1];
             f3 ak, nk; float mk, rk;
-            coverage += aov_shade(a, g0, g1, mk3(dk.x, dk.y, dk.z), ak, nk, mk, rk) ? 1u : 0u;
+            coverage += aov_shade(a.scene, a.env, g0, g1, mk3(dk.x, dk.y, dk.z), ak, nk, mk, rk) ? 1u : 0u;
             sa = sa + ak; sn = sn + nk;
         }
         const float inv = (float)(a.samples * a.samples);
@@ -105,10 +79,7 @@ __global__ __launch_bounds__(kBlock) void k_aov_resolve(AovResolve a)
 void launch_aov_raygen(const gmupt_camera_buffer& cam, uint32_t x0, uint32_t y0, uint32_t width, uint32_t rows, uint32_t samples, uint32_t R,
                        gmupt_ray* rays, hipStream_t s)
 {
-    AovRaygen g;
-    g.cam = cam; g.x0 = x0; g.y0 = y0; g.width = width; g.samples = samples; g.R = R; g.n = rows * width * R;
-    g.rays = reinterpret_cast<float4*>(rays);
-    if (g.n) hipLaunchKernelGGL(k_aov_raygen, dim3((g.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, g);
+    launch_raygen_kernel(k_aov_raygen, PinholeAovRule{ cam }, x0, y0, width, rows, samples, R, rays, s);
 }
 
 void launch_aov_resolve(const RenderParams& p, uint32_t npix, uint32_t samples, uint32_t R, const gmupt_ray* rays, const gmupt_hit* hits,

@@ -1,4 +1,5 @@
-// Small device helpers shared by the shading kernels (pt_kernels.hip) and the ray-cast kernels (pt_traverse.hip), and the image stages' pixel tile.
+// Small device helpers shared by the shading kernels (pt_kernels.hip) and the ray-cast kernels (pt_traverse.hip), the guards of the fresh-path
+// kernels (the k_*_retarget), and the image stages' pixel tile.
 #pragma once
 #include "pt_device.hpp"
 #include "detmath.hpp"
@@ -11,6 +12,21 @@ __device__ __forceinline__ void stf(const RenderParams& p, uint32_t f, uint32_t 
 __device__ __forceinline__ void stu(const RenderParams& p, uint32_t f, uint32_t i, uint32_t v) { p.state[(size_t)f * p.PS + i] = __builtin_bit_cast(float, v); }
 __device__ __forceinline__ f3 ld3(const RenderParams& p, uint32_t f, uint32_t i) { return mk3(ldf(p, f, i), ldf(p, f + 1, i), ldf(p, f + 2, i)); }
 __device__ __forceinline__ void st3(const RenderParams& p, uint32_t f, uint32_t i, f3 v) { stf(p, f, i, v.x); stf(p, f + 1, i, v.y); stf(p, f + 2, i, v.z); }
+
+// The guards of a kernel that runs between k_material and the ray cast with one thread per entry of the new-path queue (k_ad_retarget,
+// k_lens_retarget, k_proj_retarget): whether entry `queueIndex` is a fresh camera path that is still alive, with its slot in `index`
+// and the path count before this iteration's fresh paths in `lastPath`
+__device__ __forceinline__ bool fresh_path_slot(const RenderParams& p, uint32_t queueIndex, uint32_t& index, uint32_t& lastPath)
+{
+    const uint32_t qc0 = p.qc[QC_NEWPATH];
+    const uint32_t nNew = qc0 < p.L ? qc0 : p.L;                              // newPath.hlsl:21-25, as k_material
+    if (queueIndex >= nNew) return false;
+    index = p.queues[(size_t)Q_NEWPATH * p.P + queueIndex];
+    if (index >= p.L) return false;
+    lastPath = p.qc[QC_LASTPATHCNT];                                         // :19 -- the ray cast advances it, later
+    if (p.budget && (uint32_t)(lastPath + queueIndex) >= p.budget) return false;   // retired by stage_new_path
+    return true;
+}
 
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 // number of set bits of a 64-bit wave mask below this lane (the reference's NvWaveMultiPrefixExclusiveAdd(1, ballot))

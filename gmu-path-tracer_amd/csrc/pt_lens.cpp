@@ -2,18 +2,11 @@
 // path (pt_lens.hip).  The arithmetic is pt_lens.hpp, shared with the kernel.
 #include "pt_lens.hpp"
 
-#include <cstring>
-#include <limits>
-
 namespace gmupt {
 
 void lens_ray_host(const gmupt_camera_buffer& cam, const gmupt_lens& lens, uint32_t q, uint32_t cx, uint32_t cy, gmupt_ray* out)
 {
-    const LensRay r = lens_ray(cam, lens.aperture_radius, lens.focus_distance, q, cx, cy);
-    std::memset(out, 0, sizeof(*out));
-    out->origin[0] = r.origin.x; out->origin[1] = r.origin.y; out->origin[2] = r.origin.z;
-    out->direction[0] = r.direction.x; out->direction[1] = r.direction.y; out->direction[2] = r.direction.z;
-    out->tmax = std::numeric_limits<float>::max();   // FLT_MAX, as gmupt_camera_pick_ray
+    store_ray(lens_ray(cam, lens.aperture_radius, lens.focus_distance, q, cx, cy), out);
 }
 
 float lens_focus_depth(const gmupt_camera_buffer& cam, const float dir[3], float t)

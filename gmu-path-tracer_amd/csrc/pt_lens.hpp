@@ -3,16 +3,13 @@
 // (build.py), sin / cos / sqrt from detmath.hpp.  pt_kernels.hip does not include this file: step 1's lines are stage_new_path's,
 // restated, because sharing them through a header moved k_material's register allocation (pt_adaptive.hip).
 #pragma once
-#include "pt_device.hpp"
+#include "pt_camera_rays.hpp"     // CamRay, store_ray
 #include "../../include/gmupt_lens.h"
-#include "detmath.hpp"
 
 namespace gmupt {
 
-struct LensRay { f3 origin, direction; };
-
 // the ray of the fresh camera path at entry q of the new-path queue whose screen coordinate is the whole-frame pixel (cx, cy)
-GM_HD LensRay lens_ray(const gmupt_camera_buffer& cam, float apertureRadius, float focusDistance, uint32_t q, uint32_t cx, uint32_t cy)
+GM_HD CamRay lens_ray(const gmupt_camera_buffer& cam, float apertureRadius, float focusDistance, uint32_t q, uint32_t cx, uint32_t cy)
 {
     // 1. the pinhole ray (newPath.hlsl:27,36-39)
     Rng g; g.seed(q, cam.randomSeed[0], cam.randomSeed[1]);
@@ -40,14 +37,14 @@ GM_HD LensRay lens_ray(const gmupt_camera_buffer& cam, float apertureRadius, flo
     const float t = focusDistance / dot3(d, fn);
     const f3 Pf = pos + d * t;
     // 5. the new ray
-    LensRay r;
+    CamRay r;
     r.origin = (pos + right * lx) + up * ly;
     r.direction = normalize3(Pf - r.origin);
     return r;
 }
 
 // ---- host side (pt_lens.cpp)
-// gmupt_lens_ray_host with checked arguments: the rule as a gmupt_ray (tmax = FLT_MAX, pad = 0)
+// gmupt_lens_ray_host with checked arguments: the rule as a gmupt_ray (store_ray)
 void lens_ray_host(const gmupt_camera_buffer& cam, const gmupt_lens& lens, uint32_t q, uint32_t cx, uint32_t cy, gmupt_ray* out);
 // gmupt_lens_focus_at: the depth along the forward axis fn of step 3 of the point at distance t on a ray of direction `dir` from the camera
 float lens_focus_depth(const gmupt_camera_buffer& cam, const float dir[3], float t);

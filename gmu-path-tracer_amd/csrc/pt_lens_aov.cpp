@@ -2,18 +2,11 @@
 // (pt_lens_aov.hip).  The arithmetic is pt_lens_aov.hpp, shared with the kernel.
 #include "pt_lens_aov.hpp"
 
-#include <cstring>
-#include <limits>
-
 namespace gmupt {
 
 void lens_aov_ray_host(const gmupt_camera_buffer& cam, const gmupt_lens& lens, uint32_t x, uint32_t y, uint32_t samples, uint32_t k, gmupt_ray* out)
 {
-    const LensRay r = lens_aov_ray(cam, lens.aperture_radius, lens.focus_distance, x, y, samples, k);
-    std::memset(out, 0, sizeof(*out));
-    out->origin[0] = r.origin.x; out->origin[1] = r.origin.y; out->origin[2] = r.origin.z;
-    out->direction[0] = r.direction.x; out->direction[1] = r.direction.y; out->direction[2] = r.direction.z;
-    out->tmax = std::numeric_limits<float>::max();   // FLT_MAX, as gmupt_aov_ray
+    store_ray(lens_aov_ray(cam, lens.aperture_radius, lens.focus_distance, x, y, samples, k), out);
 }
 
 } // namespace gmupt

@@ -9,32 +9,19 @@
 //                   texture reads of every sample; the twelve running sums stay in registers, no LDS, no scratch, no atomics.  The
 //                   k = 0 ray is read again after the loop by the few pixels without a surface sample instead of being kept live.
 //
-// Arithmetic as everywhere else: binary32 in the stated order, no contraction (build.py flags).  pt_aov.hip is not touched: the
-// shading of one sample is its aov_shade, restated here, so that k_aov_resolve stays the instructions it was.
+// Arithmetic as everywhere else: binary32 in the stated order, no contraction (build.py flags).  The ray generation's body and the
+// shading of one sample are pt_camera_rays.hpp's, shared with pt_aov.hip; the record rule is this file's own.
 #include "pt_lens_aov.hpp"
 
 namespace gmupt {
 
-struct LaovRaygen {
+struct LensAovRule {
     gmupt_camera_buffer cam;
     float apertureRadius, focusDistance;
-    uint32_t x0, y0;     // whole-frame coordinates of the chunk's first pixel
-    uint32_t width;      // pixels per row
-    uint32_t samples, R; // s, rays per pixel (s*s)
-    uint32_t n;          // rays of the chunk (rows * width * R <= GMUPT_AOV_CHUNK_RAYS)
-    float4* rays;        // 2 float4 per gmupt_ray
+    __device__ __forceinline__ CamRay operator()(uint32_t x, uint32_t y, uint32_t s, uint32_t k) const { return lens_aov_ray(cam, apertureRadius, focusDistance, x, y, s, k); }
 };
 
-__global__ __launch_bounds__(kBlock) void k_laov_raygen(LaovRaygen g)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= g.n) return;
-    const uint32_t pix = i / g.R, k = i - pix * g.R;
-    const uint32_t ly = pix / g.width, lx = pix - ly * g.width;
-    const LensRay r = lens_aov_ray(g.cam, g.apertureRadius, g.focusDistance, g.x0 + lx, g.y0 + ly, g.samples, k);
-    g.rays[2 * (size_t)i] = make_float4(r.origin.x, r.origin.y, r.origin.z, kFltMax);   // tmax = FLT_MAX
-    g.rays[2 * (size_t)i + 1] = make_float4(r.direction.x, r.direction.y, r.direction.z, 0.0f);
-}
+__global__ __launch_bounds__(kBlock) void k_laov_raygen(AovRaygen<LensAovRule> g) { aov_raygen(g.chunk, g.rule); }
 
 struct LaovResolve {
     SceneView scene;
@@ -45,21 +32,6 @@ struct LaovResolve {
     const float4* hits;
     float4* out;           // 4 float4 per pixel: the chunk's first record
 };
-
-// the shading of one ray's closest hit, aov_shade of pt_aov.hip: albedo, normal, metallic, roughness; true for a surface sample
-__device__ __forceinline__ bool laov_shade(const LaovResolve& a, const float4 h0, const float4 h1, f3 dir, f3& albedo, f3& normal, float& metallic, float& rough)
-{
-    const int tri = (int)__builtin_bit_cast(uint32_t, h0.w);
-    const uint32_t light = __builtin_bit_cast(uint32_t, h1.x);
-    normal = mk3(0.0f, 0.0f, 0.0f); metallic = 0.0f; rough = 0.0f;
-    if (light > 0) { albedo = sample_light_color(a.scene.lights, light); return false; }
-    if (tri < 0) { albedo = mk3(a.env[0], a.env[1], a.env[2]); return false; }
-    const int4 T = *reinterpret_cast<const int4*>(&a.scene.tris[tri]);
-    const HitProps hp = material_hit_properties(a.scene, (uint32_t)T.x, (uint32_t)T.y, (uint32_t)T.z, (uint32_t)T.w,
-                                                mk3(1.0f - h0.y - h0.z, h0.y, h0.z), [&]() { return dir; });
-    albedo = hp.color; normal = hp.normal; metallic = hp.metallic; rough = hp.roughness;
-    return true;
-}
 
 __global__ __launch_bounds__(kBlock) void k_laov_resolve(LaovResolve a)
 {
@@ -76,7 +48,7 @@ __global__ __launch_bounds__(kBlock) void k_laov_resolve(LaovResolve a)
         const float4 g0 = a.hits[2 * (base + k)], g1 = a.hits[2 * (base + k) + 1];
         const f3 o = mk3(ok.x, ok.y, ok.z), d = mk3(dk.x, dk.y, dk.z);
         f3 ak, nk; float mk, rk;
-        const bool surface = laov_shade(a, g0, g1, d, ak, nk, mk, rk);
+        const bool surface = aov_shade(a.scene, a.env, g0, g1, d, ak, nk, mk, rk);
         sa = sa + ak; sn = sn + nk;
         if (surface) {
             if (coverage == 0) { triangle = g0.w; material = g1.y; }
@@ -115,11 +87,7 @@ __global__ __launch_bounds__(kBlock) void k_laov_resolve(LaovResolve a)
 void launch_laov_raygen(const gmupt_camera_buffer& cam, const gmupt_lens& lens, uint32_t x0, uint32_t y0, uint32_t width, uint32_t rows, uint32_t samples,
                         gmupt_ray* rays, hipStream_t s)
 {
-    LaovRaygen g;
-    g.cam = cam; g.apertureRadius = lens.aperture_radius; g.focusDistance = lens.focus_distance;
-    g.x0 = x0; g.y0 = y0; g.width = width; g.samples = samples; g.R = samples * samples; g.n = rows * width * g.R;
-    g.rays = reinterpret_cast<float4*>(rays);
-    if (g.n) hipLaunchKernelGGL(k_laov_raygen, dim3((g.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, g);
+    launch_raygen_kernel(k_laov_raygen, LensAovRule{ cam, lens.aperture_radius, lens.focus_distance }, x0, y0, width, rows, samples, samples * samples, rays, s);
 }
 
 void launch_laov_resolve(const RenderParams& p, uint32_t npix, uint32_t samples, const gmupt_ray* rays, const gmupt_hit* hits, gmupt_aov* out, hipStream_t s)

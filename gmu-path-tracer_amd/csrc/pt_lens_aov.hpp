@@ -4,14 +4,13 @@
 // stratum in place of the two draws: lens_ray keeps its own copy, as it keeps stage_new_path's, so that k_lens_retarget stays the
 // instructions it was.
 #pragma once
-#include "pt_shading.hpp"      // camera_ray_direction, aov_ray_coords
-#include "pt_lens.hpp"
+#include "pt_lens.hpp"         // and through it pt_shading.hpp: camera_ray_direction, aov_ray_coords
 #include "../../include/gmupt_lens_aov.h"
 
 namespace gmupt {
 
 // ray k (0 .. s*s - 1) of whole-frame pixel (x, y) at s samples per axis
-GM_HD LensRay lens_aov_ray(const gmupt_camera_buffer& cam, float apertureRadius, float focusDistance, uint32_t x, uint32_t y, uint32_t s, uint32_t k)
+GM_HD CamRay lens_aov_ray(const gmupt_camera_buffer& cam, float apertureRadius, float focusDistance, uint32_t x, uint32_t y, uint32_t s, uint32_t k)
 {
     // 1. the pixel-filter cell (a, b): the stratified AOV ray k + 1, or the pixel centre at s == 1
     const uint32_t a = k % s, b = k / s;
@@ -38,14 +37,14 @@ GM_HD LensRay lens_aov_ray(const gmupt_camera_buffer& cam, float apertureRadius,
     const float t = focusDistance / dot3(d, fn);
     const f3 Pf = pos + d * t;
     // 5. the ray
-    LensRay r;
+    CamRay r;
     r.origin = (pos + right * lx) + up * ly;
     r.direction = normalize3(Pf - r.origin);
     return r;
 }
 
 // ---- host side (pt_lens_aov.cpp)
-// gmupt_aov_lens_ray with checked arguments: the rule as a gmupt_ray (tmax = FLT_MAX, pad = 0)
+// gmupt_aov_lens_ray with checked arguments: the rule as a gmupt_ray (store_ray)
 void lens_aov_ray_host(const gmupt_camera_buffer& cam, const gmupt_lens& lens, uint32_t x, uint32_t y, uint32_t samples, uint32_t k, gmupt_ray* out);
 
 // ---- device side (pt_lens_aov.hip).  rays / hits: the chunk scratch of gmupt_render_aovs, 32 bytes per ray; out: the chunk's first record.

@@ -1,10 +1,8 @@
-// The camera projections on the host (include/gmupt_projection.h): the argument checks, the rule as a gmupt_ray -- the reference of the
-// device path (pt_projection.hip), the arithmetic is pt_projection.hpp, shared with the kernels -- and the inverse in binary64.
+// The camera projections on the host (include/gmupt_projection.h): the argument checks and the inverse in binary64.  The rule itself, the
+// reference of the device path (pt_projection.hip), is pt_projection.hpp, shared with the kernels and stored by store_ray.
 #include "pt_projection.hpp"
 
 #include <cmath>
-#include <cstring>
-#include <limits>
 
 namespace gmupt {
 
@@ -16,14 +14,6 @@ const char* projection_fault(const gmupt_projection& proj)
     case GMUPT_PROJ_FISHEYE: return (std::isfinite(proj.fov) && proj.fov > 0.0f && proj.fov <= 6.28318548f) ? nullptr : "fov must be in (0, 2 pi]";
     default: return "unknown kind";
     }
-}
-
-void projection_store(const ProjRay& r, gmupt_ray* out)
-{
-    std::memset(out, 0, sizeof(*out));
-    out->origin[0] = r.origin.x; out->origin[1] = r.origin.y; out->origin[2] = r.origin.z;
-    out->direction[0] = r.direction.x; out->direction[1] = r.direction.y; out->direction[2] = r.direction.z;
-    out->tmax = std::numeric_limits<float>::max();   // FLT_MAX, as gmupt_camera_pick_ray
 }
 
 bool projection_project(const gmupt_camera_buffer& cam, const gmupt_projection& proj, const float world[3], double* px, double* py)

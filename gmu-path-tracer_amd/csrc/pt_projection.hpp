@@ -3,21 +3,19 @@
 // in the written order, nothing contracted (build.py), sin / cos / sqrt from detmath.hpp.  pt_kernels.hip does not include this file:
 // the jitter of a fresh path is stage_new_path's lines, restated, as pt_lens.hpp restates them.
 #pragma once
-#include "pt_shading.hpp"      // aov_ray_coords
+#include "pt_camera_rays.hpp"  // CamRay, store_ray; and through it pt_shading.hpp: aov_ray_coords
 #include "../../include/gmupt_projection.h"
 
 namespace gmupt {
 
-struct ProjRay { f3 origin, direction; };
-
 // the ray through the screen coordinates (u, v) that the pinhole feeds into (ulc + hor*u) - ver*v
-GM_HD ProjRay projection_ray(const gmupt_camera_buffer& cam, const gmupt_projection& proj, float u, float v)
+GM_HD CamRay projection_ray(const gmupt_camera_buffer& cam, const gmupt_projection& proj, float u, float v)
 {
     const f3 pos = mk3(cam.position[0], cam.position[1], cam.position[2]);
     const f3 ulc = mk3(cam.upperLeftCorner[0], cam.upperLeftCorner[1], cam.upperLeftCorner[2]);
     const f3 hor = mk3(cam.horizontal[0], cam.horizontal[1], cam.horizontal[2]);
     const f3 ver = mk3(cam.vertical[0], cam.vertical[1], cam.vertical[2]);
-    ProjRay r;
+    CamRay r;
     r.origin = pos;
     if (proj.kind == GMUPT_PROJ_PINHOLE) {      // newPath.hlsl:39
         r.direction = normalize3((ulc + hor * u) - ver * v);
@@ -67,7 +65,7 @@ GM_HD ProjRay projection_ray(const gmupt_camera_buffer& cam, const gmupt_project
 }
 
 // the ray of the fresh camera path at entry q of the new-path queue whose screen coordinate is the whole-frame pixel (cx, cy)
-GM_HD ProjRay projection_fresh_ray(const gmupt_camera_buffer& cam, const gmupt_projection& proj, uint32_t q, uint32_t cx, uint32_t cy)
+GM_HD CamRay projection_fresh_ray(const gmupt_camera_buffer& cam, const gmupt_projection& proj, uint32_t q, uint32_t cx, uint32_t cy)
 {
     Rng g; g.seed(q, cam.randomSeed[0], cam.randomSeed[1]);     // newPath.hlsl:27,36-37
     const float jx = g.next() * 2.0f - 1.0f;
@@ -78,13 +76,13 @@ GM_HD ProjRay projection_fresh_ray(const gmupt_camera_buffer& cam, const gmupt_p
 }
 
 // the un-jittered ray through whole-frame pixel coordinates (px, py)
-GM_HD ProjRay projection_pixel_ray(const gmupt_camera_buffer& cam, const gmupt_projection& proj, float px, float py)
+GM_HD CamRay projection_pixel_ray(const gmupt_camera_buffer& cam, const gmupt_projection& proj, float px, float py)
 {
     return projection_ray(cam, proj, px * cam.pixelSize[0], py * cam.pixelSize[1]);
 }
 
 // ray k (0 .. s*s - 1) of whole-frame pixel (x, y) at s samples per axis: the pixel-filter cell of AOV ray k + 1, the centre at s == 1
-GM_HD ProjRay projection_aov_ray(const gmupt_camera_buffer& cam, const gmupt_projection& proj, uint32_t x, uint32_t y, uint32_t s, uint32_t k)
+GM_HD CamRay projection_aov_ray(const gmupt_camera_buffer& cam, const gmupt_projection& proj, uint32_t x, uint32_t y, uint32_t s, uint32_t k)
 {
     float px, py;
     aov_ray_coords(x, y, s, s > 1 ? k + 1 : 0u, px, py);
@@ -94,7 +92,6 @@ GM_HD ProjRay projection_aov_ray(const gmupt_camera_buffer& cam, const gmupt_pro
 // ---- host side (pt_projection.cpp)
 // the argument errors of include/gmupt_projection.h as a message, nullptr for a projection that is admitted
 const char* projection_fault(const gmupt_projection& proj);
-void projection_store(const ProjRay& r, gmupt_ray* out);     // as a gmupt_ray: tmax = FLT_MAX, pad = 0
 // gmupt_projection_project_host with checked arguments: false = not on the image, (px, py) untouched
 bool projection_project(const gmupt_camera_buffer& cam, const gmupt_projection& proj, const float world[3], double* px, double* py);
 

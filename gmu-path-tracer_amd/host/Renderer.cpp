@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <filesystem>
 #include <stdexcept>
+#include <type_traits>
 
 namespace fs = std::filesystem;
 
@@ -77,6 +78,28 @@ void Renderer::draw()
 	mIterations++;
 }
 
+void Renderer::ensureCamera()
+{
+	bindScene();
+	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+}
+
+// The host form of a query: device memory for `count` elements, `call` on it, the copy back.  `name`: the public method, for the message
+// of what fails here
+template <class T, class Call> std::vector<T> Renderer::readBack(size_t count, const char* name, Call&& call)
+{
+	std::vector<T> out(count);
+	const size_t bytes = out.size() * sizeof(T);
+	void* d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error(std::string(name) + ": cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+	try { call(static_cast<T*>(d), bytes); }
+	catch (...) { (void)hipFree(d); throw; }
+	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(d);
+	if (!copied) throw std::runtime_error(std::string(name) + (std::is_same<T, gmupt_aov>::value ? ": cannot read the records back" : ": cannot read the image back"));
+	return out;
+}
+
 gmupt_trace_info Renderer::traceRays(const gmupt_ray* closest, uint32_t nClosest, gmupt_hit* hits, const gmupt_ray* any, uint32_t nAny, uint32_t* occluded,
                                      uint32_t lightCount)
 {
@@ -88,8 +111,7 @@ gmupt_trace_info Renderer::traceRays(const gmupt_ray* closest, uint32_t nClosest
 
 Renderer::Pick Renderer::pick(float x, float y)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	Pick p{};
 	check(gmupt_pick(mRenderer.get(), x, y, mScene.mCamera.getBuffer()->lightCount, &p.ray, &p.hit));
 	return p;
@@ -104,8 +126,7 @@ void Renderer::setLens(float apertureRadius, float focusDistance)
 
 gmupt_lens Renderer::focusAt(float x, float y, float apertureRadius)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	gmupt_lens lens{ apertureRadius, 1.f };
 	check(gmupt_lens_focus_at(mRenderer.get(), x, y, mScene.mCamera.getBuffer()->lightCount, &lens));
 	setLens(lens.aperture_radius, lens.focus_distance);
@@ -120,8 +141,7 @@ void Renderer::setProjection(const gmupt_projection& projection)
 
 Renderer::Pick Renderer::pickProjected(float x, float y)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	Pick p{};
 	check(gmupt_pick_projected(mRenderer.get(), x, y, mScene.mCamera.getBuffer()->lightCount, &p.ray, &p.hit));
 	return p;
@@ -129,8 +149,7 @@ Renderer::Pick Renderer::pickProjected(float x, float y)
 
 gmupt_trace_info Renderer::renderAovsProjected(gmupt_aov* deviceOut, size_t bytes, unsigned samples)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	gmupt_trace_info info{};
 	check(gmupt_render_aovs_projected(mRenderer.get(), nullptr, samples, deviceOut, bytes, &info));
 	return info;
@@ -138,23 +157,12 @@ gmupt_trace_info Renderer::renderAovsProjected(gmupt_aov* deviceOut, size_t byte
 
 std::vector<gmupt_aov> Renderer::renderAovsProjected(unsigned samples)
 {
-	const Resolution t = targetSize();
-	std::vector<gmupt_aov> out(static_cast<size_t>(t.first) * t.second);
-	const size_t bytes = out.size() * sizeof(gmupt_aov);
-	void* d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("renderAovsProjected: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-	try { renderAovsProjected(static_cast<gmupt_aov*>(d), bytes, samples); }
-	catch (...) { (void)hipFree(d); throw; }
-	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	if (!copied) throw std::runtime_error("renderAovsProjected: cannot read the records back");
-	return out;
+	return readBack<gmupt_aov>(targetPixels(), "renderAovsProjected", [&](gmupt_aov* d, size_t bytes) { renderAovsProjected(d, bytes, samples); });
 }
 
 gmupt_trace_info Renderer::denoiseProjected(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_denoise_params* params)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	gmupt_trace_info info{};
 	check(gmupt_render_denoised_projected(mRenderer.get(), nullptr, aovSamples, params, deviceOut, bytes, &info));
 	return info;
@@ -162,23 +170,12 @@ gmupt_trace_info Renderer::denoiseProjected(float* deviceOut, size_t bytes, unsi
 
 std::vector<float> Renderer::denoiseProjected(unsigned aovSamples, const gmupt_denoise_params* params)
 {
-	const Resolution t = targetSize();
-	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
-	const size_t bytes = out.size() * sizeof(float);
-	void* d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoiseProjected: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-	try { denoiseProjected(static_cast<float*>(d), bytes, aovSamples, params); }
-	catch (...) { (void)hipFree(d); throw; }
-	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	if (!copied) throw std::runtime_error("denoiseProjected: cannot read the image back");
-	return out;
+	return readBack<float>(4 * targetPixels(), "denoiseProjected", [&](float* d, size_t bytes) { denoiseProjected(d, bytes, aovSamples, params); });
 }
 
 gmupt_trace_info Renderer::renderAovs(gmupt_aov* deviceOut, size_t bytes, unsigned samples)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	gmupt_trace_info info{};
 	check(gmupt_render_aovs(mRenderer.get(), samples, deviceOut, bytes, &info));
 	return info;
@@ -186,23 +183,12 @@ gmupt_trace_info Renderer::renderAovs(gmupt_aov* deviceOut, size_t bytes, unsign
 
 std::vector<gmupt_aov> Renderer::renderAovs(unsigned samples)
 {
-	const Resolution t = targetSize();
-	std::vector<gmupt_aov> out(static_cast<size_t>(t.first) * t.second);
-	const size_t bytes = out.size() * sizeof(gmupt_aov);
-	void* d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("renderAovs: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-	try { renderAovs(static_cast<gmupt_aov*>(d), bytes, samples); }
-	catch (...) { (void)hipFree(d); throw; }
-	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	if (!copied) throw std::runtime_error("renderAovs: cannot read the records back");
-	return out;
+	return readBack<gmupt_aov>(targetPixels(), "renderAovs", [&](gmupt_aov* d, size_t bytes) { renderAovs(d, bytes, samples); });
 }
 
 gmupt_trace_info Renderer::renderAovsLens(gmupt_aov* deviceOut, size_t bytes, unsigned samples)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	gmupt_trace_info info{};
 	check(gmupt_render_aovs_lens(mRenderer.get(), nullptr, samples, deviceOut, bytes, &info));
 	return info;
@@ -210,23 +196,12 @@ gmupt_trace_info Renderer::renderAovsLens(gmupt_aov* deviceOut, size_t bytes, un
 
 std::vector<gmupt_aov> Renderer::renderAovsLens(unsigned samples)
 {
-	const Resolution t = targetSize();
-	std::vector<gmupt_aov> out(static_cast<size_t>(t.first) * t.second);
-	const size_t bytes = out.size() * sizeof(gmupt_aov);
-	void* d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("renderAovsLens: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-	try { renderAovsLens(static_cast<gmupt_aov*>(d), bytes, samples); }
-	catch (...) { (void)hipFree(d); throw; }
-	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	if (!copied) throw std::runtime_error("renderAovsLens: cannot read the records back");
-	return out;
+	return readBack<gmupt_aov>(targetPixels(), "renderAovsLens", [&](gmupt_aov* d, size_t bytes) { renderAovsLens(d, bytes, samples); });
 }
 
 gmupt_trace_info Renderer::denoiseLens(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_denoise_params* params)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	gmupt_trace_info info{};
 	check(gmupt_render_denoised_lens(mRenderer.get(), nullptr, aovSamples, params, deviceOut, bytes, &info));
 	return info;
@@ -234,23 +209,12 @@ gmupt_trace_info Renderer::denoiseLens(float* deviceOut, size_t bytes, unsigned 
 
 std::vector<float> Renderer::denoiseLens(unsigned aovSamples, const gmupt_denoise_params* params)
 {
-	const Resolution t = targetSize();
-	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
-	const size_t bytes = out.size() * sizeof(float);
-	void* d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoiseLens: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-	try { denoiseLens(static_cast<float*>(d), bytes, aovSamples, params); }
-	catch (...) { (void)hipFree(d); throw; }
-	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	if (!copied) throw std::runtime_error("denoiseLens: cannot read the image back");
-	return out;
+	return readBack<float>(4 * targetPixels(), "denoiseLens", [&](float* d, size_t bytes) { denoiseLens(d, bytes, aovSamples, params); });
 }
 
 gmupt_trace_info Renderer::denoise(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_denoise_params* params)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	gmupt_trace_info info{};
 	check(gmupt_render_denoised(mRenderer.get(), aovSamples, params, deviceOut, bytes, &info));
 	return info;
@@ -258,23 +222,12 @@ gmupt_trace_info Renderer::denoise(float* deviceOut, size_t bytes, unsigned aovS
 
 std::vector<float> Renderer::denoise(unsigned aovSamples, const gmupt_denoise_params* params)
 {
-	const Resolution t = targetSize();
-	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
-	const size_t bytes = out.size() * sizeof(float);
-	void* d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoise: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-	try { denoise(static_cast<float*>(d), bytes, aovSamples, params); }
-	catch (...) { (void)hipFree(d); throw; }
-	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	if (!copied) throw std::runtime_error("denoise: cannot read the image back");
-	return out;
+	return readBack<float>(4 * targetPixels(), "denoise", [&](float* d, size_t bytes) { denoise(d, bytes, aovSamples, params); });
 }
 
 gmupt_trace_info Renderer::denoiseTemporal(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_temporal_params* params)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	if (!mTemporal) { gmupt_temporal* t = nullptr; check(gmupt_temporal_create(mRenderer.get(), &t)); mTemporal.reset(t); }
 	gmupt_trace_info info{};
 	check(gmupt_render_denoised_temporal(mRenderer.get(), mTemporal.get(), aovSamples, params, deviceOut, bytes, &info));
@@ -283,8 +236,7 @@ gmupt_trace_info Renderer::denoiseTemporal(float* deviceOut, size_t bytes, unsig
 
 gmupt_trace_info Renderer::denoiseTemporalMotion(float* deviceOut, size_t bytes, unsigned aovSamples, const gmupt_temporal_params* params)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }
+	ensureCamera();
 	if (!mTemporal) { gmupt_temporal* t = nullptr; check(gmupt_temporal_create(mRenderer.get(), &t)); mTemporal.reset(t); }
 	gmupt_trace_info info{};
 	check(gmupt_render_denoised_temporal_motion(mRenderer.get(), mTemporal.get(), aovSamples, params, deviceOut, bytes, &info));
@@ -293,39 +245,18 @@ gmupt_trace_info Renderer::denoiseTemporalMotion(float* deviceOut, size_t bytes,
 
 std::vector<float> Renderer::denoiseTemporalMotion(unsigned aovSamples, const gmupt_temporal_params* params)
 {
-	const Resolution t = targetSize();
-	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
-	const size_t bytes = out.size() * sizeof(float);
-	void* d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoiseTemporalMotion: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-	try { denoiseTemporalMotion(static_cast<float*>(d), bytes, aovSamples, params); }
-	catch (...) { (void)hipFree(d); throw; }
-	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	if (!copied) throw std::runtime_error("denoiseTemporalMotion: cannot read the image back");
-	return out;
+	return readBack<float>(4 * targetPixels(), "denoiseTemporalMotion", [&](float* d, size_t bytes) { denoiseTemporalMotion(d, bytes, aovSamples, params); });
 }
 
 std::vector<float> Renderer::denoiseTemporal(unsigned aovSamples, const gmupt_temporal_params* params)
 {
-	const Resolution t = targetSize();
-	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
-	const size_t bytes = out.size() * sizeof(float);
-	void* d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("denoiseTemporal: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-	try { denoiseTemporal(static_cast<float*>(d), bytes, aovSamples, params); }
-	catch (...) { (void)hipFree(d); throw; }
-	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	if (!copied) throw std::runtime_error("denoiseTemporal: cannot read the image back");
-	return out;
+	return readBack<float>(4 * targetPixels(), "denoiseTemporal", [&](float* d, size_t bytes) { denoiseTemporal(d, bytes, aovSamples, params); });
 }
 
 gmupt_trace_info Renderer::preview(float* deviceOut, size_t bytes, bool temporal, bool motion, unsigned aovSamples, const gmupt_temporal_params* params,
                                    const gmupt_infill_params* infill)
 {
-	bindScene();
-	if (!mCameraSet) { check(gmupt_set_camera(mRenderer.get(), mScene.mCamera.getBuffer())); mCameraSet = true; }   // before the first frame: the camera as it stands
+	ensureCamera();
 	if (temporal && !mTemporal) { gmupt_temporal* t = nullptr; check(gmupt_temporal_create(mRenderer.get(), &t)); mTemporal.reset(t); }
 	gmupt_trace_info info{};
 	check(gmupt_render_preview(mRenderer.get(), temporal ? mTemporal.get() : nullptr, temporal && motion ? GMUPT_PREVIEW_MOTION : 0u, aovSamples, params, infill,
@@ -335,17 +266,7 @@ gmupt_trace_info Renderer::preview(float* deviceOut, size_t bytes, bool temporal
 
 std::vector<float> Renderer::preview(bool temporal, bool motion, unsigned aovSamples, const gmupt_temporal_params* params, const gmupt_infill_params* infill)
 {
-	const Resolution t = targetSize();
-	std::vector<float> out(static_cast<size_t>(t.first) * t.second * 4);
-	const size_t bytes = out.size() * sizeof(float);
-	void* d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) throw std::runtime_error("preview: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-	try { preview(static_cast<float*>(d), bytes, temporal, motion, aovSamples, params, infill); }
-	catch (...) { (void)hipFree(d); throw; }
-	const bool copied = hipMemcpy(out.data(), d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-	(void)hipFree(d);
-	if (!copied) throw std::runtime_error("preview: cannot read the image back");
-	return out;
+	return readBack<float>(4 * targetPixels(), "preview", [&](float* d, size_t bytes) { preview(d, bytes, temporal, motion, aovSamples, params, infill); });
 }
 
 gmupt_refit_info Renderer::refitScene(bool keepHistory, bool smoothNormals)

@@ -148,6 +148,9 @@ private:
 	void captureScreen();
 	void resize(const Resolution& resolution);
 	void bindScene();
+	void ensureCamera();   // bindScene(), and before the first frame the camera as it stands: what every query on the current camera starts with
+	size_t targetPixels() const { return static_cast<size_t>(targetSize().first) * targetSize().second; }
+	template <class T, class Call> std::vector<T> readBack(size_t count, const char* name, Call&& call);   // the host forms: call(deviceOut, bytes), read back
 
 	struct DeviceDeleter { void operator()(gmupt_device* d) const { gmupt_device_destroy(d); } };
 	struct RendererDeleter { void operator()(gmupt_renderer* r) const { gmupt_renderer_destroy(r); } };

@@ -301,6 +301,30 @@ def test_tile_renderer_returns_its_sub_rectangle(pkg, device, wide, textured):
     close(rt, r, sb, cam)
 
 
+def test_a_frame_of_two_chunks_equals_single_chunk_tiles(pkg, device, wide, textured):
+    """test_lens_aov_gpu's chunk seam under a projection: the three paths run one chunk loop.  On the CPU oracle this frame (the textured
+    scene from its own camera under the 180-degree fisheye) has 5988 pixels with coverage > 0 of the 13495 that have a ray inside the
+    image circle."""
+    s = pkg.capi.AOV_MAX_SAMPLES
+    Wc = 256
+    rows = pkg.capi.AOV_CHUNK_RAYS // (Wc * s * s)           # 128 rows of 256 * 64 rays fill a chunk
+    Hc = rows + 1                                            # one more: a second chunk of one row
+    assert rows * Wc * s * s == pkg.capi.AOV_CHUNK_RAYS and Wc * Hc * s * s > pkg.capi.AOV_CHUNK_RAYS
+    proj = kinds(pkg)["fisheye"]
+    cam = aov_camera(pkg, textured, Wc, Hc)
+    sb = pkg.capi.SceneBuffers(device, textured)
+    r = pkg.capi.Renderer(device, Wc, Hc, pool_paths=POOL)
+    r.bind_scene(sb); r.set_camera(cam.buffer)
+    whole = pkg.capi.projection.aovs(r, s, proj).cpu().numpy().view(np.uint32)
+    assert (pkg.capi.aov_fields(whole.view(np.float32))["coverage"] > 0).sum() > 1000
+    for y0, th in [(0, 64), (64, 64), (rows, 1)]:            # the last tile is the second chunk's row
+        rt = pkg.capi.Renderer(device, Wc, th, pool_paths=POOL, tile=(0, y0))
+        rt.bind_scene(sb); rt.set_camera(cam.buffer)
+        assert np.array_equal(pkg.capi.projection.aovs(rt, s, proj).cpu().numpy().view(np.uint32), whole[y0:y0 + th]), y0
+        rt.close()
+    close(r, sb, cam)
+
+
 def custom_scene(pkg, verts, normals, indices):
     mesh = dict(pkg.scenes.cornell_mesh())
     mesh.update(verts=np.asarray(verts, np.float32), normals=np.asarray(normals, np.float32), indices=np.asarray(indices, np.int32),
