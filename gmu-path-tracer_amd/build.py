@@ -10,9 +10,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libgmupt.so")
 
-DEVICE_SOURCES = ["csrc/pt_kernels.hip", "csrc/pt_traverse.hip", "csrc/pt_traverse_wide.hip", "csrc/pt_traverse_variants.hip", "csrc/pt_aov.hip", "csrc/pt_denoise.hip", "csrc/pt_infill.hip", "csrc/pt_temporal.hip", "csrc/pt_refit.hip", "csrc/pt_motion.hip", "csrc/pt_lbvh.hip", "csrc/pt_normals.hip", "csrc/pt_treecost.hip", "csrc/pt_treeopt.hip", "csrc/pt_pose.hip", "csrc/pt_converge.hip", "csrc/pt_adaptive.hip", "csrc/pt_lens.hip", "csrc/pt_lens_aov.hip", "csrc/pt_projection.hip", "csrc/gmupt_capi.hip", "csrc/gmupt_capi_accel.hip", "csrc/gmupt_capi_query.hip", "csrc/gmupt_capi_denoise.hip", "csrc/gmupt_capi_infill.hip", "csrc/gmupt_capi_normals.hip", "csrc/gmupt_capi_treecost.hip", "csrc/gmupt_capi_treeopt.hip", "csrc/gmupt_capi_pose.hip", "csrc/gmupt_capi_converge.hip", "csrc/gmupt_capi_adaptive.hip", "csrc/gmupt_capi_lens.hip", "csrc/gmupt_capi_lens_aov.hip", "csrc/gmupt_capi_projection.hip"]   # pt_traverse_variants.hip is empty without -DGMUPT_VARIANTS
-HOST_SOURCES = ["csrc/gmupt_capi_host.cpp", "csrc/pt_travtables.cpp", "csrc/pt_lbvh.cpp", "csrc/pt_normals.cpp", "csrc/pt_treecost.cpp", "csrc/pt_treeopt.cpp", "csrc/pt_pose.cpp", "csrc/pt_infill.cpp", "csrc/pt_converge.cpp", "csrc/pt_adaptive.cpp", "csrc/pt_lens.cpp", "csrc/pt_lens_aov.cpp", "csrc/pt_projection.cpp", "csrc/pt_denoise.cpp", "csrc/pt_temporal.cpp", "csrc/pt_motion.cpp", "csrc/pt_refit.cpp", "host/sbvh_builder.cpp", "host/Camera.cpp", "host/TextureLoader.cpp", "host/AvirResize.cpp"]
-HEADERS = ["csrc/gmupt_internal.hpp", "csrc/gmupt_work.hpp", "csrc/pt_launch.hpp", "csrc/pt_scratch.hpp", "csrc/pt_levels.hpp", "csrc/pt_ordered_sum.hpp", "csrc/pt_traverse_common.hpp", "csrc/pt_shading.hpp", "csrc/pt_guides.hpp", "csrc/pt_bands.hpp", "csrc/pt_denoise.hpp", "csrc/pt_infill.hpp", "csrc/pt_temporal.hpp", "csrc/pt_refit.hpp", "csrc/pt_travtables.hpp", "csrc/pt_motion.hpp", "csrc/pt_lbvh.hpp", "csrc/pt_normals.hpp", "csrc/pt_treecost.hpp", "csrc/pt_treeopt.hpp", "csrc/pt_pose.hpp", "csrc/pt_converge.hpp", "csrc/pt_adaptive.hpp", "csrc/pt_camera_rays.hpp", "csrc/pt_lens.hpp", "csrc/pt_lens_aov.hpp", "csrc/pt_projection.hpp", "csrc/pt_traverse_deferred.hpp", "csrc/pt_cast_plumbing.hpp", "csrc/pt_kernel_util.hpp", "host/MeshData.hpp", "host/BVHWrapper.hpp", "csrc/pt_device.hpp", "csrc/detmath.hpp", "host/sbvh_builder.hpp", "host/Camera.hpp", "host/TextureLoader.hpp", "host/png_reader.hpp", "host/Constants.hpp", "../include/gmupt.h", "../include/gmupt_adaptive.h", "../include/gmupt_lens.h", "../include/gmupt_lens_aov.h", "../include/gmupt_projection.h"]
+DEVICE_SOURCES = ["csrc/pt_kernels.hip", "csrc/pt_traverse.hip", "csrc/pt_traverse_wide.hip", "csrc/pt_traverse_variants.hip", "csrc/pt_aov.hip", "csrc/pt_denoise.hip", "csrc/pt_infill.hip", "csrc/pt_temporal.hip", "csrc/pt_refit.hip", "csrc/pt_motion.hip", "csrc/pt_lbvh.hip", "csrc/pt_normals.hip", "csrc/pt_treecost.hip", "csrc/pt_treeopt.hip", "csrc/pt_pose.hip", "csrc/pt_converge.hip", "csrc/pt_adaptive.hip", "csrc/pt_lens.hip", "csrc/pt_lens_aov.hip", "csrc/pt_projection.hip", "csrc/pt_shutter.hip", "csrc/gmupt_capi.hip", "csrc/gmupt_capi_accel.hip", "csrc/gmupt_capi_query.hip", "csrc/gmupt_capi_denoise.hip", "csrc/gmupt_capi_infill.hip", "csrc/gmupt_capi_normals.hip", "csrc/gmupt_capi_treecost.hip", "csrc/gmupt_capi_treeopt.hip", "csrc/gmupt_capi_pose.hip", "csrc/gmupt_capi_converge.hip", "csrc/gmupt_capi_adaptive.hip", "csrc/gmupt_capi_lens.hip", "csrc/gmupt_capi_lens_aov.hip", "csrc/gmupt_capi_projection.hip", "csrc/gmupt_capi_shutter.hip"]   # pt_traverse_variants.hip is empty without -DGMUPT_VARIANTS
+HOST_SOURCES = ["csrc/gmupt_capi_host.cpp", "csrc/pt_travtables.cpp", "csrc/pt_lbvh.cpp", "csrc/pt_normals.cpp", "csrc/pt_treecost.cpp", "csrc/pt_treeopt.cpp", "csrc/pt_pose.cpp", "csrc/pt_infill.cpp", "csrc/pt_converge.cpp", "csrc/pt_adaptive.cpp", "csrc/pt_lens.cpp", "csrc/pt_lens_aov.cpp", "csrc/pt_projection.cpp", "csrc/pt_shutter.cpp", "csrc/pt_denoise.cpp", "csrc/pt_temporal.cpp", "csrc/pt_motion.cpp", "csrc/pt_refit.cpp", "host/sbvh_builder.cpp", "host/Camera.cpp", "host/TextureLoader.cpp", "host/AvirResize.cpp"]
+HEADERS = ["csrc/gmupt_internal.hpp", "csrc/gmupt_work.hpp", "csrc/pt_launch.hpp", "csrc/pt_scratch.hpp", "csrc/pt_levels.hpp", "csrc/pt_ordered_sum.hpp", "csrc/pt_traverse_common.hpp", "csrc/pt_shading.hpp", "csrc/pt_guides.hpp", "csrc/pt_bands.hpp", "csrc/pt_denoise.hpp", "csrc/pt_infill.hpp", "csrc/pt_temporal.hpp", "csrc/pt_refit.hpp", "csrc/pt_travtables.hpp", "csrc/pt_motion.hpp", "csrc/pt_lbvh.hpp", "csrc/pt_normals.hpp", "csrc/pt_treecost.hpp", "csrc/pt_treeopt.hpp", "csrc/pt_pose.hpp", "csrc/pt_converge.hpp", "csrc/pt_adaptive.hpp", "csrc/pt_camera_rays.hpp", "csrc/pt_lens.hpp", "csrc/pt_lens_aov.hpp", "csrc/pt_projection.hpp", "csrc/pt_shutter.hpp", "csrc/pt_traverse_deferred.hpp", "csrc/pt_cast_plumbing.hpp", "csrc/pt_kernel_util.hpp", "host/MeshData.hpp", "host/BVHWrapper.hpp", "csrc/pt_device.hpp", "csrc/detmath.hpp", "host/sbvh_builder.hpp", "host/Camera.hpp", "host/TextureLoader.hpp", "host/png_reader.hpp", "host/Constants.hpp", "../include/gmupt.h", "../include/gmupt_adaptive.h", "../include/gmupt_lens.h", "../include/gmupt_lens_aov.h", "../include/gmupt_projection.h", "../include/gmupt_shutter.h"]
 
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",

@@ -9,8 +9,8 @@ converge, mesh and accel, then core (Camera, Renderer), which imports the featur
 
 adaptive (adaptive sampling) is the exception: it is reached as capi.adaptive.NAME and keeps its structures and prototypes itself, so
 that the names at this level, the Renderer class and SYMBOLS stay the recorded surface (tests/golden/capi_surface.json).  lens (the
-thin lens, capi.lens.NAME) follows it, and so do lens_aov (the lens-filtered AOV planes, capi.lens_aov.NAME) and projection (the camera
-projections, capi.projection.NAME).
+thin lens, capi.lens.NAME) follows it, and so do lens_aov (the lens-filtered AOV planes, capi.lens_aov.NAME), projection (the camera
+projections, capi.projection.NAME) and shutter (camera motion blur, capi.shutter.NAME).
 """
 from ._abi import *  # noqa: F401,F403
 from ._lib import _check, _ptr, lib, use_build  # noqa: F401
@@ -28,3 +28,4 @@ from . import adaptive  # noqa: F401,E402
 from . import lens  # noqa: F401,E402
 from . import lens_aov  # noqa: F401,E402
 from . import projection  # noqa: F401,E402
+from . import shutter  # noqa: F401,E402

@@ -356,8 +356,9 @@ static int run_iteration(gmupt_renderer* r, bool doShade, bool doExtend, bool do
         if (ev && !extOnly) HIP_TRY(hipEventRecord(ev->e[1], r->stream));
         launch_material(p, clearFrame, r->stream);  // computes its own queue offsets (no scan launch)
         if (plan && plan->count) launch_adaptive_retarget(p, plan->sc.list, plan->count, plan->uniformEvery, r->stream);   // re-aims the fresh camera paths
-        if (r->lens.aperture_radius > 0.0f) launch_lens_retarget(p, r->lens.aperture_radius, r->lens.focus_distance, r->stream);   // thin lens: after the re-aim, it reads the pixel from the state
-        if (r->projection.kind != GMUPT_PROJ_PINHOLE) launch_proj_retarget(p, r->projection, r->stream);   // camera projection: where the lens would be (the two do not combine)
+        if (r->shutterAttached) launch_shutter_retarget(p, r->shutter, r->lens, r->projection, r->stream);   // shutter: in place of the two below, whose rule it runs on the camera at the path's time
+        else if (r->lens.aperture_radius > 0.0f) launch_lens_retarget(p, r->lens.aperture_radius, r->lens.focus_distance, r->stream);   // thin lens: after the re-aim, it reads the pixel from the state
+        else if (r->projection.kind != GMUPT_PROJ_PINHOLE) launch_proj_retarget(p, r->projection, r->stream);   // camera projection: where the lens would be (the two do not combine)
         if (ev) HIP_TRY(hipEventRecord(ev->e[2], r->stream));
     }
     if (!doShade) HIP_TRY(hipMemsetAsync(p.travCounters, 0, 128, r->stream)); // k_material (block 0) zeroes the ray-cast work counters in a full iteration
@@ -434,6 +435,7 @@ extern "C" int gmupt_resize(gmupt_renderer* r, uint32_t width, uint32_t height)
     r->desc.width = width; r->desc.height = height;
     r->accumGeneration++;
     r->adaptive = nullptr;                            // a sampling plan is a plan for the old rectangle
+    r->shutterAttached = false;                       // a close pose is one of the old aspect: its `horizontal` no longer matches the camera's
     return GMUPT_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "pt_lens.hpp"
 #include "pt_lens_aov.hpp"
 #include "pt_projection.hpp"
+#include "pt_shutter.hpp"
 #include "pt_launch.hpp"
 #include "../host/sbvh_builder.hpp"
 #include "../host/Camera.hpp"
@@ -156,6 +157,9 @@ struct gmupt_renderer {
     gmupt_lens lens{ 0.0f, 1.0f };
     // camera projection (gmupt_renderer_set_projection): kind GMUPT_PROJ_PINHOLE = none attached, every iteration launches what it always did
     gmupt_projection projection{ GMUPT_PROJ_PINHOLE, 3.14159274f, 1.0f, 0u };
+    // shutter (gmupt_renderer_set_shutter): the camera pose at shutter close; not attached = every iteration launches what it always did
+    gmupt_shutter shutter{};
+    bool shutterAttached = false;
 
     __attribute__((visibility("default"))) ~gmupt_renderer() { if (stream) (void)hipStreamDestroy(stream); }   // gmupt_renderer_destroy has synchronised it; the library has always exported this symbol
     uint32_t tile_x0() const { return p.tileEnabled ? p.tileX0 : 0u; } uint32_t tile_y0() const { return p.tileEnabled ? p.tileY0 : 0u; }   // the origin of the rendered rectangle

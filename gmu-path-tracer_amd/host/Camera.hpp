@@ -18,6 +18,7 @@ public:
 	void setRotation(float pitch, float yaw);
 	void setPosition(float x, float y, float z);
 	CameraBuffer* getBuffer();
+	const CameraBuffer* getBuffer() const { return &mCBuffer; }
 
 	// input hooks (the reference reads a Win32 Input singleton, Source/Camera.cpp:28,50-57,72)
 	void addMouseDelta(float dx, float dy) { mDeltaX += dx; mDeltaY += dy; }

@@ -139,6 +139,20 @@ void Renderer::setProjection(const gmupt_projection& projection)
 	mScene.mCamera.getBuffer()->iterationCounter = -1; // the samples so far were made with the old projection
 }
 
+void Renderer::setShutter(const Camera& close)
+{
+	gmupt_shutter shutter;
+	check(gmupt_shutter_from_camera(close.getBuffer(), &shutter));
+	check(gmupt_renderer_set_shutter(mRenderer.get(), &shutter));
+	mScene.mCamera.getBuffer()->iterationCounter = -1; // the samples so far were made with the old shutter
+}
+
+void Renderer::clearShutter()
+{
+	check(gmupt_renderer_set_shutter(mRenderer.get(), nullptr));
+	mScene.mCamera.getBuffer()->iterationCounter = -1;
+}
+
 Renderer::Pick Renderer::pickProjected(float x, float y)
 {
 	ensureCamera();

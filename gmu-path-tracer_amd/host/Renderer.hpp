@@ -11,6 +11,7 @@
 #include "../../include/gmupt_lens.h"
 #include "../../include/gmupt_lens_aov.h"
 #include "../../include/gmupt_projection.h"
+#include "../../include/gmupt_shutter.h"
 
 class Renderer
 {
@@ -61,6 +62,11 @@ public:
 	// renderAovsProjected / denoiseProjected are renderAovsLens / denoiseLens under it (gmupt_render_aovs_projected, gmupt_render_denoised_projected):
 	// samples * samples stratified rays per pixel, no centre ray.  The temporal previews stay a pinhole's and must not be used with a projection.
 	void setProjection(const gmupt_projection& projection);
+	// camera motion blur (include/gmupt_shutter.h): the renderer's camera is the pose at shutter open, `close` (after its update()) the pose
+	// at shutter close; every fresh camera path leaves a camera interpolated between the two, under the attached lens or projection.  Both
+	// restart the accumulation like a camera move; pick, the AOV planes and the temporal projection stay at shutter open.  A resize detaches.
+	void setShutter(const Camera& close);
+	void clearShutter();
 	Pick pickProjected(float x, float y);
 	gmupt_trace_info renderAovsProjected(gmupt_aov* deviceOut, size_t bytes, unsigned samples = 1);
 	std::vector<gmupt_aov> renderAovsProjected(unsigned samples = 1);

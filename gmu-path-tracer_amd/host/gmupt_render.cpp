@@ -36,6 +36,9 @@
 //                                                         renderAovsLens, include/gmupt_lens_aov.h), S*S rays per pixel through the lens; not with --infill
 //                [--projection ortho:H | fisheye:DEG | equirect]   another camera (Renderer::setProjection, include/gmupt_projection.h); --pick, --aov and
 //                                                         --denoise follow it; one JSON line with the projection; not with --aperture, --temporal, --infill, --ranks
+//                [--shutter-to X,Y,Z,PITCH,YAW]           camera motion blur (Renderer::setShutter, include/gmupt_shutter.h): the scene's camera is the pose
+//                                                         at shutter open, a camera at position (X, Y, Z) with PITCH and YAW in degrees the pose at shutter
+//                                                         close; with --aperture or --projection as well; one JSON line with the close pose; not with --ranks
 //                [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]
 //                                                         adaptive sampling in that loop (Renderer::renderAdaptive, include/gmupt_adaptive.h): the JSON
 //                                                         line gains active, entries, max_rep, skipped_nonfinite of the last plan and paths_generated
@@ -170,6 +173,7 @@ int main(int argc, char** argv)
 	bool adaptive = false, maxRepeatGiven = false, uniformEveryGiven = false; unsigned maxRepeat = 1, uniformEvery = 0;
 	bool lensGuides = false;
 	bool projectionGiven = false; gmupt_projection projection{ GMUPT_PROJ_PINHOLE, 3.14159274f, 1.f, 0u };
+	bool shutterGiven = false; float shutterTo[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };
 	bool apertureGiven = false, focusGiven = false, focusAtGiven = false; float aperture = 0.f, focus = 0.f, focusX = 0.f, focusY = 0.f;
 	bool untilError = false, checkEveryGiven = false, allowPixelsGiven = false; float untilThreshold = 0.f; unsigned checkEvery = 8, allowPixels = 0; std::string errorMap;
 	for (int i = 1; i < argc; i++) {
@@ -232,6 +236,12 @@ int main(int argc, char** argv)
 			}
 			else { std::fprintf(stderr, "--projection takes ortho:H, fisheye:DEG or equirect\n"); return 2; }
 		}
+		else if (a == "--shutter-to") {
+			const char* v = next(); char tail = 0; shutterGiven = true;
+			bool ok = std::sscanf(v, "%f,%f,%f,%f,%f%c", &shutterTo[0], &shutterTo[1], &shutterTo[2], &shutterTo[3], &shutterTo[4], &tail) == 5;
+			for (float c : shutterTo) ok = ok && c - c == 0.f;
+			if (!ok) { std::fprintf(stderr, "--shutter-to takes a finite pose X,Y,Z,PITCH,YAW\n"); return 2; }
+		}
 		else if (a == "--pick") { if (std::sscanf(next(), "%f,%f", &pickX, &pickY) != 2) return 2; doPick = true; }
 		else if (a == "--help" || a == "-h") {
 			std::printf("gmupt_render --scene cornell|file.gmesh|file.gltf|file.glb --size WxH --frames N --pool P --live L [--capture] [--dump out.f32] [--pfm out.pfm]\n"
@@ -261,6 +271,9 @@ int main(int argc, char** argv)
 			            "                                 DEG degrees across the image circle, or the 360-degree equirectangular panorama; --pick, --aov and --denoise\n"
 			            "                                 follow it (S*S stratified rays per pixel); one JSON line with the projection; not with --aperture, --temporal,\n"
 			            "                                 --infill or --ranks\n"
+			            "             [--shutter-to X,Y,Z,PITCH,YAW]   camera motion blur: the scene's camera is the pose at shutter open, a camera at (X, Y, Z) with\n"
+			            "                                 PITCH and YAW in degrees the pose at shutter close; every camera path leaves a camera between the two; usable\n"
+			            "                                 with --aperture or --projection; picks, AOVs and previews stay at shutter open; one JSON line; not with --ranks\n"
 			            "             [--until-error T --adaptive [--max-repeat N] [--uniform-every N]]   adaptive sampling: after every check that does not end the loop\n"
 			            "                                 the new camera paths go to the pixels still above T, up to N (default 1, at most 64) list entries each,\n"
 			            "                                 every N-th path (default 0 = none) to the pixel it would have gone to anyway; T must be > 0; the JSON line\n"
@@ -387,6 +400,8 @@ int main(int argc, char** argv)
 			throw std::invalid_argument("--projection sets the camera of a single process: it cannot be combined with --ranks N > 1");
 		if (apertureGiven && ranks > 1)
 			throw std::invalid_argument("--aperture sets the lens of a single process: it cannot be combined with --ranks N > 1");
+		if (shutterGiven && ranks > 1)
+			throw std::invalid_argument("--shutter-to sets the shutter of a single process: it cannot be combined with --ranks N > 1");
 		if (untilError && ranks > 1)
 			throw std::invalid_argument("--until-error judges the frame of a single process: it cannot be combined with --ranks N > 1");
 		if (treeCost && ranks > 1)
@@ -465,6 +480,15 @@ int main(int argc, char** argv)
 			renderer.setProjection(projection);
 			unsigned fb, eb; std::memcpy(&fb, &projection.fov, 4); std::memcpy(&eb, &projection.extent, 4);
 			std::printf("{\"projection\": {\"kind\": %u, \"fov\": %.9g, \"extent\": %.9g, \"fov_bits\": \"%08x\", \"extent_bits\": \"%08x\"}}\n", projection.kind, projection.fov, projection.extent, fb, eb);
+		}
+		if (shutterGiven) {   // the close pose from the same Camera code as the open one
+			Camera close(w, h);
+			close.setPosition(shutterTo[0], shutterTo[1], shutterTo[2]); close.setRotation(shutterTo[3], shutterTo[4]); close.update(0.f);
+			renderer.setShutter(close);
+			const gmupt_camera_buffer* cb = close.getBuffer();
+			std::printf("{\"shutter\": {\"position\": [%.9g, %.9g, %.9g], \"upper_left_corner\": [%.9g, %.9g, %.9g], \"horizontal\": [%.9g, %.9g, %.9g], \"vertical\": [%.9g, %.9g, %.9g]}}\n",
+			            cb->position[0], cb->position[1], cb->position[2], cb->upperLeftCorner[0], cb->upperLeftCorner[1], cb->upperLeftCorner[2],
+			            cb->horizontal[0], cb->horizontal[1], cb->horizontal[2], cb->vertical[0], cb->vertical[1], cb->vertical[2]);
 		}
 		if (untilError) {
 			gmupt_converge_params cp; gmupt_converge_default_params(&cp);

@@ -40,6 +40,8 @@ class ProgressiveSession:
         self._epoch = 0        # accumulations started (a frame that cleared the target, a resize): what denoised_temporal(lens_guides=True) folds its history by
         self._guided_epoch = None   # the epoch of its last call
         self.projection = None # the capi.projection.Projection of set_projection(); None = the pinhole
+        self._shutter_fraction = None   # set_shutter(fraction=f): the session sets the close pose of every frame
+        self._shutter_prev = None       # ... from the pose of the frame before (a capi.shutter.Shutter), None after a resize
 
     # ---- events (applied before the next frame, like the GUI callbacks of the reference)
     def move_camera(self, mouse_dx=0.0, mouse_dy=0.0, w=False, s=False, a=False, d=False):
@@ -76,6 +78,52 @@ class ProgressiveSession:
         self.camera.reset_accumulation()
         self._reset_converge()                       # the batches seen so far are of the old lens
         return lens
+
+    def set_shutter(self, close_camera=None, fraction=None):
+        """Camera motion blur (capi.shutter, include/gmupt_shutter.h): from the next frame on every fresh camera path draws a time in
+        [0, 1) and leaves the camera interpolated between the session's camera (shutter open) and a close pose; an attached lens or
+        projection runs on that camera.  set_shutter() with no argument detaches.
+        close_camera: an explicit close pose, a capi.CameraBuffer (or a camera with a `buffer`); it stays where it is put while the
+        session's camera goes on moving, until the next set_shutter or a resize(), which detaches it.
+        fraction=f in (0, 1]: the session sets the close pose itself on each later camera event -- a frame whose pose differs from the
+        pose of the frame before -- by one rule: the shutter spans the last f of the way from the previous pose to the new one, open =
+        the new camera, close = camera + (previous - camera) * f for the twelve pose components, in binary32.  (The box shutter does
+        not tell open from close, so the exposure is the segment of that motion that ends at the new pose; no later pose is needed.)
+        The close pose is then held: every frame of the accumulation that the event starts is made with the same shutter, until the
+        next event.  While the camera moves every frame is an event.  Before the first event, and after a resize() until the next
+        one, there is no previous pose of that aspect and nothing is attached: those frames are the frames without a shutter.
+        The accumulation restarts like after set_lens: the temporal history stays and is reprojected as usual (pick, the AOV planes
+        and the projection stay at t = 0), the convergence monitor is reset.  Returns the attached capi.shutter.Shutter, None when
+        detached or when the first close pose is still to come (fraction)."""
+        from .capi import shutter as S
+        if close_camera is not None and fraction is not None:
+            raise ValueError("set_shutter: either close_camera=pose or fraction=f, not both")
+        if fraction is not None and not (0.0 < float(fraction) <= 1.0):
+            raise ValueError("set_shutter: fraction=%r (a float in (0, 1])" % (fraction,))
+        self._shutter_fraction = float(fraction) if fraction is not None else None
+        self._shutter_prev = None
+        sh = S.from_camera(getattr(close_camera, "buffer", close_camera)) if close_camera is not None else None
+        S.set_shutter(self.renderer, sh)
+        self.camera.reset_accumulation()
+        self._reset_converge()                       # the batches seen so far are of the old shutter
+        return sh
+
+    def _follow_shutter(self):
+        """fraction mode, before the frame's camera is set: on a camera event the close pose of the accumulation it starts (set_shutter
+        has the rule); on any other frame nothing, the attached shutter is held."""
+        from .capi import shutter as S
+        cam = S.from_camera(self.camera.buffer)
+        prev, self._shutter_prev = self._shutter_prev, cam
+        if prev is None:
+            S.set_shutter(self.renderer, None)       # no previous pose of this aspect yet
+            return
+        if bytes(prev) == bytes(cam):
+            return
+        sh, f = S.from_camera(self.camera.buffer), np.float32(self._shutter_fraction)
+        for name in ("position", "upperLeftCorner", "horizontal", "vertical"):
+            a, b = np.array(getattr(cam, name)[:], np.float32), np.array(getattr(prev, name)[:], np.float32)
+            getattr(sh, name)[:] = [float(x) for x in (a + ((b - a).astype(np.float32) * f).astype(np.float32)).astype(np.float32)]
+        S.set_shutter(self.renderer, sh)
 
     def set_projection(self, kind, fov=None, extent=None):
         """Another camera projection (capi.projection, include/gmupt_projection.h): kind "orthographic" (extent: the world-space height
@@ -310,6 +358,7 @@ class ProgressiveSession:
         self.width, self.height = width, height
         self.renderer.resize(width, rows if rows is not None else height)
         self.camera.update_resolution(width, height)
+        self._shutter_prev = None                    # the renderer detached the shutter: a close pose is one of the old aspect
         self._epoch += 1
         self._reset_converge()
 
@@ -413,6 +462,8 @@ class ProgressiveSession:
             self._epoch += 1                         # this frame clears the target: a new accumulation
             if self._planned:
                 self._detach_plan()                  # the restarted frame has no error plane yet
+        if self._shutter_fraction is not None:
+            self._follow_shutter()
         self.renderer.set_camera(self.camera.buffer)
         self.renderer.iterate()                      # Renderer::draw
         self.frames += 1
